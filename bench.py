@@ -6,9 +6,13 @@ generated in the step kernel + the full BaseEnv.step pipeline + the auto-reset o
 with the tick, ONE step_kernel launch.  Workload =
 BASELINE.json configs[1]: 2 cops vs 1 thief, labyrinth map, 4096 envs per GPU, 64 rays/agent.
 Env slots shard across GPUs with no data-path collective (weak scaling); only the timing uses a
-barrier + MAX all-reduce.  Prints ONE JSON line on rank 0; at N = 1 it also carries `extra`: the other
-BASELINE shapes measured in the same run (kernel_ms each) and the learner's collect + update rate on the headline workload
-(SURVEY 8f rank 2); the headline stays configs[1].
+barrier + MAX all-reduce.  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only: set up, burn in, warm up, time the --steps steps, write the last step's outputs
+(--dump-outputs DIR) and print the line.  --full adds everything else, in the same run: at N = 1 `extra` (the other BASELINE
+shapes, kernel_ms each, the resident-rollout legs and the learner's collect + update rate on the headline workload, SURVEY 8f
+rank 2), `cpu_baseline`, the HBM stream copy and the replayed PMC profiles of `roofline`; at N > 1 the agh-map shard and the
+learner under the job's group.  The headline stays configs[1] either way.
 """
 from __future__ import annotations
 
@@ -214,6 +218,31 @@ def timed_rollout(sim, T: int, fence, hip: "HipEvents", first_tick: int, reps: i
     return elapsed, sum(hip.elapsed_ms(a, b) for a, b in ev) / (reps * T), reps
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(sim, out_dir: Path, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step handed its caller -- CatSim.step_fused's output tensors, [N, ...] each -- as
+    DIR/<name>.npy, widened to float32 without loss (float16 / 8-bit fields).  The inputs are fixed by the arguments (seed 0,
+    Philox actions keyed by tick and env id), so two builds run with the same arguments can be compared array for array.  Above
+    64 MB in all, the same seeded sample of env rows is taken from every array and its indices go to DIR/env_index.npy.  In a
+    multi-rank job each rank writes its own shard as <name>.rank<r>.npy, within its share of the 64 MB."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize(sim.device)
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in sim.out.items()}
+    total, limit = sum(a.nbytes for a in arrays.values()), DUMP_LIMIT_BYTES // world
+    suffix = f".rank{rank}" if world > 1 else ""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    if total > limit:
+        keep = max(1, sim.N * limit // total)
+        rows = np.sort(np.random.default_rng(0).choice(sim.N, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        np.save(out_dir / f"env_index{suffix}.npy", rows.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}{suffix}.npy", a)
+
+
 def source_sha16() -> str:
     """sha256 of the shipped env-core source, first 16 hex digits: what a committed profile must have been collected on to describe this build."""
     import hashlib
@@ -388,12 +417,20 @@ def main() -> None:
                     "lengths, so that a short timed region (the driver's --steps 20 --warmup 5) sees the batch in the middle of an episode, "
                     "agents spread over the map, and not the ticks after a reset (every env of a random-action labyrinth batch times out at "
                     "tick 400 together: 400 would land on the next reset); kernel time there = the whole-episode average (DESIGN 5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE shapes (the `extra` object)")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the other BASELINE shapes and the resident-rollout legs (`extra`), the "
+                    "learner legs, the CPU baseline, the HBM stream copy and the replayed PMC profiles of `roofline`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other BASELINE shapes (the `extra` object)")
     ap.add_argument("--rollout-ticks", type=int, default=64, help="T of the resident-rollout legs in `extra` (cat_rollout_fused)")
-    ap.add_argument("--shape-only", action="store_true", help="profiling runs of one shape (tools/collect_profiles.sh): this workload's one-launch-per-tick "
-                    "region and its resident-rollout leg only -- no other shapes, no learner legs, no CPU baseline")
+    ap.add_argument("--shape-only", action="store_true", help="with --full, profiling runs of one shape (tools/collect_profiles.sh): this workload's "
+                    "one-launch-per-tick region and its resident-rollout leg only -- no other shapes, no learner legs, no CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one handed its caller (CatSim.step_fused's "
+                    "output tensors) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.shape_only and not args.full:
+        ap.error("--shape-only restricts --full to one shape: pass both")
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and (world_env is None or (world_env == "1" and "RANK" not in os.environ)):
@@ -455,9 +492,11 @@ def main() -> None:
         sim.step_fused(None, tick=t, auto_reset=True)
     elapsed, tick_ms, n_timed, tick_method = timed_steps(sim, args.steps, args.warmup, fence, hip, first_tick=args.burn_in)
     elapsed = max_over_ranks(elapsed, device=None if rehearse else dev)   # the slowest rank bounds the whole-job rate
+    if args.dump_outputs:
+        dump_outputs(sim, Path(args.dump_outputs), rank, world)
     TR = args.rollout_ticks
     roll = None
-    if not args.no_extras or args.shape_only:   # the resident rollout launch on the same running batch (value stays one launch per tick)
+    if args.full and (not args.no_extras or args.shape_only):   # the resident rollout launch on the same running batch (value stays one launch per tick)
         r_el, r_kms, r_n = timed_rollout(sim, TR, fence, hip, first_tick=args.burn_in + args.warmup + args.steps)
         r_el = max_over_ranks(r_el, device=None if rehearse else dev)
         roll = (r_el, r_kms, r_n)
@@ -472,7 +511,7 @@ def main() -> None:
         dist.all_gather_object(offsets, int(cfg.env_id_offset))
 
     copy_gbs = None
-    if rank == 0 and world == 1:   # the HBM peak as a stream copy measures it on this box (read + write bytes)
+    if args.full and rank == 0 and world == 1:   # the HBM peak as a stream copy measures it on this box (read + write bytes)
         a = torch.empty(1 << 28, dtype=torch.float32, device=dev); b = torch.empty_like(a)   # 1 GiB each
         b.copy_(a); torch.cuda.synchronize(dev)
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -509,14 +548,14 @@ def main() -> None:
         return ent
 
     extra = None
-    if world > 1 and not args.no_extras and not args.shape_only:    # BASELINE configs[2]: agh-map, 32768 envs over 8 GPUs = 4096 per GPU, all ranks
+    if args.full and world > 1 and not args.no_extras and not args.shape_only:    # BASELINE configs[2]: agh-map, 32768 envs over 8 GPUs = 4096 per GPU, all ranks
         label, w = EXTRA_WORKLOADS[0]
         extra = {f"agh-map 2v1 x4096 per GPU (configs[2]), {world} GPUs": measure_extra(w)}
         # configs[2]'s other half: MAPPO on the sharded envs, gradients all-reduced under the SAME process group the timing uses
         lt = learner_throughput("agh-map", w["envs"], args.rays, rank=rank, world=world, reduce_device=None if rehearse else dev)
         lt["rccl_ranks"] = rccl_ranks
         extra[f"learner_collect_plus_update, {world} GPUs (agh-map 2v1 x4096 per GPU, CFG_AGENT)"] = lt
-    if rank == 0 and world == 1 and not args.no_extras and not args.shape_only:   # the other BASELINE shapes, same process, same box
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.shape_only:   # the other BASELINE shapes, same process, same box
         extra = {label: measure_extra(w) for label, w in EXTRA_WORKLOADS}
         extra["learner_collect_plus_update"] = learner_throughput(args.map, cfg.n_envs, args.rays)
         extra["learner_collect_plus_update, 90 rays"] = learner_throughput(args.map, cfg.n_envs, 90)
@@ -531,7 +570,7 @@ def main() -> None:
         # replayed from the committed PMC summary of this exact workload and labelled as such
         traffic = valu = traffic_source = traffic_regime = traffic_from_reset = None
         wl = {"map": args.map, "envs": cfg.n_envs, "rays": R, "cops": args.cops, "thieves": args.thieves}
-        prof = find_profile(wl, one_tick_kernel)   # newest round whose workload and kernel match
+        prof = find_profile(wl, one_tick_kernel) if args.full else None   # newest round whose workload and kernel match
         if prof is not None:
             traffic, valu = prof["hbm_bytes_per_launch"], prof.get("valu")
             traffic_regime = prof.get("regime", "from reset (--burn-in 0: 25 launches straight after the reset)")
@@ -563,23 +602,24 @@ def main() -> None:
                        "envs_per_gpu": cfg.n_envs, "rays": R, "agents": A, "map": args.map,
                        "parallelism": f"env-sharded x{world}, no data-path collective",
                        "episodes_reset_per_gpu": episodes, "burn_in_steps": args.burn_in, "env_id_offsets": offsets},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_regime": traffic_regime,
-                         "traffic_from_reset": traffic_from_reset, "traffic_source": traffic_source,
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "kernel": one_tick_kernel, "kernel_ms": tick_ms, "kernel_launches_timed": n_timed, "kernel_ms_method": tick_method,
-                         "algorithmic_bytes_per_launch": bytes_launch, "valu": valu, "valu_source": traffic_source,
-                         "compute": compute_block(valu), "profile_stale": stale, "profile_source_sha16": prof.get("source_sha16") if prof else None,
-                         "profile_git_head": prof.get("git_head") if prof else None, "shipped_source_sha16": source_sha16(),
-                         "hbm_stream_copy_GBs": copy_gbs,
-                         "frac_of_stream_copy": (achieved / copy_gbs) if copy_gbs else None,
+                         "algorithmic_bytes_per_launch": bytes_launch,
                          "note": "path is FP64-VALU/LDS bound, not HBM bound (SURVEY 8d); fraction reported as contracted"},
         }
+        if args.full:   # the replayed PMC profile of this workload and the stream copy measured above
+            line["roofline"].update({
+                "traffic": traffic, "traffic_regime": traffic_regime, "traffic_from_reset": traffic_from_reset, "traffic_source": traffic_source,
+                "valu": valu, "valu_source": traffic_source, "compute": compute_block(valu), "profile_stale": stale,
+                "profile_source_sha16": prof.get("source_sha16") if prof else None, "profile_git_head": prof.get("git_head") if prof else None,
+                "shipped_source_sha16": source_sha16(), "hbm_stream_copy_GBs": copy_gbs,
+                "frac_of_stream_copy": (achieved / copy_gbs) if copy_gbs else None})
         if timing_backend:
             line["config"]["timing_reductions"] = timing_backend
             line["config"]["rccl_ranks"] = rccl_ranks     # what the RCCL group reported; null = the timing went over gloo
         if extra is not None:
             line["extra"] = extra
-        if not args.no_cpu_baseline and world == 1:   # reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported at N=1 only
             line["cpu_baseline"] = cpu_baseline(cfg, cmap)
     # device-side error words of every sim of every rank (the reference raises at once on a bad call, entity.py:126-134; the launches here are
     # asynchronous, so the kernels flag and the host reads the word after each leg): the line carries the OR over ranks and legs, and a run that

@@ -53,3 +53,39 @@ def test_plain_multi_gpu_command_is_a_launcher_invocation(monkeypatch):
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and cmd[cmd.index("--nproc-per-node") + 1] == "4"
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-6:] == ["--gpus", "4", "--steps", "20", "--warmup", "5"]
     assert "RANK" not in seen["env"] and seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_arguments_a_run_cannot_honour_are_refused(monkeypatch, capsys):
+    import pytest
+    for argv, msg in ((["--steps", "0"], "--steps must be at least 1"), (["--shape-only"], "--shape-only restricts --full")):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        with pytest.raises(SystemExit) as exc:
+            bench.main()
+        assert exc.value.code == 2 and msg in capsys.readouterr().err
+
+
+def test_dumped_outputs_are_float32_and_a_large_batch_keeps_the_same_seeded_rows(tmp_path, monkeypatch):
+    """--dump-outputs on host tensors: every output field widened to float32 without loss; over the size limit, one seeded sample of
+    env rows is taken from every array and its indices are written beside them, the same rows on every run."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    N, gen = 500, torch.Generator().manual_seed(1)
+    sim = type("FakeSim", (), {})()
+    sim.device, sim.N = torch.device("cpu"), N
+    sim.out = {"obs_distance": (torch.rand(N, 3, 8, generator=gen) * 500).half(), "obs_type": torch.randint(0, 4, (N, 3, 8), generator=gen, dtype=torch.uint8),
+               "reward": torch.randn(N, 3, generator=gen), "winner": torch.randint(-1, 2, (N,), generator=gen, dtype=torch.int8)}
+    bench.dump_outputs(sim, tmp_path / "all", 0, 1)
+    for k, v in sim.out.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy())
+    assert not (tmp_path / "all" / "env_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20_000)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(sim, tmp_path / run, 0, 1)
+    rows = np.load(tmp_path / "s1" / "env_index.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "env_index.npy")) and 0 < len(rows) < N
+    assert np.all(np.diff(rows) > 0) and rows[-1] < N
+    assert sum(np.load(tmp_path / "s1" / f"{k}.npy").nbytes for k in sim.out) <= 20_000
+    for k, v in sim.out.items():
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), v.float().numpy()[rows.astype(np.int64)])

@@ -24,7 +24,7 @@ def test_two_rank_bench_prints_one_aggregate_line():
     envs, steps = 1024, 60
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "10",
-           "--envs", str(envs)]
+           "--envs", str(envs), "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

@@ -96,7 +96,7 @@ def test_eight_ranks_share_one_self_play_job(tmp_path):
         assert sorted(p.name for p in (tmp_path / d).glob("*.pt")) == [f"{role}_iter_{i}.pt" for i in range(4)]
 
 
-def _refusing_worker(rank, world, port, q):
+def _refusing_worker(rank, world, port, out_dir, q):
     sys.path.insert(0, str(ROOT))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -104,7 +104,7 @@ def _refusing_worker(rank, world, port, q):
     from as_cops_and_thieves_amd.selfplay.mappo import RoleConfig, TrainerConfig
     rc = RoleConfig(learning_epochs=1, mini_batches=2)
     try:
-        self_play.run_self_play("squarinth", 3, "/nonexistent", iterations=1, trainer_cfg=TrainerConfig(horizon=4, timesteps=8), role_cfg={"cop": rc, "thief": rc},
+        self_play.run_self_play("squarinth", 3, out_dir, iterations=1, trainer_cfg=TrainerConfig(horizon=4, timesteps=8), role_cfg={"cop": rc, "thief": rc},
                                 env_factory=lambda n, s, off=0: None, log=lambda *a: None)
         q.put((rank, "no error"))
     except ValueError as exc:
@@ -112,7 +112,7 @@ def _refusing_worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_a_shard_too_small_for_the_minibatches_is_refused_by_every_rank_together():
+def test_a_shard_too_small_for_the_minibatches_is_refused_by_every_rank_together(tmp_path):
     """3 envs over 2 ranks with two minibatches per update: rank 1's single env cannot fill them.  Every rank computes every rank's shard and raises
     the same error before anything is built -- a rank failing alone would leave the other waiting in the trainer's first all-reduce."""
     with socket.socket() as s:
@@ -120,7 +120,7 @@ def test_a_shard_too_small_for_the_minibatches_is_refused_by_every_rank_together
         port = s.getsockname()[1]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_refusing_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_refusing_worker, args=(r, 2, port, tmp_path, q)) for r in range(2)]
     for p in procs:
         p.start()
     got = sorted(q.get(timeout=120) for _ in range(2))

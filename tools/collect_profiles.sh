@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: per BASELINE shape, a rocprofv3 kernel trace + PMC passes (one counter group per pass, with --kernel-trace only) of the
-# bench command the driver runs (--steps 20 --warmup 5 after the burn-in ticks) restricted to that shape (--shape-only: the
+# bench command the driver runs (--steps 20 --warmup 5 after the burn-in ticks) restricted to that shape (--full --shape-only: the
 # one-launch-per-tick region + the resident-rollout leg of the SAME workload), summarised into profiles/<tag>_*:
 #   <tag>_<shape>_kernel_stats.csv   trace: tick_kernel / rollout_kernel rows      <tag>_<shape>_pmc_summary.txt   counters
 #   <tag>_traffic_<shape>.json       tick_kernel, last 25 launches                  <tag>_traffic_<shape>_rollout.json   rollout_kernel, last 4
@@ -20,7 +20,7 @@ ARGS[3v2]="--map grandbyrinth --cops 3 --thieves 2 --envs 8192"; KEY[3v2]='{"map
 ARGS[mixed]="--map mixed --envs 16384";                  KEY[mixed]='{"map": "mixed", "envs": 16384, "rays": 64, "cops": 2, "thieves": 1}'
 ARGS[r90]="--map labyrinth --envs 4096 --rays 90";       KEY[r90]='{"map": "labyrinth", "envs": 4096, "rays": 90, "cops": 2, "thieves": 1}'
 for sh in $shapes; do
-  a="${ARGS[$sh]} --steps 20 --warmup 5 --shape-only"
+  a="${ARGS[$sh]} --steps 20 --warmup 5 --full --shape-only"
   d=$out/$sh; rm -rf $d; mkdir -p $d
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $d/trace -o t -- python3 bench.py $a > $d/bench_under_rocprof.json 2> $d/trace.err
   echo "$sh trace done" >> $out/progress.txt

@@ -96,7 +96,7 @@ out = {
     "formula": "(2 * FETCH_SIZE + WRITE_SIZE) * 1024 -- FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half the bytes of a "
                "coalesced stream); this kernel mixes 16-byte record loads with 4/8-byte table gathers, so the read side is an upper estimate",
     "collected_with": f"tools/collect_profiles.sh {tag}: rocprofv3 --kernel-trace --pmc <one group per pass> -- python3 bench.py <shape> --steps 20 --warmup 5 "
-                      "--shape-only, counters of the kernel's last launches (25 tick_kernel / 4 rollout_kernel)",
+                      "--full --shape-only, counters of the kernel's last launches (25 tick_kernel / 4 rollout_kernel)",
     "source": str(summary.relative_to(root)) if summary.is_relative_to(root) else str(summary),
     "valu": {
         "valu_insts_per_wave": val["SQ_INSTS_VALU"] / per_step, "salu_insts_per_wave": val["SQ_INSTS_SALU"] / per_step,
