@@ -29,6 +29,8 @@ STATE_FIELDS = ("pos", "vel", "vbias", "tc", "leaf_bb", "wall_shape", "wall_age"
 WALL_CACHE = 8
 DEVERR_BAD_ACTION, DEVERR_CONTACT_DROPPED, DEVERR_SCHEDULER = 1, 2, 4
 
+GATE_NONE, GATE_INDEX, GATE_TREE = 0, 1, 2   # cat_config.bbtree_gate (CAT_GATE_*)
+
 ERRORS = {-1: "CAT_ERR_BAD_CONFIG", -2: "CAT_ERR_BAD_MAP", -3: "CAT_ERR_BAD_SLOT_MAP",
           -4: "CAT_ERR_NO_DEVICE", -5: "CAT_ERR_HIP", -6: "CAT_ERR_BAD_ARG"}
 
@@ -126,6 +128,12 @@ def lib() -> C.CDLL:
     L.cat_grid_free_host.restype = None
     L.cat_map_wall_bb_depth_host.argtypes = [vp, C.c_size_t, C.c_double]
     L.cat_map_wall_bb_depth_host.restype = i32
+    if hasattr(L, "cat_bbtree_host"):
+        L.cat_bbtree_host.argtypes = [vp, C.c_size_t, vp, vp, i32, vp, vp]
+        L.cat_bbtree_host.restype = i32
+    if hasattr(L, "cat_debug_tree_counts"):      # diagnostic builds only (-DCAT_TREE_COUNTS)
+        L.cat_debug_tree_counts.argtypes = [vp, i32]
+        L.cat_debug_tree_counts.restype = i32
     for name in ("cat_create", "cat_destroy", "cat_reset", "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_get_state",
                  "cat_set_state", "cat_random_actions", "cat_set_seed", "cat_device_errors", "cat_arm_kernel_timing", "cat_num_agents", "cat_num_shapes", "cat_selftest_arith", "cat_debug_grid_lookup"):
         getattr(L, name).restype = i32
@@ -136,4 +144,5 @@ def lib() -> C.CDLL:
 EXPORTED_SYMBOLS = ("cat_abi_version", "cat_one_tick_kernel", "cat_rollout_kernel", "cat_chunks_per_unit", "cat_last_error", "cat_create", "cat_destroy", "cat_reset",
                     "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_get_state", "cat_set_state", "cat_random_actions",
                     "cat_set_seed", "cat_device_errors", "cat_arm_kernel_timing", "cat_num_agents", "cat_num_shapes", "cat_selftest_arith", "cat_debug_grid_lookup",
-                    "cat_grid_build_host", "cat_grid_lookup_host", "cat_grid_bytes_host", "cat_grid_free_host", "cat_map_wall_bb_depth_host")
+                    "cat_grid_build_host", "cat_grid_lookup_host", "cat_grid_bytes_host", "cat_grid_free_host", "cat_map_wall_bb_depth_host",
+                    "cat_bbtree_host")

@@ -79,6 +79,12 @@ struct Params {
     int item_cap;           // fan_slot: items its list holds (itbb / ialpha / itm arrays of a scratch union); the chunks per unit are per map: GridDesc::span
     unsigned pool_magic; int pool_shift;   // ring position of entry i: i & pool_mask where the capacity is a power of two (pool_shift < 0), else i - capacity * (i / capacity)
                                            // with the quotient by multiply-high and shifts (unsigned division by an invariant, computed by cat_create)
+    // Chipmunk's static tree of every map (bbtree_gate = CAT_GATE_TREE only; null otherwise), read by the rare rays whose wall result depends on the visiting
+    // order (fan_chunk's slow path).  Node n of the sim: tree_bb[4n ..] its bb (l b r t), tree_link[4n ..] = child a, child b, parent (-1 at the root), wall id
+    // (leaf) or -1.  tree_root[m]: the root node of map m.
+    const double *tree_bb;
+    const int *tree_link;
+    const int *tree_root;
 };
 
 // Problem dimensions as seen by the device code: either read from the parameter block (DynDims) or compile-time
@@ -88,6 +94,7 @@ struct Params {
 // spilled SGPRs fixed, 107 - 134 + 64 B of scratch generic -- see "opaque roots" below).
 struct DynDims {
     static constexpr bool kFixed = false;
+    static constexpr bool kTree = false;   // walls visited in Chipmunk's tree order (TreeDims) instead of index order
     static __device__ __forceinline__ int A(const Params &p) { return p.A; }
     static __device__ __forceinline__ int R(const Params &p) { return p.R; }
     static __device__ __forceinline__ int n_cops(const Params &p) { return p.n_cops; }
@@ -97,6 +104,7 @@ struct DynDims {
 };
 template <int TA, int TR, int TC> struct FixDims {
     static constexpr bool kFixed = true;
+    static constexpr bool kTree = false;
     static constexpr int kNP = TA * (TA - 1) / 2, kNPs = kNP > 0 ? kNP : 1;
     static constexpr int kHotBytes = 96 * TA + 16;
     static constexpr int kColdBytes = ((TA * CAT_WALL_CACHE + kNPs) * 8 + (2 * TA * CAT_WALL_CACHE + kNPs) * 4 + 15) / 16 * 16;
@@ -107,6 +115,10 @@ template <int TA, int TR, int TC> struct FixDims {
     static __device__ __forceinline__ constexpr int rec_bytes(const Params &) { return kHotBytes + kColdBytes; }
     static __device__ __forceinline__ constexpr int hot_bytes(const Params &) { return kHotBytes; }
 };
+
+// bbtree_gate = CAT_GATE_TREE: the generic dimensions with the walls of every segment query visited in the order of Chipmunk's static tree (fan_chunk,
+// termination_captured).  Only the chunk form is instantiated with it.
+struct TreeDims : DynDims { static constexpr bool kTree = true; };
 
 // Which form of the ray fan an instantiation carries: 0 = fan_chunk (one 64-ray chunk of one agent per work unit: any map),
 // 1 = fan_group (the agents of a group per unit, only the rays that have a candidate on the lanes: maps whose rays meet few walls).

@@ -299,6 +299,80 @@ __device__ void agent_setup(const Lds &L, const Params &p, const GridDesc &gd, i
     wave_sync();
 }
 
+#ifdef CAT_TREE_COUNTS
+// Diagnostic build only (-DCAT_TREE_COUNTS, tools/query_order_bench.py): [0] rays of tree-order chunks with a wall hit, [1] those that took the slow path
+__device__ unsigned long long g_tree_counts[2];
+__device__ __forceinline__ void tree_count(int which)
+{
+    const unsigned long long m = __ballot(true);
+    if ((int)__builtin_ctzll(m) == (int)(threadIdx.x % 64)) atomicAdd(&g_tree_counts[which], (unsigned long long)__popcll(m));
+}
+extern "C" int cat_debug_tree_counts(unsigned long long *out2, int reset)
+{
+    unsigned long long h[2];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tree_counts), sizeof h) != hipSuccess) return -1;
+    out2[0] = h[0]; out2[1] = h[1];
+    if (reset) { h[0] = h[1] = 0ull; if (hipMemcpyToSymbol(HIP_SYMBOL(g_tree_counts), h, sizeof h) != hipSuccess) return -1; }
+    return 0;
+}
+#endif
+
+// Tree order (bbtree_gate = CAT_GATE_TREE): the walls' result of one ray from the order-free summary of its wall items -- the smallest alpha a1 (item
+// fi1, gate value tbb1), the second smallest a2 (1 if none), a1 tied.  The tables list every wall that the thin segment enters (t_bb < 1) and that
+// hits, and every such wall got an item; if a1 is unique and tbb1 < a2, the wall of a1 wins under EVERY visiting order: before its turn the best alpha
+// cannot fall below a2, so its leaf and every ancestor (whose bb holds the leaf's: entered no later) pass the gate, and after it nothing is smaller
+//.  No hit: "no hit" under every order.  Otherwise (the slow path: ties, or a second hit that can
+// come first) the ray's lane descends the tree as [CP SubtreeSegmentQuery] does.  Writes best_a / best_fi (1.0 / -1: no hit).
+template <class D>
+__device__ __forceinline__ void tree_walls_result(const Lds &L, const Params &p, int lane, int S, float cmax, double ax, double ay, double bx, double by,
+                                                  double rdx, double rdy, double rix, double riy, int near0, int near1, double a1, double a2, double tbb1,
+                                                  int fi1, bool tie, double &best_a, int &best_fi)
+{
+    (void)lane; (void)S; (void)near0; (void)near1;
+    best_a = 1.0; best_fi = -1;
+    if (!(a1 < 1.0)) return;
+#ifdef CAT_TREE_COUNTS
+    tree_count(0);
+#endif
+    if (!tie && tbb1 < a2) { best_a = a1; best_fi = fi1; return; }
+#ifdef CAT_TREE_COUNTS
+    tree_count(1);
+#endif
+    // Depth first without a stack: the child whose bb the segment enters first is descended first (b on equal entry times), a child only if its
+    // entry lies before the best alpha so far; coming back up from a child, the order at its parent is recomputed (the same two entry times) to know
+    // whether the other child is still to be tried.  Nodes from global memory (L2: only rare rays read them).
+    GAS const double *tb = G(p.tree_bb);
+    GAS const int *tl = G(p.tree_link);
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    auto entry = [&](int n) {
+        const f64x2 lo = *(GAS const f64x2 *)(tb + 4 * n), hi = *(GAS const f64x2 *)(tb + 4 * n + 2);
+        const double nb[4] = {lo.x, lo.y, hi.x, hi.y};
+        return bb_segment_query(nb, ax, ay, rdx, rdy, rix, riy);
+    };
+    const double wall_r = p.wall_r, r2 = p.ray_radius;
+    int node = G(p.tree_root)[G(p.block_map)[blockIdx.x]], from = -1;
+    for (int it = 0; it < 6 * CAT_MAX_SHAPES && node >= 0; it++) {   // (a node is entered once from above and once from each child)
+        const i32x4 lk = *(GAS const i32x4 *)(tl + 4 * node);
+        int next = -1;   // -1: back up to the parent
+        if (lk.w >= 0) {   // a leaf: the wall's own query, with the "origin inside" rule of the items (exact here: any number of such walls)
+            const int s = lk.w;
+            double al = 0.0;
+            int f = kFeatNear;
+            if (!poly_point_within(L, s, wall_r, ax, ay, r2)) { poly_query_feat(L, cmax, true, s, wall_r, 0.0, 0.0, ax, ay, bx, by, r2, al, f); f = f < 0 ? 0 : f; }
+            if (al < best_a) { best_a = al; best_fi = (s << 6) | f; }
+        } else {
+            const double ta = entry(lk.x), tv = entry(lk.y);
+            const bool a_first = ta < tv;
+            const int first = a_first ? lk.x : lk.y, second = a_first ? lk.y : lk.x;
+            const double tf = a_first ? ta : tv, ts = a_first ? tv : ta;
+            if (from < 0 && tf < best_a) next = first;
+            else if ((from < 0 || from == first) && ts < best_a) next = second;
+        }
+        if (next >= 0) { from = -1; node = next; }
+        else { from = node; node = lk.z; }
+    }
+}
+
 // One 64-ray chunk c (agent c / cpa, rays (c % cpa) * 64 ...) of the env whose env area is in L; the scratch
 // union of L is the calling wave's.  Writes the chunk's observations to the env's output staging.
 template <class D>
@@ -368,11 +442,17 @@ __device__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, c
                 int rel = k - dk; if (rel < 0) rel += R;
                 if (rel < dc) dynmask |= 1u << j;
             }
-        const int cnt = cnt_w + __popc(dynmask);
+        const int cnt = cnt_w + (D::kTree ? 0 : __popc(dynmask));   // (tree order: the walls only, the agents come after the walls' result)
         PHASE(pc, 20);
         double best_a = 1.0;
         int best_fi = -1;   // id << 6 | feature of the accepted item
         int jj0 = 0;
+        // tree order: the walls' order-free summary (tree_walls_result) -- smallest alpha a1 with its item fi1 and gate value tbb1, second smallest a2, a1 tied
+        double a1 = 1.0, a2 = 1.0, tbb1 = 0.0;
+        int fi1 = -1;
+        bool tie = false;
+        const bool root_leaf = D::kTree && S == 1;   // a root that is a leaf is visited ungated (DESIGN D6)
+        (void)a1; (void)a2; (void)tbb1; (void)fi1; (void)tie; (void)root_leaf;
         while (__ballot(cnt > jj0) != 0ull) {
             // ---- pack the items (ray, jj) for jj in [jj0, jj1) j-major
             int n_items = 0, jj = jj0;
@@ -399,7 +479,10 @@ __device__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, c
                     // ray's best alpha NOW can never be visited (best only decreases): it gets no item.
                     if (gate) tbb = bb_segment_query((id < S) ? (L.bb + kBB * id) : (L.fleaf + 4 * (id - S)), ax, ay, rdx, rdy, rix, riy);
                 }
-                const bool live = has && tbb < best_a;
+                bool live = has && tbb < best_a;
+                // tree order: the running best of index order gates no wall -- a wall gets its alpha whenever the thin segment enters its bb (a root
+                // that is a leaf is visited ungated)
+                if constexpr (D::kTree) live = has && (tbb < 1.0 || root_leaf);
                 const unsigned long long m = __ballot(live);
                 const int c = __popcll(m);
                 if (n_items + c > kItemCap) break;
@@ -441,17 +524,35 @@ __device__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, c
             }
             wave_sync();
             PHASE(pc, 6);
-            // ---- each ray walks its own items in index order
+            // ---- each ray walks its own items in index order (tree order: into the order-free summary)
             for (int q = jj0; q < jj1; q++) {
                 const int t = cnt > q ? (int)L.itemidx[(q - jj0) * kLanes + lane] : 0xFFFF;
                 if (t != 0xFFFF) {
                     const double al = L.ialpha[t];
-                    if (al < best_a && L.itbb[t] < best_a) { best_a = al; best_fi = L.itm[t]; }   // t_exit == best alpha
+                    if constexpr (D::kTree) {
+                        if (al < a1) { a2 = a1; a1 = al; fi1 = L.itm[t]; tbb1 = L.itbb[t]; tie = false; }
+                        else if (al == a1 && al < 1.0) { a2 = al; tie = true; }
+                        else if (al < a2) a2 = al;
+                    } else if (al < best_a && L.itbb[t] < best_a) { best_a = al; best_fi = L.itm[t]; }   // t_exit == best alpha
                 }
             }
             wave_sync();
             PHASE(pc, 7);
             jj0 = jj1;
+        }
+        if constexpr (D::kTree) {
+            tree_walls_result<D>(L, p, lane, S, cmax, ax, ay, bx, by, rdx, rdy, rix, riy, near0, near1, a1, a2, tbb1, fi1, tie, best_a, best_fi);
+            // the agents after the walls, in index order, gated by the walls' result (the candidates the cone test found, as the items of index order)
+            unsigned dj = dynmask;
+            while (dj) {
+                const int j = __builtin_ctz(dj);
+                dj &= dj - 1;
+                if (!(bb_segment_query(L.fleaf + 4 * j, ax, ay, rdx, rdy, rix, riy) < best_a)) continue;
+                double al = 0.0;
+                int f = kFeatNear;
+                if (!((dnear_mask >> j) & 1u)) { poly_query_feat(L, cmax, false, 0, rc, L.ftc[2 * j], L.ftc[2 * j + 1], ax, ay, bx, by, r2, al, f); f = f < 0 ? 0 : f; }
+                if (al < best_a) { best_a = al; best_fi = ((S + j) << 6) | f; }
+            }
         }
         // ---- hit point -> f16 distance and class (entity.py:200-215, :222-241)
         unsigned d16 = d_empty, ty = CAT_EMPTY;
@@ -1034,7 +1135,7 @@ __device__ int termination_captured(const Lds &L, const Params &p, int S, int la
                 bool hit = false;
                 if (s < S) {
                     bool visit = true;
-                    if (p.gate) visit = bb_segment_query(L.bb + kBB * s, ax, ay, dx, dy, idx, idy) < 1.0;
+                    if (p.gate && !(D::kTree && S == 1)) visit = bb_segment_query(L.bb + kBB * s, ax, ay, dx, dy, idx, idy) < 1.0;   // (tree order, one wall: D6)
                     if (visit) {
                         SegInfo info = {0, 1.0, bx, by};
                         if (poly_point_distance(L, s, p.wall_r, ax, ay) <= 0.0) { info.hit = 1; info.alpha = 0.0; }

@@ -62,11 +62,15 @@ struct GridRowOut { std::vector<int> off, coff; std::vector<unsigned char> ent, 
 
 static void build_grids(const double *bb, int S, int R, const double *rdx, const double *rdy, double reach,
                         bool gate, double m_contact, double cell, GridHost &g, const int *hull_first, const int *hull_count,
-                        double rsum, double ray_radius)
+                        double rsum, double ray_radius, bool tree = false)
 {
+    // Tree order (bbtree_gate = CAT_GATE_TREE): rules 1 and 2 only.  Both are necessary for a wall to change the best alpha under ANY visiting order,
+    // and the device's order-free summary needs the alpha of every wall that is entered and hit, which rule 3 (proved for index order) does not keep.
+    // A single wall is the root of its tree and visited ungated (DESIGN D6): it is listed by rule 2 alone (rule 1 with the fat ray, which rule 2 implies).
+    if (tree && S == 1) gate = false;
     const double m_ray = gate ? 1e-6 : ray_radius + 1e-6;   // gate off: every wall the fat ray can touch counts as visited
     const double *planes = bb + 4 * (size_t)S;
-    bool by_hull = hull_first != nullptr, occlusion = hull_first != nullptr;
+    bool by_hull = hull_first != nullptr, occlusion = hull_first != nullptr && !tree;
     if (const char *e = getenv("CAT_GRID_HULLS")) { if (atoi(e) == 0) by_hull = false; }
     if (const char *e = getenv("CAT_GRID_OCCLUSION")) { if (atoi(e) == 0) occlusion = false; }
     double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
@@ -258,6 +262,82 @@ static void build_grids(const double *bb, int S, int R, const double *rdx, const
     g.rows_of.push_back(d.nx * d.ny * R);
 }
 
+// ---------------------------------------------------------------------- Chipmunk's static tree ----
+// The tree [CP cpBBTreeInsert] builds when the walls are inserted one after the other in index order (Map.populate_space adds them in file order):
+// node s < S is the leaf of wall s (its bb is the wall's bb, the static index has no velocity function); inner nodes follow in creation order.  An
+// insertion below an inner node descends into the child with the smaller cost  area(other child) + merged area(this child, new leaf), on equal costs
+// into the one nearer by [CP cpBBProximity], into b only if strictly better; where it meets a leaf (or the empty tree) a new inner node takes the
+// NEW leaf as child a and what it met as child b; every inner node on the way is merged with the new leaf's bb (exact min / max).  Nothing reorders
+// a static tree afterwards.
+struct TreeNode { double bb[4]; int a, b, parent, wall; };
+constexpr int kMaxTreeDepth = 48;   // cat_create refuses a tree-order map whose tree is deeper (the five maps shipped: 3 - 11)
+
+static void build_static_tree(const double *bb, int S, std::vector<TreeNode> &n, int &root, int &depth)
+{
+    n.assign(S > 0 ? 2 * (size_t)S - 1 : 0, TreeNode{});
+    for (int s2 = 0; s2 < S; s2++) { memcpy(n[s2].bb, bb + 4 * (size_t)s2, 32); n[s2].a = n[s2].b = n[s2].parent = -1; n[s2].wall = s2; }
+    auto mn = [](double x, double y) { return x < y ? x : y; };   // [CP cpfmin / cpfmax]
+    auto mx = [](double x, double y) { return x > y ? x : y; };
+    auto area = [](const double *x) { return (x[2] - x[0]) * (x[3] - x[1]); };
+    auto merged_area = [&](const double *x, const double *y) { return (mx(x[2], y[2]) - mn(x[0], y[0])) * (mx(x[3], y[3]) - mn(x[1], y[1])); };
+    auto proximity = [](const double *x, const double *y) { return std::fabs(x[0] + x[2] - y[0] - y[2]) + std::fabs(x[1] + x[3] - y[1] - y[3]); };
+    auto merge_into = [&](double *d, const double *y) { d[0] = mn(d[0], y[0]); d[1] = mn(d[1], y[1]); d[2] = mx(d[2], y[2]); d[3] = mx(d[3], y[3]); };
+    int next = S;
+    root = S > 0 ? 0 : -1;
+    for (int leaf = 1; leaf < S; leaf++) {
+        const double *lb = n[leaf].bb;
+        int at = root, up = -1;   // the subtree the leaf meets, and the inner node above it
+        bool in_b = false;
+        while (n[at].wall < 0) {
+            const int ca = n[at].a, cb = n[at].b;
+            double cost_a = area(n[cb].bb) + merged_area(n[ca].bb, lb), cost_b = area(n[ca].bb) + merged_area(n[cb].bb, lb);
+            if (cost_a == cost_b) { cost_a = proximity(n[ca].bb, lb); cost_b = proximity(n[cb].bb, lb); }
+            merge_into(n[at].bb, lb);
+            up = at;
+            in_b = cost_b < cost_a;
+            at = in_b ? cb : ca;
+        }
+        const int k = next++;
+        TreeNode &q = n[k];
+        q.a = leaf; q.b = at; q.wall = -1; q.parent = up;
+        memcpy(q.bb, lb, 32);
+        merge_into(q.bb, n[at].bb);
+        n[leaf].parent = k; n[at].parent = k;
+        if (up < 0) root = k;
+        else if (in_b) n[up].b = k;
+        else n[up].a = k;
+    }
+    depth = 0;
+    for (int s2 = 0; s2 < S; s2++) {
+        int d = 0;
+        for (int x = s2; n[x].parent >= 0; x = n[x].parent) d++;
+        depth = std::max(depth, d);
+    }
+}
+
+// Host-only: the static tree of one map's walls (what cat_create builds in tree order), for the CPU tests.  Writes up to max_nodes nodes:
+// bb[4 n ..] (l b r t) and link[4 n ..] = child a, child b, parent, wall id (leaf) or -1; returns the node count (2 S - 1) or an error.
+extern "C" int cat_bbtree_host(const void *blob, size_t size, double *bb_out, int *link_out, int max_nodes, int *root, int *depth)
+{
+    if (!blob || size < 64) return CAT_ERR_BAD_ARG;
+    int32_t h[16];
+    memcpy(h, blob, 64);
+    const int S = h[2];
+    if ((unsigned)h[0] != kBlobMagic || S < 1 || S > CAT_MAX_SHAPES || size < 64 + (2 + 4 * (size_t)S) * 8) return CAT_ERR_BAD_MAP;
+    std::vector<double> bb(4 * (size_t)S);
+    memcpy(bb.data(), static_cast<const unsigned char *>(blob) + 64 + 16, bb.size() * 8);
+    std::vector<TreeNode> n;
+    int r = -1, d = 0;
+    build_static_tree(bb.data(), S, n, r, d);
+    for (int k = 0; k < (int)n.size() && k < max_nodes; k++) {
+        if (bb_out) memcpy(bb_out + 4 * (size_t)k, n[k].bb, 32);
+        if (link_out) { link_out[4 * k] = n[k].a; link_out[4 * k + 1] = n[k].b; link_out[4 * k + 2] = n[k].parent; link_out[4 * k + 3] = n[k].wall; }
+    }
+    if (root) *root = r;
+    if (depth) *depth = d;
+    return (int)n.size();
+}
+
 // The most wall bounding boxes the bb of ONE agent circle can overlap at once, anywhere on the map: an upper bound on the wall
 // arbiters an agent can hold in one step ([CP cpSpaceCollideShapes] makes one only on a real contact), to be held against the
 // CAT_WALL_CACHE slots of the state record at cat_create instead of being discovered at run time (CAT_DEVERR_CONTACT_DROPPED).
@@ -365,10 +445,19 @@ template <class D, bool kExact> static void pooled_of(bool pool_roll, bool pool_
     if (pool_roll) rollout = rollout_kernel_pooled<WithFan<D, 1>, kExact>;
     if (pool_step) step = step_kernel_pooled<WithFan<D, 1>, kExact>;
 }
-static const char *select_kernels(int A, int R, int n_cops, int fan, bool pool_roll, bool pool_step, bool exact, KernelFn &reset, KernelFn &rollout, KernelFn &step)
+// tree: walls in Chipmunk's tree order (chunk form only, generic dimensions).  slot (may be null): whether the chosen chunk-form kernels carry fan_slot --
+// the fixed-dimension ones at 64 rays (with run-time dimensions, or at 90 rays, a unit of several chunks would need scratch): only then may cat_create
+// give a map several chunks per work unit.
+static const char *select_kernels(int A, int R, int n_cops, int fan, bool pool_roll, bool pool_step, bool exact, KernelFn &reset, KernelFn &rollout, KernelFn &step,
+                                  bool tree = false, bool *slot = nullptr)
 {
     const char *e = getenv("CAT_GENERIC_KERNEL");
     const bool generic = e && atoi(e) != 0;
+    if (slot) *slot = false;
+    if (tree) {
+        reset = reset_kernel<WithFan<TreeDims, 0>>; rollout = rollout_kernel<WithFan<TreeDims, 0>>; step = step_kernel<WithFan<TreeDims, 0>>;
+        return "generic, tree order";
+    }
     if ((pool_roll || pool_step) && fan == 1) {
         if (!generic && A == 3 && n_cops == 2 && R == 64 && !exact) {
             kernels_of<FixDims<3, 64, 2>>(fan, reset, rollout, step);
@@ -397,11 +486,11 @@ static const char *select_kernels(int A, int R, int n_cops, int fan, bool pool_r
         else pooled_of<DynDims, false>(pool_roll, pool_step, rollout, step);
         return "generic, pooled fan";
     }
-    if (!generic && A == 3 && n_cops == 2 && R == 64) { kernels_of<FixDims<3, 64, 2>>(fan, reset, rollout, step); return "3 agents (2 cops), 64 rays"; }
+    if (!generic && A == 3 && n_cops == 2 && R == 64) { kernels_of<FixDims<3, 64, 2>>(fan, reset, rollout, step); if (slot) *slot = true; return "3 agents (2 cops), 64 rays"; }
 #ifndef CAT_QUICK_BUILD   // diagnostic builds (tools/build_variant.sh -DCAT_QUICK_BUILD): the headline instantiation + the generic one only
     if (!generic && A == 3 && n_cops == 2 && R == 90) { kernels_of<FixDims<3, 90, 2>>(fan, reset, rollout, step); return "3 agents (2 cops), 90 rays"; }
     if (!generic && A == 2 && n_cops == 1 && R == 90) { kernels_of<FixDims<2, 90, 1>>(fan, reset, rollout, step); return "2 agents (1 cop), 90 rays"; }
-    if (!generic && A == 5 && n_cops == 3 && R == 64) { kernels_of<FixDims<5, 64, 3>>(fan, reset, rollout, step); return "5 agents (3 cops), 64 rays"; }
+    if (!generic && A == 5 && n_cops == 3 && R == 64) { kernels_of<FixDims<5, 64, 3>>(fan, reset, rollout, step); if (slot) *slot = true; return "5 agents (3 cops), 64 rays"; }
 #endif
     kernels_of<DynDims>(fan, reset, rollout, step);
     return "generic";
@@ -536,8 +625,8 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
     }
     const int A = cfg->n_cops + cfg->n_thieves;
     if (A < 1 || A > CAT_MAX_AGENTS || cfg->n_cops < 0 || cfg->n_thieves < 0 || cfg->n_rays < 1 ||
-        cfg->n_rays > CAT_MAX_RAYS || cfg->n_envs < 1 || A * kK > 64) {
-        snprintf(g_create_err, sizeof g_create_err, "bad config: agents=%d rays=%d envs=%d", A, cfg->n_rays, cfg->n_envs);
+        cfg->n_rays > CAT_MAX_RAYS || cfg->n_envs < 1 || A * kK > 64 || cfg->bbtree_gate > CAT_GATE_TREE) {
+        snprintf(g_create_err, sizeof g_create_err, "bad config: agents=%d rays=%d envs=%d bbtree_gate=%d", A, cfg->n_rays, cfg->n_envs, cfg->bbtree_gate);
         return CAT_ERR_BAD_CONFIG;
     }
     int ndev = 0;
@@ -625,6 +714,31 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
         if (geo_f.size() & 1) geo_f.push_back(0.0);  // keep 16-byte alignment of each map's base
         descs[m] = d;
     }
+    // ---- tree order: every map's static tree (node indices of the sim: the maps' trees one after the other)
+    const bool tree = cfg->bbtree_gate == CAT_GATE_TREE;
+    std::vector<TreeNode> tree_nodes;
+    std::vector<int> tree_roots;
+    if (tree) {
+        for (int m = 0; m < n_maps; m++) {
+            std::vector<TreeNode> tn;
+            int root = -1, depth = 0;
+            build_static_tree(geo_f.data() + descs[m].f64_off, descs[m].S, tn, root, depth);
+            if (depth > kMaxTreeDepth) {
+                snprintf(g_create_err, sizeof g_create_err, "map blob %d: its static tree is %d levels deep; tree order (bbtree_gate = %d) supports at most %d",
+                         m, depth, CAT_GATE_TREE, kMaxTreeDepth);
+                return CAT_ERR_BAD_MAP;
+            }
+            const int base = (int)tree_nodes.size();
+            for (TreeNode &q : tn) {
+                if (q.a >= 0) q.a += base;
+                if (q.b >= 0) q.b += base;
+                if (q.parent >= 0) q.parent += base;
+            }
+            tree_roots.push_back(base + root);
+            tree_nodes.insert(tree_nodes.end(), tn.begin(), tn.end());
+            if (getenv("CAT_VERBOSE")) fprintf(stderr, "[cat_sim] tree order, map %d: %d walls, static tree of %zu nodes, depth %d\n", m, descs[m].S, tn.size(), depth);
+        }
+    }
     const int N = cfg->n_envs;
     std::vector<int> slot((size_t)N, 0);
     for (int e = 0; e < N; e++) {
@@ -662,7 +776,7 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
             }
             build_grids(geo_f.data() + descs[m].f64_off, descs[m].S, cfg->n_rays, tab->ray_dx, tab->ray_dy, reach, cfg->bbtree_gate != 0,
                         cfg->ray_radius + 2e-6, cell, map_grid[(size_t)m], geo_i.data() + descs[m].i32_off, geo_i.data() + descs[m].i32_off + descs[m].S,
-                        cfg->wall_radius + cfg->ray_radius, cfg->ray_radius);
+                        cfg->wall_radius + cfg->ray_radius, cfg->ray_radius, tree);
             map_grid_max_row[(size_t)m] = map_grid[(size_t)m].max_row;
         }
     }
@@ -680,6 +794,7 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
         bool chunks_only = false, split = false;
         if (const char *e = getenv("CAT_FAN")) chunks_only = !strcmp(e, "chunks");
         if (const char *e = getenv("CAT_SPLIT")) split = atoi(e) != 0;
+        if (tree) chunks_only = true;   // tree order is carried by the chunk form only (whatever CAT_FAN / CAT_SPLIT / CAT_POOL say)
         std::vector<int> light, dense;
         for (int m = 0; m < n_maps; m++) (map_grid[(size_t)m].max_row <= 7 && cfg->n_rays <= kGroupRays && !chunks_only ? light : dense).push_back(m);
         if (!light.empty()) {   // the four-byte row must hold the longest list of the part in fields of the part's id width
@@ -754,6 +869,17 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
     TRY_ALLOC(dev_alloc(s, const_cast<double **>(&base.geo_f64), geo_f.size(), geo_f.data()));
     TRY_ALLOC(dev_alloc(s, const_cast<int **>(&base.geo_i32), geo_i.size(), geo_i.data()));
     TRY_ALLOC(dev_alloc(s, &base.err_word, 1, nullptr));
+    if (tree) {   // read-only, from global memory (only the rays of fan_chunk's slow path read them)
+        std::vector<double> tbb(4 * tree_nodes.size());
+        std::vector<int> tlink(4 * tree_nodes.size());
+        for (size_t k = 0; k < tree_nodes.size(); k++) {
+            memcpy(tbb.data() + 4 * k, tree_nodes[k].bb, 32);
+            tlink[4 * k] = tree_nodes[k].a; tlink[4 * k + 1] = tree_nodes[k].b; tlink[4 * k + 2] = tree_nodes[k].parent; tlink[4 * k + 3] = tree_nodes[k].wall;
+        }
+        TRY_ALLOC(dev_alloc(s, const_cast<double **>(&base.tree_bb), tbb.size(), tbb.data()));
+        TRY_ALLOC(dev_alloc(s, const_cast<int **>(&base.tree_link), tlink.size(), tlink.data()));
+        TRY_ALLOC(dev_alloc(s, const_cast<int **>(&base.tree_root), tree_roots.size(), tree_roots.data()));
+    }
     {   // ray-direction cone parameters: valid when the table is a uniform full circle
         const double two_pi = 6.283185307179586;
         const double a0 = atan2(tab->ray_dy[0], tab->ray_dx[0]);
@@ -833,10 +959,11 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
         for (GridDesc &d : grid_host.desc) d.span = d.span_tick = 1;
         {
             const int nch = A * ((cfg->n_rays + kLanes - 1) / kLanes);
-            const bool fixed_roster = !(getenv("CAT_GENERIC_KERNEL") && atoi(getenv("CAT_GENERIC_KERNEL")) != 0) && cfg->n_rays == 64 && ((A == 3 && cfg->n_cops == 2) || (A == 5 && cfg->n_cops == 3));
-            // (fan_slot is carried by the chunk-form kernels of fixed dimensions only -- select_kernels: 2v1 and 3v2 at 64 rays; 2v1 / 1v1 at 90 rays and the generic
-            //  kernels keep one chunk per unit: with run-time dimensions the unit needs scratch)
-            if (fan == 0 && fixed_roster && wide && grid_host.row_words == 1 && maxS + A <= 127 && nch >= 2 && grid_host.max_row + A - 1 <= 15) {
+            // (fan_slot is carried by the chunk-form kernels of fixed dimensions at 64 rays only -- select_kernels says whether the part's kernels are such; the
+            //  others keep one chunk per unit: with run-time dimensions the unit needs scratch)
+            bool carries_slot = false;
+            if (fan == 0) { KernelFn r0, r1, r2; select_kernels(A, cfg->n_rays, cfg->n_cops, fan, false, false, false, r0, r1, r2, tree, &carries_slot); }
+            if (fan == 0 && carries_slot && wide && grid_host.row_words == 1 && maxS + A <= 127 && nch >= 2 && grid_host.max_row + A - 1 <= 15) {
 #ifdef CAT_PHASE_TIMING
                 const size_t budget = 160 * 1024 - 4096;   // (the diagnostic build keeps its cycle accumulators in static LDS)
 #else
@@ -998,7 +1125,8 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
         }
         pt.wpb = wpb;
         pt.lds_bytes = pool_cap ? (size_t)p.lds_pool_off + (size_t)pool_cap * 8 : ls.total(wpb);
-        pt.kernel_variant = select_kernels(A, p.R, p.n_cops, fan, pool_cap != 0, pool_step, p.pool_shift >= 0, pt.reset_fn, pt.rollout_fn, pt.step_fn);
+        pt.kernel_variant = select_kernels(A, p.R, p.n_cops, fan, pool_cap != 0, pool_step, p.pool_shift >= 0, pt.reset_fn, pt.rollout_fn, pt.step_fn, tree);
+        if (getenv("CAT_VERBOSE")) fprintf(stderr, "[cat_sim] part %zu kernels: %s\n", pi + 1, pt.kernel_variant);
         pt.pool_step = pool_step;
         if (pt.lds_bytes > 64 * 1024) {
             hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(pt.step_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pt.lds_bytes);
@@ -1301,7 +1429,7 @@ extern "C" int cat_grid_build_host(const cat_config *cfg, const cat_tables *tab,
     gh->R = cfg->n_rays;
     build_grids(f.data() + 2, S, cfg->n_rays, tab->ray_dx, tab->ray_dy, cfg->ray_length + cfg->ray_radius + 1e-3,
                 cfg->bbtree_gate != 0, cfg->ray_radius + 2e-6, cell > 0 ? cell : 8.0, gh->g,
-                iv.data(), iv.data() + S, cfg->wall_radius + cfg->ray_radius, cfg->ray_radius);
+                iv.data(), iv.data() + S, cfg->wall_radius + cfg->ray_radius, cfg->ray_radius, cfg->bbtree_gate == CAT_GATE_TREE);
     finalize_rows(gh->g);
     *out = gh;
     return CAT_OK;

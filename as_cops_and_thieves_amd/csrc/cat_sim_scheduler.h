@@ -641,9 +641,12 @@ __device__ __forceinline__ void rollout_body(const Params *__restrict__ pp0, con
 #ifndef CAT_ABL_NOFAN      // diagnostic builds: a phase compiled out, for instruction counts by difference (tools/ablate_rollout.sh)
                 if constexpr (D::kFan == 1) fan_group<D>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, unit, gsz, pc);
                 else {
-                    const int nch = D::A(p) * ((D::R(p) + kLanes - 1) / kLanes), c0 = unit * gsz;
-                    unsigned chunks = 1u;   // one chunk per unit: fan_chunk; several: fan_slot, which hands back what its item list cannot hold
-                    if (D::kFixed && gsz > 1) chunks = fan_slot<D>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, c0, nch - c0 < gsz ? nch - c0 : gsz, pc);
+                    const int nch = D::A(p) * ((D::R(p) + kLanes - 1) / kLanes), c0 = unit * gsz, nq = nch - c0 < gsz ? nch - c0 : gsz;
+                    // every chunk of the unit to fan_chunk, one after the other -- unless fan_slot runs, which hands back only what its item list cannot hold.
+                    // cat_create gives a map several chunks per unit only where select_kernels chose kernels that carry fan_slot (fixed dimensions): the
+                    // generic kernels always get one (a loop over several would cost them 8 VGPRs for nothing)
+                    unsigned chunks = D::kFixed ? (1u << nq) - 1u : 1u;
+                    if (D::kFixed && gsz > 1) chunks = fan_slot<D>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, c0, nq, pc);
                     while (chunks) {
                         const int q = uni(__builtin_ctz(chunks));
                         chunks &= chunks - 1;

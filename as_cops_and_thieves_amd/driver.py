@@ -23,13 +23,15 @@ def configure_argparser():
     parser.add_argument("-i", "--map-image", type=Path, default=None)
     parser.add_argument("--steps", type=int, default=500)
     parser.add_argument("--seed", type=int, default=None)
+    parser.add_argument("--query-order", choices=["index", "chipmunk"], default="index",
+                        help="visiting order of the walls in segment queries: index order (default) or Chipmunk's static tree (DESIGN.md D2)")
     return parser.parse_args()
 
 
 def main() -> None:
     args = configure_argparser()
     map = Map(args.mapfile) if Path(args.mapfile).exists() else load_preset(args.mapfile)
-    env = SimpleEnv(map=map, map_image=args.map_image, render_mode=args.render_mode)
+    env = SimpleEnv(map=map, map_image=args.map_image, render_mode=args.render_mode, query_order=args.query_order)
     observations, infos = env.reset(seed=args.seed)
     ended_at = None
     for t in range(args.steps):

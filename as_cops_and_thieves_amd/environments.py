@@ -52,6 +52,21 @@ def _physical_from_cwd() -> PhysicalParams:
     return load_physical_params(None)
 
 
+QUERY_ORDERS = ("index", "chipmunk")
+
+
+def gate_mode(bbtree_gate: bool, query_order: str) -> int:
+    """``SimConfig.bbtree_gate`` for the env options: 0 no gate, 1 the gate with the walls in index order (the default), 2 the gate with the walls in
+    the order of Chipmunk's static tree (``query_order="chipmunk"``).  The tree order is an order of the GATED query, so it needs the gate."""
+    if query_order not in QUERY_ORDERS:
+        raise ValueError(f"query_order must be one of {QUERY_ORDERS}, not {query_order!r}")
+    if query_order == "chipmunk":
+        if not bbtree_gate:
+            raise ValueError('query_order="chipmunk" orders the gated segment query: it needs bbtree_gate=True')
+        return 2
+    return int(bool(bbtree_gate))
+
+
 class BaseEnv(_ParallelEnvBase):
     """Single-env PettingZoo ``ParallelEnv`` surface (reference ``BaseEnv(ParallelEnv)``, base_env.py:30-554)."""
 
@@ -60,7 +75,8 @@ class BaseEnv(_ParallelEnvBase):
     def __init__(self, map: Map, map_image: Optional[Path] = None, render_mode: Optional[str] = None,
                  max_step_count: int = 400, time_step: float = 1 / 15.0, *,
                  num_rays: int = DEFAULT_SENSOR.num_rays, device=None, seed: int = 1,
-                 physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True):
+                 physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True, query_order: str = "index"):
+        gate = gate_mode(bbtree_gate, query_order)   # (before anything touches a device)
         assert render_mode is None or render_mode in self.metadata["render_modes"]  # base_env.py:117
         self.map, self.map_image = map, map_image
         self.width, self.height = self.map.window_dimensions
@@ -74,7 +90,7 @@ class BaseEnv(_ParallelEnvBase):
 
         self._cfg = SimConfig.from_params(
             physical=physical, n_envs=1, n_cops=map.cops_count, n_thieves=map.thieves_count,
-            max_step_count=max_step_count, dt=time_step, seed=seed, bbtree_gate=int(bbtree_gate))
+            max_step_count=max_step_count, dt=time_step, seed=seed, bbtree_gate=gate)
         self._cfg.n_rays = num_rays
         self._compiled: CompiledMap = map.compile(self._cfg.wall_radius)
         self._sim = CatSim(self._cfg, [self._compiled], device=device)
@@ -237,9 +253,9 @@ class SimpleEnv(BaseEnv):
     """reference ``SimpleEnv`` (simple_env.py:6-58): dt = 1/60, render_mode "rgb_array"."""
 
     def __init__(self, map: Map, render_mode: str = "rgb_array", map_image: Optional[Path] = None,
-                 max_step_count: int = 400, time_step: float = 1 / 60.0, **kw):
+                 max_step_count: int = 400, time_step: float = 1 / 60.0, query_order: str = "index", **kw):
         super().__init__(map=map, map_image=map_image, render_mode=render_mode,
-                         max_step_count=max_step_count, time_step=time_step, **kw)
+                         max_step_count=max_step_count, time_step=time_step, query_order=query_order, **kw)
 
     def _get_info(self) -> dict:
         info = super()._get_info()
@@ -279,7 +295,8 @@ class VecCopsEnv:
     def __init__(self, maps, num_envs: int, *, slot_map_ids: Optional[Sequence[int]] = None,
                  num_rays: int = 64, max_step_count: int = 400, time_step: float = 1 / 60.0,
                  auto_reset: bool = True, device=None, seed: int = 1, env_id_offset: int = 0,
-                 physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True):
+                 physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True, query_order: str = "index"):
+        gate = gate_mode(bbtree_gate, query_order)   # (before anything touches a device)
         self.maps: List[Map] = list(maps) if isinstance(maps, (list, tuple)) else [maps]
         m0 = self.maps[0]
         for m in self.maps[1:]:
@@ -290,7 +307,7 @@ class VecCopsEnv:
         self._cfg = SimConfig.from_params(
             physical=physical, n_envs=num_envs, n_cops=m0.cops_count, n_thieves=m0.thieves_count,
             max_step_count=max_step_count, dt=time_step, seed=seed, env_id_offset=env_id_offset,
-            bbtree_gate=int(bbtree_gate))
+            bbtree_gate=gate)
         self._cfg.n_rays = num_rays
         self._compiled = [m.compile(self._cfg.wall_radius) for m in self.maps]
         self._sim = CatSim(self._cfg, self._compiled, slot_map_ids, device=device)

@@ -181,8 +181,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   training: Optional[TrainingConfig] = None, trainer_cfg: Optional[TrainerConfig] = None,
                   role_cfg: Optional[Dict[str, RoleConfig]] = None, num_rays: int = 64, n_cops: Optional[int] = None,
                   n_thieves: Optional[int] = None, max_step_count: int = 2000, eval_envs: Optional[int] = None,
-                  seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None) -> Dict[str, object]:
+                  seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
+                  query_order: str = "index") -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
+    ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
     ``env_factory(num_envs, seed[, env_id_offset])``: build the envs some other way (the CPU tests pass a stand-in env with the
     same surface).
@@ -221,7 +223,7 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     if env_factory is None:
         preset = load_preset(map_name, n_cops, n_thieves)
         env_factory = lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
-                                                     env_id_offset=off)
+                                                     env_id_offset=off, query_order=query_order)
     n_local, offset = shard_envs(num_envs, rank, world)
     if multi:
         # checked on EVERY rank from the same numbers, so that all of them refuse together (a rank that raised alone would leave the others in the
@@ -357,6 +359,8 @@ def main() -> None:
     ap.add_argument("--freeze-duration", type=int, default=None, help="override of CFG_TRAINER's policy / opponent freeze durations (15000)")
     ap.add_argument("--non-recurrent", action="store_true", help="the reference's non-recurrent Policy / Value pair (policy_net.py, value_net.py; "
                     "model_utils.py:45-77) instead of the LSTM pair its drivers use")
+    ap.add_argument("--query-order", default="index", choices=["index", "chipmunk"],
+                    help="visiting order of the walls in segment queries: index order (default) or Chipmunk's static tree (DESIGN.md D2)")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -378,7 +382,8 @@ def main() -> None:
     rank = int(os.environ.get("RANK", "0"))
     res = run_self_play(args.map, args.envs, args.out, iterations=args.iterations, training=tc, trainer_cfg=tcfg, role_cfg=role_cfg,
                         num_rays=args.rays, n_cops=args.cops, n_thieves=args.thieves, max_step_count=args.max_step_count,
-                        eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None))
+                        eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
+                        query_order=args.query_order)
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

@@ -52,7 +52,7 @@ typedef struct cat_config {
     int32_t max_step_count;
     int32_t iterations;
     int32_t persistence;
-    int32_t bbtree_gate;          /* 1 = Chipmunk BBTree visiting rule for segment queries */
+    int32_t bbtree_gate;          /* CAT_GATE_*: visiting rule of segment queries (see below) */
     int64_t env_id_offset;        /* global id of env slot 0 (env sharding across GPUs) */
     uint64_t seed;                /* Philox4x32-10 key */
     double dt;
@@ -67,6 +67,18 @@ typedef struct cat_config {
     double termination_radius;
     double wall_radius;
 } cat_config;
+
+/* cat_config.bbtree_gate.  Which walls and agents a segment query (ray or line of sight) visits, and in which order:
+   CAT_GATE_NONE  every shape, in index order (no spatial-index gate);
+   CAT_GATE_INDEX Chipmunk's gate -- a shape is visited iff the thin segment enters its bounding box before the best alpha so far --
+                  with the walls visited in index order (the default);
+   CAT_GATE_TREE  the same gate with the walls visited in the depth-first order of Chipmunk's static BBTree ([CP SubtreeSegmentQuery],
+                  nearer child first, the tree cpBBTreeInsert builds from the walls in index order); the agents follow in index order.
+                  Runs the chunk form of the ray fan only; cat_create refuses a map whose tree is deeper than 48 (CAT_ERR_BAD_MAP).
+   Other values: CAT_ERR_BAD_CONFIG. */
+#define CAT_GATE_NONE 0
+#define CAT_GATE_INDEX 1
+#define CAT_GATE_TREE 2
 
 /* HOST pointers, copied at create.  ray_dx/dy[k] = ray_length * cos/sin(2*pi*k/R) built with
    NumPy as entity.py:182-193 builds them; reward LUTs indexed by float16 bits (cop.py:69-74,
@@ -225,6 +237,12 @@ void cat_grid_free_host(cat_grid_host *grid);
    bound cat_create holds against CAT_WALL_CACHE -- a map where it is larger is refused (CAT_ERR_BAD_MAP) instead of dropping a
    contact at run time (CAT_DEVERR_CONTACT_DROPPED stays as the backstop).  Negative: an error code. */
 int cat_map_wall_bb_depth_host(const void *map_blob, size_t blob_size, double agent_radius);
+
+/* Host-only: the static tree cat_create builds for a map in tree order (CAT_GATE_TREE), for the CPU tests.  Node n < S is the leaf of wall n,
+   inner nodes follow in creation order.  Writes up to max_nodes nodes: bb_out[4n..4n+3] = l b r t, link_out[4n..4n+3] = child a, child b,
+   parent (-1 at the root), wall id (leaf) or -1; *root, *depth (edges from the root to the deepest leaf).  Returns the node count 2S - 1,
+   or an error code.  Any output pointer may be NULL. */
+int cat_bbtree_host(const void *map_blob, size_t blob_size, double *bb_out, int *link_out, int max_nodes, int *root, int *depth);
 
 /* Device arithmetic self-test used by tests: out[i] = op(in_a[i], in_b[i]) evaluated on the GPU
    with the same primitives the kernels use (op 0 sqrt(a), 1 a/b, 2 f64->f16 bits of a,
