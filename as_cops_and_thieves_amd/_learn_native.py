@@ -1,5 +1,6 @@
-"""ctypes binding of libcat_learn.so (include/cat_lstm.h, include/cat_trunk.h): the LSTM recurrence and the
-convolutional trunk of the self-play learner's networks, one launch per direction each.  No CPU fallback inside: callers
+"""ctypes binding of libcat_learn.so (include/cat_lstm.h, include/cat_trunk.h, ...): the LSTM recurrence and the
+convolutional trunk of the self-play learner's networks, one launch per direction each, the learner's other kernels, and the batched
+frame renderer (include/cat_render.h).  No CPU fallback inside: callers
 on a CUDA/HIP device in bf16 get these kernels or an exception."""
 from __future__ import annotations
 
@@ -13,8 +14,8 @@ ROOT = PKG.parent
 LIB_PATH = PKG / "libcat_learn.so"
 if os.environ.get("CAT_LEARN_LIB"):         # diagnostic builds (A/B of kernel variants): another build of the same sources
     LIB_PATH = Path(os.environ["CAT_LEARN_LIB"]).resolve()
-SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout"))
-HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout"))
+SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render"))
+HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render"))
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared"]
 HIDDEN = 128
 EXPORTED_SYMBOLS = ("cat_lstm_abi_version", "cat_lstm_last_error", "cat_lstm_blocks", "cat_lstm_saved_acts_bytes", "cat_lstm_saved_cell_bytes",
@@ -71,6 +72,25 @@ ROLLOUT_SYMBOLS = ("cat_rollout_abi_version", "cat_rollout_last_error", "cat_rol
 DENSE_SYMBOLS = ("cat_dense_abi_version", "cat_dense_last_error", "cat_dense_bias_act", "cat_dense_act_grad", "cat_dense_sum_chunks",
                  "cat_dense_wgrad_splits", "cat_dense_wgrad", "cat_dense_forward", "cat_dense_dgrad", "cat_dense_sum_chunks2")
 PPO_SYMBOLS = ("cat_ppo_abi_version", "cat_ppo_last_error", "cat_ppo_loss_grad", "cat_ppo_adam_step", "cat_ppo_gae_scan")
+RENDER_SYMBOLS = ("cat_render_abi_version", "cat_render_last_error", "cat_render_frames")
+RENDER_RAYS = 1                 # cat_render_args.flags
+RENDER_MAX_AGENTS = 16
+
+
+class RenderSceneDesc(C.Structure):
+    """include/cat_render.h cat_render_scene (device pointers except the two *_host arrays)."""
+    _fields_ = [("n_maps", C.c_int32), ("n_rays", C.c_int32), ("window", C.c_void_p), ("window_host", C.c_void_p),
+                ("shape_off", C.c_void_p), ("shape_off_host", C.c_void_p), ("shape_bb", C.c_void_p), ("shape_first", C.c_void_p),
+                ("shape_count", C.c_void_p), ("planes", C.c_void_p), ("ray_dx", C.c_void_p), ("ray_dy", C.c_void_p)]
+
+
+class RenderArgs(C.Structure):
+    """include/cat_render.h cat_render_args."""
+    _fields_ = [("F", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_int32),
+                ("n_cops", C.c_int32), ("A", C.c_int32), ("R", C.c_int32), ("pad", C.c_int32),
+                ("agent_radius", C.c_double), ("ray_length", C.c_double),
+                ("map_ids", C.c_void_p), ("map_ids_dev", C.c_void_p), ("positions", C.c_void_p), ("obs_distance", C.c_void_p),
+                ("obs_type", C.c_void_p), ("frames", C.c_void_p)]
 
 
 class PpoLoss(C.Structure):
@@ -180,6 +200,11 @@ def lib() -> C.CDLL:
             getattr(L, n).restype = C.c_int
             getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
         assert L.cat_rollout_abi_version() == 1
+        L.cat_render_abi_version.restype = C.c_int
+        L.cat_render_last_error.restype = C.c_char_p
+        L.cat_render_frames.restype = C.c_int
+        L.cat_render_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        assert L.cat_render_abi_version() == 1
         _lib = L
     return _lib
 
@@ -188,6 +213,7 @@ def _check(rc: int, what: str) -> None:
     if rc != 0:
         err = (lib().cat_trunk_last_error() if "trunk" in what else lib().cat_ppo_last_error() if "ppo" in what
                else lib().cat_dense_last_error() if "dense" in what else lib().cat_rollout_last_error() if "rollout" in what
+               else lib().cat_render_last_error() if "render" in what
                else lib().cat_lstm_last_error())
         raise RuntimeError(f"{what} failed ({rc}): {err.decode()}")
 

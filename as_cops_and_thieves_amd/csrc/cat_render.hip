@@ -1,0 +1,317 @@
+// cat_render.hip -- libcat_learn.so, part 6: batched rgb_array frames on MI355X (gfx950).  include/cat_render.h has the interface and
+// the pixel contract; as_cops_and_thieves_amd/render.py (render_frame_reference) is its NumPy statement, byte for byte.
+//
+// One workgroup draws one TX x TY tile of one frame.  The frame is x-major, [width][height][3], so a column x is a contiguous run of
+// height pixels: a lane owns 4 consecutive pixels along y (12 bytes, three dword stores) in each of ROWS columns, and the 16 lanes of
+// a column group write 192 contiguous bytes.  Before drawing, the workgroup culls into LDS, in their original order, the walls and ray
+// segments whose pixel windows meet the tile; then every pixel takes the first hit of a backward walk over the discs, the rays and the
+// walls (a later item overwrites an earlier one in the reference, so the last hit is the one that stays).  Lists longer than a chunk
+// are culled and walked chunk by chunk, last chunk first.
+//
+// Byte equality with NumPy needs binary64 arithmetic in the reference's operation order and no a*b+c contraction into an FMA, which
+// hip-clang does by default: the pragma below turns it off for this file (and only here: the library's other kernels keep their flags).
+#pragma clang fp contract(off)
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "cat_render.h"
+
+namespace {
+
+constexpr int BLOCK = 256, WAVES = BLOCK / 64;
+constexpr int LANES_Y = 16, PIX = 4, ROWS = 2;            // 16 lanes x 4 pixels along y; each thread draws 2 columns
+constexpr int TY = LANES_Y * PIX;                         // 64 pixels along y per tile
+constexpr int COLS = BLOCK / LANES_Y;                     // 16 columns per pass
+constexpr int TX = COLS * ROWS;                           // 32 columns per tile
+constexpr int CHUNK = BLOCK;                              // culled items per pass: one candidate per thread
+constexpr uint32_t WHITE = 0xFFFFFFu, GREY = 0x3C3C3Cu, BLUE = 0xFF0000u, RED = 0x0000FFu;   // 0xBBGGRR
+
+__device__ __forceinline__ uint32_t rgb(int r, int g, int b) { return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16); }
+
+__device__ __forceinline__ uint32_t ray_colour(int type)
+{
+    constexpr uint8_t pal[5][3] = CAT_RENDER_RAY_COLOURS;
+    const int t = type > 4 ? 4 : type;
+    return rgb(pal[t][0], pal[t][1], pal[t][2]);
+}
+
+// [trunc(v) + off] clamped to [0, limit]: one bound of a reference window max(int(v) + off, 0) / min(int(v) + off, limit), formed
+// in binary64 so that no coordinate can overflow an int (a NaN bound opens the whole window; the pixel tests reject it anyway)
+__device__ __forceinline__ int bound(double v, double off, int limit)
+{
+    return (int)fmin(fmax(trunc(v) + off, 0.0), (double)limit);
+}
+
+struct Window { int x0, x1, y0, y1; };
+
+__device__ __forceinline__ bool meets(const Window &w, int dx0, int dx1, int dy0, int dy1)
+{
+    return w.x0 < w.x1 && w.y0 < w.y1 && w.x0 < dx1 && w.x1 > dx0 && w.y0 < dy1 && w.y1 > dy0;
+}
+
+struct Shared {
+    int wave_count[WAVES];
+    int n;                                                // length of the current list
+    // discs
+    double dpx[CAT_RENDER_MAX_AGENTS], dpy[CAT_RENDER_MAX_AGENTS];
+    Window dwin[CAT_RENDER_MAX_AGENTS];
+    // the current chunk's ray segments, in order
+    double px[CHUNK], py[CHUNK], ex[CHUNK], ey[CHUNK], vx[CHUNK], vy[CHUNK], c2[CHUNK];
+    Window rwin[CHUNK];
+    uint32_t rcol[CHUNK];
+    // the current chunk's walls
+    int wall[CHUNK];
+    Window wwin[CHUNK];
+};
+
+// Ordered compaction of one candidate per thread: the slot of this thread's item among the kept ones (by thread index), and the
+// number kept in s.n.  Ends with a barrier, after which s.n is valid; the caller writes the record, then synchronises again.
+__device__ __forceinline__ int compact(bool keep, Shared &s)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long mask = __ballot(keep);
+    const int before = __popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) s.wave_count[wave] = __popcll(mask);
+    __syncthreads();
+    int off = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        off += w < wave ? s.wave_count[w] : 0;
+        total += s.wave_count[w];
+    }
+    if (threadIdx.x == 0) s.n = total;
+    return off + before;
+}
+
+__global__ __launch_bounds__(BLOCK) void render_tiles_kernel(const cat_render_scene sc, const cat_render_args a, int tiles_x, int tiles_y)
+{
+    __shared__ Shared s;
+    const int tiles = tiles_x * tiles_y;
+    const int f = blockIdx.x / tiles, tile = blockIdx.x - f * tiles;
+    const int x0t = (tile / tiles_y) * TX, y0t = (tile % tiles_y) * TY;
+    const int m = a.map_ids_dev[f];
+    const bool map_ok = m >= 0 && m < sc.n_maps;          // checked on the host; a bad device copy draws a blank frame, not a fault
+    const int Wm = map_ok ? sc.window[2 * m] : 0, Hm = map_ok ? sc.window[2 * m + 1] : 0;
+    // the part of the tile inside the map's window: every item is clipped to it, and the frame beyond it stays white
+    const int dx0 = x0t, dx1 = min(x0t + TX, Wm), dy0 = y0t, dy1 = min(y0t + TY, Hm);
+    const bool live = dx0 < dx1 && dy0 < dy1;             // uniform over the workgroup
+
+    const int ly = (threadIdx.x % LANES_Y) * PIX, lx = threadIdx.x / LANES_Y;
+    uint32_t col[ROWS][PIX];
+    bool done[ROWS][PIX];
+#pragma unroll
+    for (int j = 0; j < ROWS; ++j)
+#pragma unroll
+        for (int i = 0; i < PIX; ++i) { col[j][i] = WHITE; done[j][i] = false; }
+
+    if (live) {
+        const int A = a.A;
+        const double r = a.agent_radius, r2 = r * r;
+        const double *pos = a.positions + (size_t)f * A * 2;
+        if ((int)threadIdx.x < A) {
+            const int i = threadIdx.x;
+            const double px = pos[2 * i], py = pos[2 * i + 1];
+            s.dpx[i] = px;
+            s.dpy[i] = py;
+            s.dwin[i] = Window{bound(px - r, -1.0, Wm), bound(px + r, 2.0, Wm), bound(py - r, -1.0, Hm), bound(py + r, 2.0, Hm)};
+        }
+        __syncthreads();
+        // 3. discs: the last agent that covers a pixel wins
+        for (int i = A - 1; i >= 0; --i) {
+            const Window w = s.dwin[i];
+            const double px = s.dpx[i], py = s.dpy[i];
+            const uint32_t c = i < a.n_cops ? BLUE : RED;
+#pragma unroll
+            for (int j = 0; j < ROWS; ++j) {
+                const int x = x0t + lx + COLS * j;
+                if (x < w.x0 || x >= w.x1) continue;
+                const double X = x + 0.5, dx = X - px;
+#pragma unroll
+                for (int k = 0; k < PIX; ++k) {
+                    const int y = y0t + ly + k;
+                    if (done[j][k] || y < w.y0 || y >= w.y1) continue;
+                    const double dy = (y + 0.5) - py;
+                    if (dx * dx + dy * dy <= r2) { col[j][k] = c; done[j][k] = true; }
+                }
+            }
+        }
+        // 2. ray segments, last chunk first, each list backwards
+        if (a.flags & CAT_RENDER_RAYS) {
+            const int R = a.R, n_items = A * R;
+            const uint16_t *dist = a.obs_distance + (size_t)f * A * R;
+            const uint8_t *type = a.obs_type + (size_t)f * A * R;
+            for (int c0 = ((n_items - 1) / CHUNK) * CHUNK; c0 >= 0; c0 -= CHUNK) {
+                const int item = c0 + threadIdx.x;
+                double px = 0, py = 0, ex = 0, ey = 0;
+                Window w{0, 0, 0, 0};
+                bool keep = false;
+                if (item < n_items) {
+                    const int ag = item / R, k = item - ag * R;
+                    px = pos[2 * ag];
+                    py = pos[2 * ag + 1];
+                    const double d = (double)__builtin_bit_cast(_Float16, dist[item]);
+                    const double t = d / a.ray_length;
+                    ex = px + t * sc.ray_dx[k];
+                    ey = py + t * sc.ray_dy[k];
+                    const double lo_x = px < ex ? px : ex, hi_x = px < ex ? ex : px;   // Python's min / max of two floats
+                    const double lo_y = py < ey ? py : ey, hi_y = py < ey ? ey : py;
+                    w = Window{bound(lo_x, -1.0, Wm), bound(hi_x, 2.0, Wm), bound(lo_y, -1.0, Hm), bound(hi_y, 2.0, Hm)};
+                    keep = meets(w, dx0, dx1, dy0, dy1);
+                }
+                const int slot = compact(keep, s);
+                if (keep) {
+                    const double vx = ex - px, vy = ey - py;
+                    s.px[slot] = px; s.py[slot] = py; s.ex[slot] = ex; s.ey[slot] = ey;
+                    s.vx[slot] = vx; s.vy[slot] = vy; s.c2[slot] = vx * vx + vy * vy;
+                    s.rwin[slot] = w;
+                    s.rcol[slot] = ray_colour(type[item]);
+                }
+                __syncthreads();
+                for (int q = s.n - 1; q >= 0; --q) {
+                    const Window rw = s.rwin[q];
+                    const double spx = s.px[q], spy = s.py[q], sex = s.ex[q], sey = s.ey[q], svx = s.vx[q], svy = s.vy[q], sc2 = s.c2[q];
+                    const uint32_t c = s.rcol[q];
+#pragma unroll
+                    for (int j = 0; j < ROWS; ++j) {
+                        const int x = x0t + lx + COLS * j;
+                        if (x < rw.x0 || x >= rw.x1) continue;
+                        const double X = x + 0.5, wx = X - spx;
+#pragma unroll
+                        for (int k = 0; k < PIX; ++k) {
+                            const int y = y0t + ly + k;
+                            if (done[j][k] || y < rw.y0 || y >= rw.y1) continue;
+                            const double Y = y + 0.5, wy = Y - spy;
+                            const double c1 = wx * svx + wy * svy;
+                            double d2;
+                            if (c1 <= 0.0) {
+                                d2 = wx * wx + wy * wy;
+                            } else if (c1 >= sc2) {
+                                const double ax = X - sex, ay = Y - sey;
+                                d2 = ax * ax + ay * ay;
+                            } else {
+                                const double u = c1 / sc2, qx = wx - u * svx, qy = wy - u * svy;
+                                d2 = qx * qx + qy * qy;
+                            }
+                            if (d2 <= 0.25) { col[j][k] = c; done[j][k] = true; }
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // 1. walls: any hit is grey
+        const int s_begin = sc.shape_off[m], s_end = sc.shape_off[m + 1];
+        for (int c0 = s_begin; c0 < s_end; c0 += CHUNK) {
+            const int sh = c0 + threadIdx.x;
+            Window w{0, 0, 0, 0};
+            bool keep = false;
+            if (sh < s_end) {
+                const double *bb = sc.shape_bb + 4 * (size_t)sh;
+                w = Window{bound(bb[0], 0.0, Wm), bound(bb[2], 1.0, Wm), bound(bb[1], 0.0, Hm), bound(bb[3], 1.0, Hm)};
+                keep = meets(w, dx0, dx1, dy0, dy1);
+            }
+            const int slot = compact(keep, s);
+            if (keep) { s.wall[slot] = sh; s.wwin[slot] = w; }
+            __syncthreads();
+            for (int q = 0; q < s.n; ++q) {
+                const Window ww = s.wwin[q];
+                const int first = sc.shape_first[s.wall[q]], count = sc.shape_count[s.wall[q]];
+#pragma unroll
+                for (int j = 0; j < ROWS; ++j) {
+                    const int x = x0t + lx + COLS * j;
+                    if (x < ww.x0 || x >= ww.x1) continue;
+                    const double X = x + 0.5;
+#pragma unroll
+                    for (int k = 0; k < PIX; ++k) {
+                        const int y = y0t + ly + k;
+                        if (done[j][k] || y < ww.y0 || y >= ww.y1) continue;
+                        const double Y = y + 0.5;
+                        bool inside = true;
+                        for (int p = 0; p < count && inside; ++p) {
+                            const double *pl = sc.planes + 5 * (size_t)(first + p);
+                            inside = pl[0] * X + pl[1] * Y - pl[4] <= 1.0;
+                        }
+                        if (inside) { col[j][k] = GREY; done[j][k] = true; }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // store: 4 pixels = 12 bytes per column, as three dwords where the address allows it
+#pragma unroll
+    for (int j = 0; j < ROWS; ++j) {
+        const int x = x0t + lx + COLS * j, y = y0t + ly;
+        if (x >= a.width || y >= a.height) continue;
+        uint8_t *p = a.frames + (((size_t)f * a.width + x) * a.height + y) * 3;
+        if (y + PIX <= a.height && ((uintptr_t)p & 3) == 0) {
+            uint32_t *q = (uint32_t *)p;
+            q[0] = col[j][0] | (col[j][1] << 24);
+            q[1] = (col[j][1] >> 8) | (col[j][2] << 16);
+            q[2] = (col[j][2] >> 16) | (col[j][3] << 8);
+        } else {
+            for (int k = 0; k < PIX && y + k < a.height; ++k) {
+                p[3 * k] = (uint8_t)col[j][k];
+                p[3 * k + 1] = (uint8_t)(col[j][k] >> 8);
+                p[3 * k + 2] = (uint8_t)(col[j][k] >> 16);
+            }
+        }
+    }
+}
+
+thread_local char g_err[256] = "";
+int fail(const char *msg)
+{
+    snprintf(g_err, sizeof g_err, "cat_render_frames: %s", msg);
+    return CAT_RENDER_ERR_BAD_ARG;
+}
+
+}   // namespace
+
+extern "C" int cat_render_abi_version(void) { return CAT_RENDER_ABI_VERSION; }
+extern "C" const char *cat_render_last_error(void) { return g_err; }
+
+extern "C" int cat_render_frames(const cat_render_scene *sc, const cat_render_args *a, void *stream)
+{
+    if (!sc || !a) return fail("NULL scene or arguments");
+    if (sc->n_maps <= 0 || !sc->window || !sc->window_host || !sc->shape_off || !sc->shape_off_host || !sc->shape_bb ||
+        !sc->shape_first || !sc->shape_count || !sc->planes)
+        return fail("incomplete scene");
+    if (a->F <= 0 || a->width <= 0 || a->height <= 0 || a->A <= 0 || a->A > CAT_RENDER_MAX_AGENTS || a->n_cops < 0 || a->n_cops > a->A)
+        return fail("bad dimensions");
+    if (!(a->agent_radius >= 0.0) || !isfinite(a->agent_radius)) return fail("agent_radius must be finite and >= 0");
+    if (a->flags & ~CAT_RENDER_RAYS) return fail("unknown flags");
+    const bool rays = a->flags & CAT_RENDER_RAYS;
+    if (rays) {
+        if (a->R <= 0 || a->R != sc->n_rays || !sc->ray_dx || !sc->ray_dy) return fail("rays: R must equal the scene's ray table");
+        if (!(a->ray_length > 0.0) || !isfinite(a->ray_length)) return fail("rays: ray_length must be finite and > 0");
+        if (!a->obs_distance || !a->obs_type) return fail("rays: obs_distance / obs_type is NULL");
+    }
+    if (!a->map_ids || !a->map_ids_dev || !a->positions || !a->frames) return fail("a required buffer is NULL");
+    for (int f = 0; f < a->F; ++f) {
+        const int m = a->map_ids[f];
+        if (m < 0 || m >= sc->n_maps) {
+            snprintf(g_err, sizeof g_err, "cat_render_frames: map_ids[%d] = %d outside [0, %d)", f, m, sc->n_maps);
+            return CAT_RENDER_ERR_BAD_ARG;
+        }
+        if (sc->window_host[2 * m] > a->width || sc->window_host[2 * m + 1] > a->height) {
+            snprintf(g_err, sizeof g_err, "cat_render_frames: frame %d: map %d's window %dx%d exceeds the frame size %dx%d", f, m,
+                     sc->window_host[2 * m], sc->window_host[2 * m + 1], a->width, a->height);
+            return CAT_RENDER_ERR_BAD_ARG;
+        }
+    }
+    const long long tiles_x = (a->width + TX - 1) / TX, tiles_y = (a->height + TY - 1) / TY;
+    const long long blocks = tiles_x * tiles_y * a->F;
+    if (blocks > INT32_MAX) return fail("too many frames for one launch");
+    hipLaunchKernelGGL(render_tiles_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, *sc, *a, (int)tiles_x, (int)tiles_y);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_err, sizeof g_err, "cat_render_frames: %s", hipGetErrorString(e));
+        return CAT_RENDER_ERR_HIP;
+    }
+    return CAT_RENDER_OK;
+}

@@ -312,6 +312,9 @@ class VecCopsEnv:
         self._compiled = [m.compile(self._cfg.wall_radius) for m in self.maps]
         self._sim = CatSim(self._cfg, self._compiled, slot_map_ids, device=device)
         self.device = self._sim.device
+        self.slot_map_ids = np.zeros(num_envs, dtype=np.int32) if slot_map_ids is None else \
+            np.array(slot_map_ids, dtype=np.int32).reshape(num_envs)   # (cat_create has checked them)
+        self._render_scene = None
         self.possible_agents = [f"cop_{i}" for i in range(m0.cops_count)] + \
                                [f"thief_{j}" for j in range(m0.thieves_count)]
         self.agents = self.possible_agents[:]
@@ -424,6 +427,29 @@ class VecCopsEnv:
         out = self._sim.step_fused(None, tick=tick0 + ticks - 1, auto_reset=self.auto_reset)
         self._sim.check_errors()   # thousands of ticks went by inside one launch: a flag raised by any of them ends the run here, not never
         return out
+
+    def render(self, env_ids: Optional[Sequence[int]] = None, rays: bool = False) -> torch.Tensor:
+        """``rgb_array`` frames of the env slots ``env_ids`` (default ``[0]``), drawn on the GPU in one launch
+        (``render_gpu.RenderScene``): a ``torch.uint8 [len(env_ids), W, H, 3]`` tensor on the env's device, x-major like
+        ``BaseEnv.render``, W x H the largest map window of the batch (a slot's frame is white beyond its own map's window).
+        ``rays=True`` also draws every agent's ray fan from the current observation buffers, coloured by what each ray hit.
+        Read-only: the positions come from ``cat_get_state`` (position field only), the rays from the output buffers."""
+        ids = [0] if env_ids is None else [int(e) for e in env_ids]
+        if not ids:
+            raise ValueError("render: env_ids is empty")
+        bad = [e for e in ids if not 0 <= e < self.num_envs]
+        if bad:
+            raise IndexError(f"render: env ids {bad} outside [0, {self.num_envs})")
+        if self._render_scene is None:
+            from .render_gpu import RenderScene
+            self._render_scene = RenderScene(self._compiled, self.device, sensor=self._cfg.sensor, agent_radius=self._cfg.agent_radius)
+        sel = torch.tensor(ids, dtype=torch.long, device=self.device)
+        pos = self._sim.get_positions().index_select(0, sel)
+        ray_data = None
+        if rays:
+            o = self._sim.out
+            ray_data = (o["obs_distance"].index_select(0, sel), o["obs_type"].index_select(0, sel))
+        return self._render_scene.frames(self.slot_map_ids[ids], pos, rays=ray_data)
 
     def check_errors(self) -> None:
         """The step launches are asynchronous and cannot raise; this synchronises and raises ``ValueError`` if any

@@ -4,8 +4,16 @@ The reference's ``rgb_array`` mode returns ``pygame.surfarray.array3d`` of a sur
 draws on (``base_env.py:505-507``): an all-zero ``(width, height, 3)`` uint8 array.  This
 rasteriser keeps that shape/dtype convention but draws the scene (hull walls, cops blue, thieves
 red — the colours of ``cop.py:30`` / ``thief.py:29``), which is what a user wants from a frame.
+
+``render_frame_reference`` is the pixel contract of the batched GPU renderer (``include/cat_render.h``, ``render_gpu.RenderScene``):
+the same frame, optionally with every agent's ray fan drawn between the walls and the discs.  ``write_png`` stores a frame with the
+standard library alone.
 """
 from __future__ import annotations
+
+import struct
+import zlib
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -37,3 +45,92 @@ def render_rgb_array(cmap: CompiledMap, positions: np.ndarray, n_cops: int, agen
         disc = (xs[x0:x1] - px) ** 2 + (ys[:, y0:y1] - py) ** 2 <= agent_radius ** 2
         img[x0:x1, y0:y1][disc] = colour
     return img
+
+
+# ray colour by ObjectType (WALL, COP, THIEF, MOVABLE, EMPTY); a type above EMPTY is drawn as EMPTY.  include/cat_render.h
+# CAT_RENDER_RAY_COLOURS holds the same table for the kernel.
+RAY_COLOURS = np.array([(255, 140, 0), (0, 170, 255), (255, 60, 160), (0, 160, 0), (190, 190, 190)], dtype=np.uint8)
+
+
+def _segment_d2(X: np.ndarray, Y: np.ndarray, px: float, py: float, ex: float, ey: float) -> np.ndarray:
+    """Squared distance from the pixel centres (X, Y) to the segment (px, py) - (ex, ey), in the contract's operation order."""
+    vx, vy = ex - px, ey - py
+    wx, wy = X - px, Y - py
+    c1 = wx * vx + wy * vy
+    c2 = vx * vx + vy * vy
+    d_start = wx * wx + wy * wy
+    ax, ay = X - ex, Y - ey
+    d_end = ax * ax + ay * ay
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = c1 / c2
+        qx, qy = wx - u * vx, wy - u * vy
+        d_mid = qx * qx + qy * qy
+    return np.where(c1 <= 0.0, d_start, np.where(c1 >= c2, d_end, d_mid))
+
+
+def render_frame_reference(cmap: CompiledMap, positions: np.ndarray, n_cops: int, agent_radius: float,
+                           rays: Optional[Sequence] = None) -> np.ndarray:
+    """The frame the GPU renderer draws, as ``(W, H, 3)`` uint8 over the map's window.
+
+    Without ``rays`` this is ``render_rgb_array``.  With ``rays = (ray_dx, ray_dy, ray_length, distance_f16[A, R], obj_type_u8[A, R])``
+    the ray segments of every agent are drawn after the walls and before the discs, agent by agent and ray by ray (a later write wins):
+    ray k of an agent at (px, py) runs to ``(px + t * ray_dx[k], py + t * ray_dy[k])`` with ``t = float64(distance) / ray_length``; a
+    pixel of the window ``[int(min) - 1, int(max) + 2)`` of the segment's bounding box (clipped to the frame) is lit, in
+    ``RAY_COLOURS[object_type]``, when its centre lies within 0.5 of the segment (squared distance ``<= 0.25``)."""
+    if rays is None:
+        return render_rgb_array(cmap, positions, n_cops, agent_radius)
+    ray_dx, ray_dy, ray_length, distance, obj_type = rays
+    ray_dx = np.asarray(ray_dx, dtype=np.float64)
+    ray_dy = np.asarray(ray_dy, dtype=np.float64)
+    distance = np.asarray(distance, dtype=np.float16)
+    obj_type = np.asarray(obj_type, dtype=np.uint8)
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1, 2)
+    A, R = distance.shape
+    if pos.shape[0] != A or obj_type.shape != (A, R) or ray_dx.shape != (R,) or ray_dy.shape != (R,):
+        raise ValueError(f"rays: distance / object_type must be [A={pos.shape[0]}, R] and the ray table [R]")
+    img = render_rgb_array(cmap, pos[:0], n_cops, agent_radius)     # background and walls only
+    W, H = img.shape[0], img.shape[1]
+    ray_length = float(ray_length)
+    for i in range(A):
+        px, py = float(pos[i, 0]), float(pos[i, 1])
+        for k in range(R):
+            t = float(distance[i, k]) / ray_length
+            ex, ey = px + t * float(ray_dx[k]), py + t * float(ray_dy[k])
+            x0, x1 = max(int(min(px, ex)) - 1, 0), min(int(max(px, ex)) + 2, W)
+            y0, y1 = max(int(min(py, ey)) - 1, 0), min(int(max(py, ey)) + 2, H)
+            if x0 >= x1 or y0 >= y1:
+                continue
+            X = np.arange(x0, x1, dtype=np.float64)[:, None] + 0.5
+            Y = np.arange(y0, y1, dtype=np.float64)[None, :] + 0.5
+            lit = _segment_d2(X, Y, px, py, ex, ey) <= 0.25
+            img[x0:x1, y0:y1][lit] = RAY_COLOURS[min(int(obj_type[i, k]), len(RAY_COLOURS) - 1)]
+    xs = np.arange(W, dtype=np.float64)[:, None] + 0.5
+    ys = np.arange(H, dtype=np.float64)[None, :] + 0.5
+    for i, (px, py) in enumerate(pos):                                # the discs: render_rgb_array's rule and colours
+        colour = (0, 0, 255) if i < n_cops else (255, 0, 0)
+        x0, x1 = max(int(px - agent_radius) - 1, 0), min(int(px + agent_radius) + 2, W)
+        y0, y1 = max(int(py - agent_radius) - 1, 0), min(int(py + agent_radius) + 2, H)
+        if x0 >= x1 or y0 >= y1:
+            continue
+        disc = (xs[x0:x1] - px) ** 2 + (ys[:, y0:y1] - py) ** 2 <= agent_radius ** 2
+        img[x0:x1, y0:y1][disc] = colour
+    return img
+
+
+def write_png(path, frame: np.ndarray) -> None:
+    """Store a ``(W, H, 3)`` uint8 frame (x-major, as ``render_rgb_array`` returns it) as an 8-bit RGB PNG of W x H pixels, with
+    ``zlib`` and ``struct`` only: one IDAT chunk, filter type 0 on every row."""
+    frame = np.asarray(frame)
+    if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
+        raise ValueError(f"write_png wants a (W, H, 3) uint8 frame, got {frame.shape} {frame.dtype}")
+    W, H = frame.shape[0], frame.shape[1]
+    rows = np.ascontiguousarray(frame.transpose(1, 0, 2)).reshape(H, 3 * W)
+    raw = np.concatenate([np.zeros((H, 1), dtype=np.uint8), rows], axis=1).tobytes()
+
+    def chunk(tag: bytes, data: bytes) -> bytes:
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    png = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+           + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(png)

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Watch a checkpoint play: the headless counterpart of the reference's ``src/self_play_eval.py`` (which runs
+``SimpleEnv(render_mode="human")`` on a checkpoint), on the batched env and the GPU frame renderer.
+
+    python -m as_cops_and_thieves_amd.selfplay.watch --map agh-map --envs 4 --checkpoint run/joint_iter_3_full_agent.pt \\
+        --ticks 2000 --rays --out clips/
+
+K env slots play one episode each with the policies' sampled actions, as ``self_play.evaluate_agents`` plays them; a slot stops at
+its first termination (capture or timeout).  Every tick the K envs are drawn in ONE launch (``VecCopsEnv.render``) and written as
+``DIR/env_{k}/frame_{t:05d}.png`` -- frame 0 is the reset state, frame t the state after tick t, the last one the terminal tick --
+and ``DIR/episode.json`` records each slot's winner and length.  Without ``--checkpoint`` the policies are freshly initialised.
+The env does not reset finished episodes (``auto_reset=False``), so a slot's last frame shows how its episode ended.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+from pathlib import Path
+from typing import Dict, Optional
+
+import torch
+
+from ..environments import WINNER_NAMES, VecCopsEnv
+from ..maps import load_preset
+from ..render import write_png
+from .mappo import CFG_AGENT, MAPPOTrainer, TrainerConfig, _sample
+from .self_play import runner_pack
+
+
+def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None,
+             n_thieves: Optional[int] = None, device=None) -> VecCopsEnv:
+    """The env ``watch`` plays on (its reset state is what frame 0 shows)."""
+    preset = load_preset(map_name, n_cops, n_thieves)
+    return VecCopsEnv(preset, envs, num_rays=num_rays, max_step_count=max_step_count, seed=seed, device=device, auto_reset=False)
+
+
+@torch.no_grad()
+def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, ticks: int = 2000, rays: bool = False, seed: int = 0,
+          num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None, n_thieves: Optional[int] = None, device=None,
+          log=print) -> Dict[str, object]:
+    out_dir = Path(out_dir)
+    torch.manual_seed(seed)
+    env = make_env(map_name, envs, seed, num_rays, max_step_count, n_cops, n_thieves, device)
+    runner = MAPPOTrainer(env, {"cop": CFG_AGENT, "thief": CFG_AGENT}, TrainerConfig(graph_rollout=False, graph_update=False), seed=seed)
+    if checkpoint:
+        runner.load_state_dict(torch.load(checkpoint, map_location=runner.device, weights_only=True), optimizer=False)
+    N = env.num_envs
+    W, H = (int(v) for v in env.maps[0].window_dimensions)
+    slots = list(range(N))
+    dirs = [out_dir / f"env_{k}" for k in slots]
+    for d in dirs:
+        d.mkdir(parents=True, exist_ok=True)
+
+    def save(t: int, open_host):
+        frames = env.render(slots, rays=rays).cpu().numpy()          # one launch for the K envs, one copy to the host
+        for k in slots:
+            if open_host[k]:
+                write_png(dirs[k] / f"frame_{t:05d}.png", frames[k, :W, :H])
+
+    obs, _ = env.reset()
+    starts = torch.ones(N, dtype=torch.bool, device=runner.device)
+    state = {r: rl.policy.initial_state(N) for r, rl in runner.roles.items()}
+    actions = torch.zeros(N, len(runner.agents), dtype=torch.int32, device=runner.device)
+    open_host = [True] * N
+    winner, length, ended = [None] * N, [ticks] * N, [False] * N
+    save(0, open_host)
+    for t in range(1, ticks + 1):
+        keep = (~starts).view(1, N)
+        for r, rl in runner.roles.items():                           # self_play.evaluate_agents' action selection
+            pin = torch.stack([runner_pack(obs[a]) for a in rl.agents])
+            if runner.tcfg.normalize_inputs:
+                pin = pin * runner._pin_scale
+            logits, state[r] = rl.policy.forward(pin.unsqueeze(1), state[r], keep)
+            act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
+            actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))
+        obs, _, terms, _, infos = env.step(actions)
+        starts = torch.zeros_like(starts)
+        save(t, open_host)
+        done = terms[runner.agents[0]].cpu().tolist()
+        win = infos["winner"].cpu().tolist()
+        for k in slots:
+            if open_host[k] and done[k]:
+                open_host[k], ended[k], length[k], winner[k] = False, True, t, WINNER_NAMES[int(win[k])]
+        if not any(open_host):
+            break
+    env.check_errors()
+    result = {"map": map_name, "envs": N, "ticks": ticks, "checkpoint": checkpoint, "seed": seed, "rays": bool(rays),
+              "slots": [{"env": k, "winner": winner[k], "length": length[k], "terminated": ended[k],
+                         "frames": (length[k] + 1) if ended[k] else (t + 1)} for k in slots]}
+    (out_dir / "episode.json").write_text(json.dumps(result, indent=1))
+    for s in result["slots"]:
+        log(f"[watch] env {s['env']}: {'winner ' + str(s['winner']) if s['terminated'] else 'no termination'} after {s['length']} ticks")
+    env.close()
+    return result
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--map", default="squarinth")
+    ap.add_argument("--envs", type=int, default=4, help="env slots K (one episode each, drawn in one launch per tick)")
+    ap.add_argument("--checkpoint", default=None, help="a self-play checkpoint (joint_iter_*_full_agent.pt); fresh policies without it")
+    ap.add_argument("--ticks", type=int, default=2000, help="ticks at most")
+    ap.add_argument("--rays", action="store_true", help="draw every agent's ray fan, coloured by what each ray hit")
+    ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--num-rays", type=int, default=64)
+    ap.add_argument("--max-steps", type=int, default=2000, help="episode length limit of the env (the self-play driver's 2000)")
+    args = ap.parse_args(argv)
+    if args.envs < 1 or args.ticks < 1:
+        ap.error("--envs and --ticks must be >= 1")
+    watch(args.map, args.envs, args.out, args.checkpoint, args.ticks, args.rays, args.seed, args.num_rays, args.max_steps)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

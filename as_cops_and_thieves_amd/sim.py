@@ -222,6 +222,13 @@ class CatSim:
         self._check(self._L.cat_get_state(self._h, C.byref(view), self._stream()), "cat_get_state")
         return st
 
+    def get_positions(self) -> torch.Tensor:
+        """``get_state()["pos"]`` alone: f64 [N, A, 2], every other field of the copy left NULL (asynchronous on the current stream)."""
+        pos = torch.empty((self.N, self.A, 2), dtype=torch.float64, device=self.device)
+        view = nat.CatState(*[pos.data_ptr() if k == "pos" else None for k in nat.STATE_FIELDS])
+        self._check(self._L.cat_get_state(self._h, C.byref(view), self._stream()), "cat_get_state")
+        return pos
+
     def set_state(self, **arrays) -> None:
         spec = _state_spec(self.N, self.A)
         keep = {}

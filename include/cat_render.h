@@ -1,0 +1,77 @@
+/*
+ * cat_render.h -- C ABI of libcat_learn.so, part 6: batched rgb_array frames of the env core's state, drawn on the GPU
+ * straight from device buffers (many frames per launch, no host copy of the state).
+ *
+ * Pixel contract: render.render_frame_reference (NumPy) defines every byte; render.render_rgb_array when no rays are drawn.
+ *   frame [width][height][3] uint8, x-major (the layout of pygame's surfarray); pixel (x, y) has its centre at (x + .5, y + .5).
+ *   Later layers overwrite earlier ones:
+ *   1. white background, then walls grey (60,60,60): the pixels of a wall's clipped bounding-box window
+ *      [max(int(l),0), min(int(r)+1,W)) x [max(int(b),0), min(int(t)+1,H)) with pl[0]*X + pl[1]*Y - pl[4] <= 1.0 on every plane;
+ *   2. with CAT_RENDER_RAYS: every agent's ray fan, agent by agent, ray by ray -- the segment from the agent's position to
+ *      position + (distance / ray_length) * (ray_dx[k], ray_dy[k]) in float64, lit where the pixel centre's squared distance to the
+ *      segment is <= 0.25, inside the window [int(min)-1, int(max)+2) of the segment's bounding box, coloured by obs_type;
+ *   3. the agents' discs: (X-px)^2 + (Y-py)^2 <= r^2 inside [int(px-r)-1, int(px+r)+2), blue (0,0,255) for agents < n_cops,
+ *      red (255,0,0) after; a later agent overwrites an earlier one.
+ *   W, H are the frame's own map window (int(window)); everything is clipped to it, and pixels of the frame beyond it are 255.
+ *   All arithmetic is binary64 without contraction, in the order the reference writes it.
+ *
+ * Conventions as in cat_rollout.h (status codes, stream as void*, no CPU fallback).  Bad arguments return
+ * CAT_RENDER_ERR_BAD_ARG with a message in cat_render_last_error() before any device call.
+ */
+#ifndef CAT_RENDER_H
+#define CAT_RENDER_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define CAT_RENDER_ABI_VERSION 1
+#define CAT_RENDER_MAX_AGENTS 16
+#define CAT_RENDER_RAYS 1            /* flags: draw the agents' ray fans */
+
+enum { CAT_RENDER_OK = 0, CAT_RENDER_ERR_BAD_ARG = -1, CAT_RENDER_ERR_HIP = -2 };
+
+/* ray colours by object type (WALL, COP, THIEF, MOVABLE, EMPTY); a type above 4 is drawn as EMPTY */
+#define CAT_RENDER_RAY_COLOURS { {255, 140, 0}, {0, 170, 255}, {255, 60, 160}, {0, 160, 0}, {190, 190, 190} }
+
+/* The maps of a batch, concatenated, uploaded once.  DEVICE pointers unless marked HOST. */
+typedef struct cat_render_scene {
+    int32_t n_maps;               /* M */
+    int32_t n_rays;               /* R of the ray table */
+    const int32_t *window;        /* [M][2] int(window): frame pixels of map m are [0, W) x [0, H) */
+    const int32_t *window_host;   /* HOST [M][2], the same values (argument checks) */
+    const int32_t *shape_off;     /* [M + 1] first wall of map m in the lists below; shape_off[M] = S */
+    const int32_t *shape_off_host;/* HOST [M + 1], the same values */
+    const double *shape_bb;       /* [S][4] l, b, r, t (CompiledMap.shape_bb) */
+    const int32_t *shape_first;   /* [S] first plane of the wall in `planes` (already offset to the concatenated list) */
+    const int32_t *shape_count;   /* [S] */
+    const double *planes;         /* [P][5] the first five doubles of CompiledMap.planes */
+    const double *ray_dx;         /* [R] ray_length * cos(angle) (tables.ray_table) */
+    const double *ray_dy;         /* [R] */
+} cat_render_scene;
+
+typedef struct cat_render_args {
+    int32_t F;                    /* frames */
+    int32_t width, height;        /* frame size; at least the window of every map drawn */
+    int32_t flags;                /* CAT_RENDER_RAYS */
+    int32_t n_cops, A, R, pad;    /* agents [0, n_cops) are cops; R = scene n_rays when rays are drawn */
+    double agent_radius, ray_length;
+    const int32_t *map_ids;       /* HOST [F] map of frame f (checked against n_maps and the frame size) */
+    const int32_t *map_ids_dev;   /* [F] the same values on the device */
+    const double *positions;      /* [F][A][2] */
+    const uint16_t *obs_distance; /* [F][A][R] float16 bits (cat_outputs.obs_distance); CAT_RENDER_RAYS only */
+    const uint8_t *obs_type;      /* [F][A][R] ObjectType; CAT_RENDER_RAYS only */
+    uint8_t *frames;              /* [F][width][height][3], any byte alignment */
+} cat_render_args;
+
+int cat_render_abi_version(void);
+const char *cat_render_last_error(void);
+int cat_render_frames(const cat_render_scene *scene, const cat_render_args *a, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
