@@ -139,3 +139,61 @@ def test_two_bias_vectors_are_added_by_the_kernel():
         one = _learn_native.seq_forward(xproj, w_hh, b1 + b2, h0, c0, keep, save=save)
         torch.cuda.synchronize()
         assert all(torch.equal(a, b) for a, b in zip(two[:3], one[:3]))
+
+
+@pytest.mark.parametrize("T,B", [(1, 4096), (2, 1000), (16, 8192), (33, 257)])
+def test_inference_instantiation_equals_the_training_one_bit_for_bit(T, B):
+    """The !SAVE instantiation (4 waves, nothing kept) and the training one compute the same recurrence in the same order:
+    out, h_T and c_T must be equal bit for bit, with keep masks (every other sequence restarting at t = 0, every sequence
+    at one later tick).  T = 16 is the product path of the critics evaluated per window under no_grad."""
+    import torch
+    from as_cops_and_thieves_amd.selfplay.stacked import _LSTMSeq
+    xproj, w_hh, h0, c0, keep = _case(3, T, B, True, seed=T * 100 + B)
+    keep[0, ::2] = 0.0
+    keep[T // 2] = 0.0
+    gen = torch.Generator(device="cuda").manual_seed(T)
+    bias = (0.3 * torch.randn(3, 4 * H, generator=gen, device="cuda")).to(torch.bfloat16)
+    with torch.no_grad():
+        inf = _LSTMSeq.apply(xproj, w_hh, bias, None, h0, c0, keep, None, torch.is_grad_enabled())
+    leaves = [t.detach().clone().requires_grad_(True) for t in (xproj, w_hh, h0, c0)]
+    train = _LSTMSeq.apply(leaves[0], leaves[1], bias, None, leaves[2], leaves[3], keep)
+    torch.cuda.synchronize()
+    for name, a, b in zip(("out", "h_T", "c_T"), inf, train):
+        assert torch.equal(a, b), name
+
+
+# the per-row constant k of test_per_row_errors_stay_within_k_bf16_ulps_of_the_row_scale, calibrated once on the MI355X:
+# observed worst case over B = 1, 17, 8192 was out 1.11, d_xproj 3.93, d_h0 2.65, d_c0 3.19 (all at B = 8192); k is
+# about twice that
+LSTM_K = {"out": 2.5, "d_xproj": 8.0, "d_h0": 6.0, "d_c0": 6.0}
+
+
+@pytest.mark.parametrize("B", [1, 17, 8192])
+def test_per_row_errors_stay_within_k_bf16_ulps_of_the_row_scale(B):
+    """out, d_xproj, d_h0 and d_c0 against the fp64 recurrence from the same bf16 inputs, ROW by row ((g, t, b) or (g, b)):
+    max |err| of a row <= k 2^-8 max |row of the reference| + 2^-12 max |tensor| (tests/learner_exact.row_k).  A per-tensor
+    relative error hides a single wrong (t, b); this does not (tests/test_learner_exact_host.py shows it on the CPU).
+    G = 3, T = 16; B = 1, 17 and the trainer's 8192 cover both fold paths.  Keep: every other sequence restarts at t = 0,
+    every sequence at t = 9, and 20 % at random.  Calibrated k: LSTM_K (observed worst case beside it)."""
+    import torch
+    from as_cops_and_thieves_amd.selfplay.stacked import _LSTMSeq
+    from tests import learner_exact as lx
+    G, T = 3, 16
+    xproj, w_hh, h0, c0, keep = _case(G, T, B, True, seed=B + 5)
+    keep[0, ::2] = 0.0
+    keep[9] = 0.0
+    gen = torch.Generator(device="cuda").manual_seed(B)
+    r_out = torch.randn(G, T, B, H, generator=gen, device="cuda")
+    r_h, r_c = torch.randn(G, B, H, generator=gen, device="cuda"), torch.randn(G, B, H, generator=gen, device="cuda")
+    leaves = [t.detach().clone().requires_grad_(True) for t in (xproj, w_hh, h0, c0)]
+    out, hT, cT = _LSTMSeq.apply(leaves[0], leaves[1], None, None, leaves[2], leaves[3], keep)
+    ((out.float() * r_out).sum() + (hT.float() * r_h).sum() + (cT.float() * r_c).sum()).backward()
+    ref = [t.detach().double().clone().requires_grad_(True) for t in (xproj, w_hh, h0, c0)]
+    ro, rh, rc = lx.lstm_reference(*ref, keep.double())
+    ((ro * r_out.double()).sum() + (rh * r_h.double()).sum() + (rc * r_c.double()).sum()).backward()
+    torch.cuda.synchronize()
+    ks = {"out": lx.row_k(out.detach(), ro.detach()), "d_xproj": lx.row_k(leaves[0].grad, ref[0].grad),
+          "d_h0": lx.row_k(leaves[2].grad, ref[2].grad), "d_c0": lx.row_k(leaves[3].grad, ref[3].grad)}
+    print("per-row k", B, ks)
+    for name, k in ks.items():
+        assert k <= LSTM_K[name], (name, k, ks)

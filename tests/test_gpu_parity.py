@@ -424,6 +424,42 @@ def test_device_arithmetic_is_ieee_exact():
     assert np.array_equal(out.cpu().numpy()[:20000].astype(np.uint16), want.astype(np.uint16))
 
 
+def test_device_f16_conversion_on_ties_subnormals_and_the_overflow_edge():
+    """op 2 (f64 -> f16: round to odd, then to nearest even) on the neighbourhood set of
+    test_oracle_f16_numpy.py::test_f64_to_f16_matches_numpy_exhaustive_neighbourhoods -- every finite f16 (subnormals
+    included), the midpoints between neighbours, nextafter on either side of them, 65504 / 65519.99 / 65520, +-inf, both
+    signs, no NaN -- against NumPy's astype(float16).  Then op 3 (the obs-distance pipeline) on points whose coordinates
+    sit exactly on f16 ties, against the reference's NumPy formulation."""
+    import torch
+    from as_cops_and_thieves_amd import _native as nat
+    from tests.test_oracle_f16_numpy import _numpy_distance
+    L = nat.lib()
+    h = np.arange(0, 0x7C00, dtype=np.uint16).view(np.float16).astype(np.float64)
+    mids = (h[:-1] + h[1:]) / 2
+    xs = np.concatenate([h, mids, np.nextafter(mids, np.inf), np.nextafter(mids, -np.inf),
+                         [65504.0, 65519.99, 65520.0, np.inf, 2.0 ** -25, 2.0 ** -24, 2.0 ** -25 * 3]])
+    xs = np.concatenate([xs, -xs])
+    tx = torch.from_numpy(xs).cuda()
+    out = torch.empty_like(tx)
+    assert L.cat_selftest_arith(2, tx.data_ptr(), tx.data_ptr(), out.data_ptr(), len(xs), 0, None) == 0
+    torch.cuda.synchronize()
+    with np.errstate(over="ignore"):
+        want = xs.astype(np.float16).view(np.uint16)
+    got = out.cpu().numpy().astype(np.uint16)
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, [(xs[i], hex(got[i]), hex(want[i])) for i in bad[:8]]
+    rng = np.random.default_rng(3)
+    ties = mids[(mids > 1.0) & (mids < 400.0)]
+    n = 4000
+    px, py = rng.choice(ties, n) * rng.choice([-1.0, 1.0], n), rng.choice(ties, n) * rng.choice([-1.0, 1.0], n)
+    tpx, tpy = torch.from_numpy(px).cuda(), torch.from_numpy(py).cuda()
+    out = torch.empty_like(tpx)
+    assert L.cat_selftest_arith(3, tpx.data_ptr(), tpy.data_ptr(), out.data_ptr(), n, 0, None) == 0
+    torch.cuda.synchronize()
+    want = _numpy_distance(np.stack([px, py], 1), [(0.0, 0.0)] * n).view(np.uint16)
+    assert np.array_equal(out.cpu().numpy().astype(np.uint16), want)
+
+
 def test_fused_step_equals_three_separate_calls():
     """cat_step_fused(actions=NULL, tick, auto_reset) == cat_random_actions + cat_step + cat_reset_done."""
     import torch
