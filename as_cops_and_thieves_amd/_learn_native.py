@@ -14,8 +14,8 @@ ROOT = PKG.parent
 LIB_PATH = PKG / "libcat_learn.so"
 if os.environ.get("CAT_LEARN_LIB"):         # diagnostic builds (A/B of kernel variants): another build of the same sources
     LIB_PATH = Path(os.environ["CAT_LEARN_LIB"]).resolve()
-SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render"))
-HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render"))
+SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes"))
+HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes"))
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared"]
 HIDDEN = 128
 EXPORTED_SYMBOLS = ("cat_lstm_abi_version", "cat_lstm_last_error", "cat_lstm_blocks", "cat_lstm_saved_acts_bytes", "cat_lstm_saved_cell_bytes",
@@ -73,6 +73,10 @@ DENSE_SYMBOLS = ("cat_dense_abi_version", "cat_dense_last_error", "cat_dense_bia
                  "cat_dense_wgrad_splits", "cat_dense_wgrad", "cat_dense_forward", "cat_dense_dgrad", "cat_dense_sum_chunks2")
 PPO_SYMBOLS = ("cat_ppo_abi_version", "cat_ppo_last_error", "cat_ppo_loss_grad", "cat_ppo_adam_step", "cat_ppo_gae_scan")
 RENDER_SYMBOLS = ("cat_render_abi_version", "cat_render_last_error", "cat_render_frames")
+EPISODES_SYMBOLS = ("cat_episodes_abi_version", "cat_episodes_last_error", "cat_episodes_update", "cat_episodes_summary")
+EPISODES_MAX_AGENTS = 8         # CAT_ROLLOUT_MAX_AGENTS
+EPISODES_HIST_BINS = 64
+EPISODES_MAX_TICKS = 65536      # of one cat_episodes_update launch (= CAT_MAX_ROLLOUT_TICKS)
 RENDER_RAYS = 1                 # cat_render_args.flags
 RENDER_MAX_AGENTS = 16
 
@@ -205,6 +209,12 @@ def lib() -> C.CDLL:
         L.cat_render_frames.restype = C.c_int
         L.cat_render_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         assert L.cat_render_abi_version() == 1
+        L.cat_episodes_abi_version.restype = C.c_int
+        L.cat_episodes_last_error.restype = C.c_char_p
+        for n in ("cat_episodes_update", "cat_episodes_summary"):
+            getattr(L, n).restype = C.c_int
+            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
+        assert L.cat_episodes_abi_version() == 1
         _lib = L
     return _lib
 
@@ -214,6 +224,7 @@ def _check(rc: int, what: str) -> None:
         err = (lib().cat_trunk_last_error() if "trunk" in what else lib().cat_ppo_last_error() if "ppo" in what
                else lib().cat_dense_last_error() if "dense" in what else lib().cat_rollout_last_error() if "rollout" in what
                else lib().cat_render_last_error() if "render" in what
+               else lib().cat_episodes_last_error() if "episodes" in what
                else lib().cat_lstm_last_error())
         raise RuntimeError(f"{what} failed ({rc}): {err.decode()}")
 
@@ -674,3 +685,58 @@ def rollout_post(raw, agent_indices, reward_out, done_out=None, start_out=None, 
     a = PostArgs(N, A, len(agent_indices), 0, (C.c_int32 * 8)(*agent_indices), rew.data_ptr(), term.data_ptr(), reward_out.data_ptr(),
                  reward_out.stride(0), _ptr(done_out), _ptr(start_out), _ptr(keep_out))
     _check(lib().cat_rollout_post(C.byref(a), _stream()), "cat_rollout_post")
+
+
+# ---------------------------------------------------------------------------------------------- episode accounting
+EPISODES_STATE_FIELDS = ("ret_run", "len_run", "finished", "cop_wins", "thief_wins", "timeouts", "len_sum", "len_min", "len_max",
+                         "ret_sum", "ret_sq", "len_hist")
+
+
+class EpisodesState(C.Structure):
+    """include/cat_episodes.h cat_episodes_state (device pointers)."""
+    _fields_ = [(n, C.c_void_p) for n in EPISODES_STATE_FIELDS]
+
+
+class EpisodesUpdate(C.Structure):
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("A", C.c_int32), ("max_step_count", C.c_int32),
+                ("reward", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("winner", C.c_void_p),
+                ("quota", C.c_void_p), ("s", EpisodesState)]
+
+
+class EpisodesSummaryBlock(C.Structure):
+    _fields_ = [("episodes", C.c_int64), ("cop_wins", C.c_int64), ("thief_wins", C.c_int64), ("timeouts", C.c_int64),
+                ("open_slots", C.c_int64), ("len_sum", C.c_int64), ("len_min", C.c_int32), ("len_max", C.c_int32),
+                ("ret_sum", C.c_double * EPISODES_MAX_AGENTS), ("ret_sq", C.c_double * EPISODES_MAX_AGENTS)]
+
+
+class EpisodesSummary(C.Structure):
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("quota", C.c_void_p), ("s", EpisodesState), ("out", C.c_void_p)]
+
+
+def _episodes_state(state) -> EpisodesState:
+    return EpisodesState(*[state[n].data_ptr() for n in EPISODES_STATE_FIELDS])
+
+
+def episodes_update(state, reward, terminated, truncated, winner, quota, max_step_count: int) -> None:
+    """``state``: the tracker's device tensors by name (``EPISODES_STATE_FIELDS``); reward fp32 [T, N, A], terminated / truncated
+    u8 [T, N], winner i8 [T, N], all contiguous; quota int32 [N] or None.  One launch on the current stream (capturable)."""
+    import torch
+    T, N, A = reward.shape
+    assert reward.dtype == torch.float32 and reward.is_contiguous()
+    for t, dt in ((terminated, torch.uint8), (truncated, torch.uint8), (winner, torch.int8)):
+        assert t.dtype == dt and t.shape == (T, N) and t.is_contiguous()
+    assert quota is None or (quota.dtype == torch.int32 and quota.shape == (N,) and quota.is_contiguous())
+    assert state["ret_run"].shape == (N, A) and state["len_run"].shape == (N,)
+    a = EpisodesUpdate(T, N, A, int(max_step_count), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), winner.data_ptr(),
+                       _ptr(quota), _episodes_state(state))
+    _check(lib().cat_episodes_update(C.byref(a), _stream()), "cat_episodes_update")
+
+
+def episodes_summary(state, quota, block) -> None:
+    """The per-slot ``state`` -> ``block`` (uint8 device tensor of at least ``sizeof(EpisodesSummaryBlock)`` bytes, 8-byte
+    aligned).  One launch on the current stream; the caller copies the block to the host."""
+    import torch
+    N, A = state["ret_run"].shape
+    assert block.dtype == torch.uint8 and block.is_contiguous() and block.numel() >= C.sizeof(EpisodesSummaryBlock) and block.data_ptr() % 8 == 0
+    a = EpisodesSummary(N, A, _ptr(quota), _episodes_state(state), block.data_ptr())
+    _check(lib().cat_episodes_summary(C.byref(a), _stream()), "cat_episodes_summary")

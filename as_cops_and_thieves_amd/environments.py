@@ -288,15 +288,23 @@ class VecCopsEnv:
     returned for that slot is the first observation of the new episode; ``infos`` carries the
     per-slot ``winner`` (int8: -1 none, 0 cop, 1 thief), ``terminated`` and ``truncated`` flags of
     the tick that just ended.
+
+    ``track_episodes=True`` (needs ``auto_reset``): an ``episodes.EpisodeTracker`` on the device adds the ticks of ``step``,
+    ``step_raw`` and ``rollout_random`` up into episodes -- returns, lengths, outcomes (``episode_stats()``); an explicit
+    ``reset`` abandons the episodes it cuts short.  Off by default: nothing is launched or stored.
     """
 
     metadata = BaseEnv.metadata
+    TRACKED_ROLLOUT_BYTES = 64 << 20    # rollout_random with tracking: most bytes of reward / flag rows kept per resident launch
 
     def __init__(self, maps, num_envs: int, *, slot_map_ids: Optional[Sequence[int]] = None,
                  num_rays: int = 64, max_step_count: int = 400, time_step: float = 1 / 60.0,
                  auto_reset: bool = True, device=None, seed: int = 1, env_id_offset: int = 0,
-                 physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True, query_order: str = "index"):
+                 physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True, query_order: str = "index",
+                 track_episodes: bool = False):
         gate = gate_mode(bbtree_gate, query_order)   # (before anything touches a device)
+        if track_episodes and not auto_reset:
+            raise ValueError("track_episodes=True needs auto_reset=True: the accounting restarts a slot's episode at its terminal tick")
         self.maps: List[Map] = list(maps) if isinstance(maps, (list, tuple)) else [maps]
         m0 = self.maps[0]
         for m in self.maps[1:]:
@@ -331,6 +339,30 @@ class VecCopsEnv:
         self.state_space = self._shared_observation_spaces
         self.max_step_count, self.time_step = max_step_count, time_step
         self._actions = torch.zeros((num_envs, len(everyone)), dtype=torch.int32, device=self.device)
+        self._tracker = None
+        if track_episodes:
+            from .episodes import EpisodeTracker
+            self._tracker = EpisodeTracker(num_envs, self.possible_agents, max_step_count, self.device)
+            self._tracked_rows: Dict[str, torch.Tensor] = {}
+
+    # episode accounting
+    @property
+    def episode_tracker(self):
+        """The ``EpisodeTracker`` that ``step`` / ``step_raw`` / ``rollout_random`` feed."""
+        if self._tracker is None:
+            raise RuntimeError("this VecCopsEnv was built without track_episodes=True: it keeps no episode statistics")
+        return self._tracker
+
+    def episode_stats(self, clear: bool = False) -> dict:
+        """``EpisodeTracker.summary()`` of the episodes finished since the last clear (one synchronisation)."""
+        stats = self.episode_tracker.summary()
+        if clear:
+            self._tracker.clear()
+        return stats
+
+    def _track(self, out) -> None:
+        if self._tracker is not None:
+            self._tracker.update(out["reward"], out["terminated"], out["truncated"], out["winner"])
 
     # spaces
     def observation_space(self, agent: str):
@@ -359,6 +391,8 @@ class VecCopsEnv:
         positions = None if not options else options.get("positions")
         mask = None if not options else options.get("mask")
         self._sim.reset(mask=mask, positions=positions)
+        if self._tracker is not None:
+            self._tracker.abandon(mask)
         return self._obs(), {a: {} for a in self.possible_agents}
 
     def step(self, actions):
@@ -372,6 +406,7 @@ class VecCopsEnv:
         # one launch: finished episodes are reset inside the tick kernel, which leaves the NEW episode's first
         # observations in the buffers of those slots (rewards / flags / winner are the terminal tick's)
         out = self._sim.step_fused(acts, auto_reset=self.auto_reset)
+        self._track(out)
         rewards = {aid: out["reward"][:, i] for i, aid in enumerate(self.possible_agents)}
         terminated, truncated = out["terminated"].bool(), out["truncated"].bool()   # fresh tensors
         infos = {"winner": out["winner"].clone(), "terminated": terminated, "truncated": truncated}
@@ -398,7 +433,9 @@ class VecCopsEnv:
     def step_raw(self, actions: torch.Tensor) -> Dict[str, torch.Tensor]:
         """``step`` without the per-agent dictionaries: one launch (tick + auto-reset), returns the output buffers
         themselves (``raw_outputs()``): reward fp32 [N, A], terminated / truncated u8 [N], winner, observations."""
-        return self._sim.step_fused(actions, auto_reset=self.auto_reset)
+        out = self._sim.step_fused(actions, auto_reset=self.auto_reset)
+        self._track(out)
+        return out
 
     def raw_outputs(self) -> Dict[str, torch.Tensor]:
         """The env core's output buffers as they lie on the device (``include/cat_sim.h`` ``cat_outputs``: f16 distances,
@@ -415,18 +452,39 @@ class VecCopsEnv:
         launch (``cat_rollout_fused``: the map stays in LDS, the state records stay in LDS) for the first ``ticks - 1`` ticks, whose
         outputs nobody reads (NULL output pointers: nothing is stored), and one ordinary step for the last, which leaves the
         ``[N, ...]`` output buffers as ``step`` does.  The actions are the synthetic Philox draws of ticks ``tick0 .. tick0 + ticks - 1``
-        (``cat_random_actions``).  Returns the raw output buffers (``raw_outputs()``)."""
+        (``cat_random_actions``).  Returns the raw output buffers (``raw_outputs()``).
+
+        With ``track_episodes`` the resident ticks keep their reward / terminated / truncated / winner rows (4 A + 3 bytes per env-tick;
+        the observation pointers stay NULL) in ``[T, N, ...]`` buffers of at most ``TRACKED_ROLLOUT_BYTES`` (64 MiB: 1092 ticks of 4096
+        envs of 3 agents per launch, never more than ``CAT_MAX_ROLLOUT_TICKS``), and the tracker takes each chunk in one launch."""
         ticks = int(ticks)
         if ticks < 1:
             raise ValueError("ticks must be >= 1")
         done, cap = 0, 65536
+        if self._tracker is not None:
+            A = len(self.possible_agents)
+            cap = max(1, min(cap, self.TRACKED_ROLLOUT_BYTES // (self.num_envs * (4 * A + 3))))
         while ticks - 1 - done > 0:
             n = min(cap, ticks - 1 - done)
-            self._sim.rollout_fused(n, None, tick=tick0 + done, auto_reset=self.auto_reset, out={})
+            rows = {} if self._tracker is None else self._tracked_rollout_rows(min(cap, ticks - 1), n)
+            self._sim.rollout_fused(n, None, tick=tick0 + done, auto_reset=self.auto_reset, out=rows)
+            self._track(rows)
             done += n
         out = self._sim.step_fused(None, tick=tick0 + ticks - 1, auto_reset=self.auto_reset)
+        self._track(out)
         self._sim.check_errors()   # thousands of ticks went by inside one launch: a flag raised by any of them ends the run here, not never
         return out
+
+    def _tracked_rollout_rows(self, rows: int, n: int) -> Dict[str, torch.Tensor]:
+        """The first ``n`` rows of the ``[rows, N, ...]`` reward / flag buffers of a tracked ``rollout_random`` (kept, and grown when a
+        longer chunk comes)."""
+        from .sim import _OUT_SPEC
+        keys = ("reward", "terminated", "truncated", "winner")
+        if not self._tracked_rows or self._tracked_rows["reward"].shape[0] < rows:
+            N, A = self.num_envs, len(self.possible_agents)
+            self._tracked_rows = {k: torch.zeros((rows,) + tuple(_OUT_SPEC[k][0](N, A, 0)), dtype=_OUT_SPEC[k][1], device=self.device)
+                                  for k in keys}
+        return {k: self._tracked_rows[k][:n] for k in keys}
 
     def render(self, env_ids: Optional[Sequence[int]] = None, rays: bool = False) -> torch.Tensor:
         """``rgb_array`` frames of the env slots ``env_ids`` (default ``[0]``), drawn on the GPU in one launch
@@ -457,9 +515,10 @@ class VecCopsEnv:
         wall contact had to be dropped."""
         self._sim.check_errors()
 
-    def get_env_state(self) -> Dict[str, torch.Tensor]:
-        """Full simulator state (bodies, caches, counters) for checkpointing."""
-        return self._sim.get_state()
+    def get_env_state(self, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """Full simulator state (bodies, caches, counters) for checkpointing: a copy on the device, no synchronisation.  ``out``: the
+        dictionary an earlier call returned, overwritten instead of allocating a new one."""
+        return self._sim.get_state(out)
 
     def set_env_state(self, **arrays) -> None:
         self._sim.set_state(**arrays)

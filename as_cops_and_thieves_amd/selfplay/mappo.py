@@ -99,6 +99,11 @@ class TrainerConfig:
     normalize_inputs: bool = False         # False = the reference: raw distances (0..400) and type codes (0..4) go into the
                                            # convolutions (skrl's state_preprocessor is None).  True (build-side option):
                                            # distances / ray length, types / 4 -- see tools/learn_curve.py
+    episode_stats: bool = False            # with an env that offers ``episode_stats`` / ``episode_tracker`` (``VecCopsEnv(track_episodes=True)``): ``read_stats``
+                                           # adds the episodes, the cops' win rate, the mean episode length and every agent's mean
+                                           # return of the episodes finished during this ``train()`` call.  The accounting rides inside the
+                                           # env's step (captured and replayed with the rollout graph); nothing of the rollout or the update
+                                           # changes
 
 
 def compute_gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: torch.Tensor,
@@ -631,8 +636,18 @@ class MAPPOTrainer:
             s = rl.stat.cpu()
             for g, a in enumerate(rl.agents):
                 out[f"{a}/policy_loss"], out[f"{a}/value_loss"], out[f"{a}/kl"] = float(s[0, g]), float(s[1, g]), float(s[2, g])
+        ep = self._episode_stats()
+        if ep is not None:
+            e = ep()
+            out["episodes"], out["cop_win_rate"], out["mean_episode_length"] = e["episodes"], e["cop_win_rate"], e["mean_length"]
+            for a in self.agents:
+                out[f"mean_return/{a}"] = e[f"mean_return/{a}"]
         self.stats = out
         return out
+
+    def _episode_stats(self):
+        """The env's ``episode_stats`` when ``TrainerConfig.episode_stats`` asks for it and the env offers it, else None."""
+        return getattr(self.env, "episode_stats", None) if self.tcfg.episode_stats else None
 
     def set_frozen(self, role: Optional[str] = None, policy: Optional[bool] = None, value: Optional[bool] = None) -> None:
         for rl in self.roles.values():
@@ -651,6 +666,9 @@ class MAPPOTrainer:
         tc = self.tcfg
         timesteps = tc.timesteps if timesteps is None else timesteps
         self.timestep = 0
+        ep = self._episode_stats()
+        if ep is not None:
+            self.env.episode_tracker.clear()                     # the figures of read_stats describe this call
         if freeze_policies_first:
             self.set_frozen(policy=tc.policy_freeze_duration > 0, value=False)
         while self.timestep < timesteps:

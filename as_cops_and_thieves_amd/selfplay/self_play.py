@@ -38,6 +38,7 @@ from __future__ import annotations
 import argparse
 import dataclasses
 import inspect
+import json
 import os
 import random
 import sys
@@ -107,6 +108,86 @@ def evaluate_agents(env, runner: MAPPOTrainer, n_episodes: int, random_roles: Tu
     return float((w == 0).sum()) / n_episodes, float((w == 1).sum()) / n_episodes
 
 
+class _Rewind:
+    """What a later evaluation on the same env can see of this one, kept per tick for the ticks since the last poll: the global
+    generators ``_sample`` / ``torch.randint`` draw from (host-side reads) and a device-side copy of the env's state
+    (``get_env_state``: no synchronisation; the copies of a tick ``window`` ticks back are overwritten in place).  ``restore(tick)`` puts
+    both back to where they stood after that tick."""
+
+    def __init__(self, env, device, window: int):
+        self.env, self.device, self.window, self.kept = env, device, window, {}
+
+    def keep(self, tick: int) -> None:
+        old = self.kept.get(tick % self.window)
+        rng = (torch.get_rng_state(), torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None)
+        self.kept[tick % self.window] = (tick, rng, self.env.get_env_state(out=None if old is None else old[2]))
+
+    def restore(self, tick: int) -> None:
+        kept_tick, rng, state = self.kept[tick % self.window]
+        assert kept_tick == tick, (kept_tick, tick)
+        self.env.set_env_state(**state)
+        torch.set_rng_state(rng[0])
+        if rng[1] is not None:
+            torch.cuda.set_rng_state(rng[1], self.device)
+
+
+@torch.no_grad()
+def evaluate_agents_tracked(env, runner: MAPPOTrainer, n_episodes: int, random_roles: Tuple[str, ...] = (),
+                            poll_every: int = 32) -> Tuple[float, float]:
+    """``evaluate_agents`` with the book-keeping done on the device by the env's ``episode_tracker`` (``episodes.EpisodeTracker``,
+    which the env feeds on every ``step``): the same tick loop, but the host looks at the number of slots still owing an episode only
+    every ``poll_every`` ticks instead of every tick, and a slot plays several episodes in a row, so any ``n_episodes`` is allowed.
+    Slot n counts its first ``n_episodes // N + (n < n_episodes % N)`` episodes.  For ``n_episodes <= N`` that is the first episode of
+    the first ``n_episodes`` slots: from the same generator state the result equals ``evaluate_agents``'s exactly -- the ticks played
+    between the last counted episode and the next poll count nothing.  Those ticks are then taken back (``_Rewind``): the global
+    generators and the env's state are put back to where the tick that ended the last counted episode left them, which is where
+    ``evaluate_agents`` stops, so a later evaluation on the same env starts from the same state either way.  Beyond the surface
+    ``evaluate_agents`` uses, the env must offer ``episode_tracker`` and ``get_env_state(out=None)`` / ``set_env_state(**state)``.
+    Cost of ``poll_every``: the window holds that many full copies of the env state on the device (a few hundred bytes per slot
+    each), and every tick makes one state-copy launch and two host reads of generator state (a new 5 KB CPU snapshot each)."""
+    N = env.num_envs
+    assert N == runner.N and n_episodes >= 1 and poll_every >= 1
+    tracker = env.episode_tracker
+    obs, _ = env.reset()
+    quota = torch.full((N,), n_episodes // N, dtype=torch.int32)
+    quota[:n_episodes % N] += 1
+    tracker.set_quota(quota)
+    tracker.abandon()
+    tracker.clear()
+    starts = torch.ones(N, dtype=torch.bool, device=runner.device)
+    state = {r: rl.policy.initial_state(N) for r, rl in runner.roles.items()}
+    actions = torch.zeros(N, len(runner.agents), dtype=torch.int32, device=runner.device)
+    limit = int(quota.max()) * env.max_step_count + 2
+    rewind = _Rewind(env, runner.device, poll_every)
+    stats, tick = None, 0
+    while tick < limit:
+        keep = (~starts).view(1, N)
+        for r, rl in runner.roles.items():
+            pin = torch.stack([runner_pack(obs[a]) for a in rl.agents])
+            if runner.tcfg.normalize_inputs:
+                pin = pin * runner._pin_scale
+            logits, state[r] = rl.policy.forward(pin.unsqueeze(1), state[r], keep)
+            act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
+            rnd = [ar in random_roles for ar in rl.agent_roles]
+            if any(rnd):                                # a uniformly random opponent (not part of the reference protocol)
+                rows = torch.tensor(rnd, device=runner.device).view(rl.G, 1)
+                act = torch.where(rows, torch.randint(0, 4, (rl.G, N), device=runner.device), act)
+            actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))
+        obs, _, terms, _, _ = env.step(actions)
+        starts = terms[runner.agents[0]].clone()
+        tick += 1
+        rewind.keep(tick)
+        if tick % poll_every == 0 or tick == limit:
+            stats = tracker.summary()                   # the one host synchronisation of these poll_every ticks
+            if stats["open_slots"] == 0:
+                break
+    assert stats is not None and stats["open_slots"] == 0 and stats["episodes"] == n_episodes, stats
+    # a slot's counted episodes are its first ones after the reset, back to back: the last of them ended at tick max(len_sum), which
+    # lies after the poll before this one (slots were still open then), i.e. within the poll_every ticks kept
+    rewind.restore(int(tracker.per_slot()["len_sum"].max()))
+    return float(stats["cop_wins"]) / n_episodes, float(stats["thief_wins"]) / n_episodes
+
+
 @torch.no_grad()
 def mean_reward_per_tick(env, runner: MAPPOTrainer, ticks: int, random_roles: Tuple[str, ...] = ()) -> Dict[str, float]:
     """Diagnostic (not part of the reference protocol): reset ``env``, act for ``ticks`` ticks with sampled actions
@@ -144,9 +225,10 @@ def runner_pack(obs_agent):
 
 
 def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, learned_role: str, opponent_role: str,
-                   opponent_archive: Path, tc: TrainingConfig, rng: random.Random, log=print) -> Dict[str, bool]:
+                   opponent_archive: Path, tc: TrainingConfig, rng: random.Random, log=print, tracked: bool = False) -> Dict[str, bool]:
     """``agent_learning_utils.py:233-380``: the newly trained ``learned_role`` against up to
-    ``tc.num_opponents_to_evaluate`` distinct archived ``opponent_role`` policies.  Returns {opponent file: opponent won}."""
+    ``tc.num_opponents_to_evaluate`` distinct archived ``opponent_role`` policies.  Returns {opponent file: opponent won}.
+    ``tracked``: play the episodes through ``evaluate_agents_tracked`` (``eval_env`` must feed an ``episode_tracker``)."""
     results: Dict[str, bool] = {}
     evaluator.load_state_dict(learned.state_dict(), roles=[learned_role], optimizer=False)
     seen = set()
@@ -169,7 +251,7 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
         seen.add(name)
         evaluator.load_state_dict(torch.load(path, map_location=evaluator.device, weights_only=True), roles=[opponent_role],
                                   optimizer=False)                       # copy_role_models: policy + value weights
-        cop_rate, thief_rate = evaluate_agents(eval_env, evaluator, tc.n_trial_episodes)
+        cop_rate, thief_rate = (evaluate_agents_tracked if tracked else evaluate_agents)(eval_env, evaluator, tc.n_trial_episodes)
         opponent_won = (thief_rate > cop_rate) if learned_role == tc.cop_role_prefix else (cop_rate > thief_rate)
         archive.update_policy_win_rate(opponent_archive, name, opponent_won, tc.win_rate_buffer_size)
         results[name] = opponent_won
@@ -182,12 +264,16 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   role_cfg: Optional[Dict[str, RoleConfig]] = None, num_rays: int = 64, n_cops: Optional[int] = None,
                   n_thieves: Optional[int] = None, max_step_count: int = 2000, eval_envs: Optional[int] = None,
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
-                  query_order: str = "index") -> Dict[str, object]:
+                  query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
     ``env_factory(num_envs, seed[, env_id_offset])``: build the envs some other way (the CPU tests pass a stand-in env with the
     same surface).
+    ``tracked_eval``: the evaluation env is built with ``track_episodes=True`` and evaluation goes through
+    ``evaluate_agents_tracked``.  ``episode_stats``: the training env is built with ``track_episodes=True``, the trainer reports the
+    training episodes (``TrainerConfig.episode_stats``), every iteration's log line carries their win rate and mean length, and rank
+    0 writes ``episode_stats.json``, one entry per iteration (in a data-parallel run: the episodes of rank 0's shard of the envs).  Envs of an ``env_factory`` must bring their own ``episode_tracker``.
 
     With an initialised ``torch.distributed`` group of W > 1 ranks this is ONE data-parallel job: ``num_envs`` is the TOTAL,
     rank r simulates ``shard_envs(num_envs, r, W)``; the trainer all-reduces its gradient | KL buffer every optimiser step (all
@@ -213,6 +299,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     # TrainerConfig's 128-tick rollouts: with 16-tick rollouts the cops' win rate against random thieves stays at its untrained
     # 10 % for 262 M env-steps, with 128 it rises (profiles/r02_learning_curves.txt); the reference collects 4096 ticks per update
     trainer_cfg = trainer_cfg or TrainerConfig(timesteps=tc.training_timesteps_per_role_training)
+    if episode_stats:
+        trainer_cfg = dataclasses.replace(trainer_cfg, episode_stats=True)
     out_dir = Path(out_dir)
     arch = {tc.cop_role_prefix: out_dir / "cops", tc.thief_role_prefix: out_dir / "thieves"}
     if chief:
@@ -220,10 +308,13 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
             p.mkdir(parents=True, exist_ok=True)
     sync()
     n_eval = eval_envs or tc.n_trial_episodes
+    train_factory = eval_factory = env_factory
     if env_factory is None:
         preset = load_preset(map_name, n_cops, n_thieves)
-        env_factory = lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
-                                                     env_id_offset=off, query_order=query_order)
+        make = lambda track: (lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
+                                                             env_id_offset=off, query_order=query_order, track_episodes=track))
+        env_factory = train_factory = make(episode_stats)
+        eval_factory = make(tracked_eval)
     n_local, offset = shard_envs(num_envs, rank, world)
     if multi:
         # checked on EVERY rank from the same numbers, so that all of them refuse together (a rank that raised alone would leave the others in the
@@ -237,8 +328,11 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     takes_offset = len(inspect.signature(env_factory).parameters) >= 3
     if multi and not takes_offset:
         raise TypeError("a data-parallel run needs env_factory(num_envs, seed, env_id_offset): the ranks must simulate different envs")
-    env = env_factory(n_local, seed, offset) if takes_offset else env_factory(n_local, seed)
-    eval_env = env_factory(n_eval, seed + 7919)          # every rank builds one (the evaluator's shapes); only rank 0 plays on it
+    env = train_factory(n_local, seed, offset) if takes_offset else train_factory(n_local, seed)
+    eval_env = eval_factory(n_eval, seed + 7919)         # every rank builds one (the evaluator's shapes); only rank 0 plays on it
+    for what, e, attr in (("tracked_eval", eval_env, "episode_tracker"), ("episode_stats", env, "episode_stats")):
+        if {"tracked_eval": tracked_eval, "episode_stats": episode_stats}[what] and not hasattr(e, attr):
+            raise TypeError(f"{what}=True needs envs with an {attr!r} (VecCopsEnv(track_episodes=True)); the env_factory's have none")
     role_cfg = role_cfg or {"cop": CFG_AGENT, "thief": CFG_AGENT}        # self_play_driver.py passes CFG_AGENT
     trainer = MAPPOTrainer(env, role_cfg, trainer_cfg, seed=seed)
     evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False),
@@ -249,7 +343,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         latest = [archive.get_latest_policy_from_archive(arch[r], r) for r in arch]
         its = [int(Path(p).stem.split("_")[-1]) for p in latest if p]
         start = max(its) + 1 if its else 0
-    history = []
+    history, episode_log = [], []
+    stats_file = out_dir / "episode_stats.json"
+    if episode_stats and chief and start > 0 and stats_file.exists():
+        episode_log = json.loads(stats_file.read_text())
     for it in range(start, start + iterations):
         # ---- 1. continue from the latest archived checkpoint of each role (orchestration.py:146-211)
         for role in arch:
@@ -266,8 +363,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         if chief:
             try:
                 # ---- 3. evaluation against archived opponents (:199-228)
-                ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log),
-                      thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log)}
+                ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval),
+                      thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval)}
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -275,7 +372,13 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                     for role in arch:
                         archive.add_policy_to_archive(str(ck), arch[role], it, role)
                 log(f"[self-play] iteration {it}: saved {ck.name}; evaluated {len(ev[cop])} thief and {len(ev[thief])} cop opponents"
-                    + (f"; {world} ranks x {n_local} envs" if multi else ""))
+                    + (f"; {world} ranks x {n_local} envs" if multi else "")
+                    + (f"; training episodes{' of rank 0' if multi else ''} {stats['episodes']}, cop win rate {stats['cop_win_rate']:.3f}, mean length "
+                       f"{stats['mean_episode_length']:.1f}" if episode_stats else ""))
+                if episode_stats:
+                    keys = ("episodes", "cop_win_rate", "mean_episode_length") + tuple(f"mean_return/{a}" for a in trainer.agents)
+                    episode_log.append(dict({"iteration": it}, **{k: stats[k] for k in keys}))
+                    stats_file.write_text(json.dumps(episode_log, indent=1))
             except Exception as exc:   # noqa: BLE001 -- handed to the other ranks below, then re-raised here
                 if not multi:
                     raise
@@ -361,6 +464,10 @@ def main() -> None:
                     "model_utils.py:45-77) instead of the LSTM pair its drivers use")
     ap.add_argument("--query-order", default="index", choices=["index", "chipmunk"],
                     help="visiting order of the walls in segment queries: index order (default) or Chipmunk's static tree (DESIGN.md D2)")
+    ap.add_argument("--tracked-eval", action="store_true", help="evaluate through evaluate_agents_tracked: episode book-keeping on the device, "
+                    "the host polls every 32 ticks instead of every tick")
+    ap.add_argument("--episode-stats", action="store_true", help="account the training episodes on the device: win rate and mean length in "
+                    "every iteration's log line, episode_stats.json in --out (with --gpus N: of rank 0's shard)")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -383,7 +490,7 @@ def main() -> None:
     res = run_self_play(args.map, args.envs, args.out, iterations=args.iterations, training=tc, trainer_cfg=tcfg, role_cfg=role_cfg,
                         num_rays=args.rays, n_cops=args.cops, n_thieves=args.thieves, max_step_count=args.max_step_count,
                         eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
-                        query_order=args.query_order)
+                        query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats)
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

@@ -216,8 +216,11 @@ class CatSim:
         self.cfg.seed = int(seed) & (2**64 - 1)
         self._check(self._L.cat_set_seed(self._h, self.cfg.seed, self._stream()), "cat_set_seed")
 
-    def get_state(self) -> Dict[str, torch.Tensor]:
-        st = {k: torch.zeros(shape, dtype=dt, device=self.device) for k, (shape, dt) in _state_spec(self.N, self.A).items()}
+    def get_state(self, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """A copy of the simulator state (asynchronous on the current stream).  ``out``: the tensors of an earlier call, written again
+        instead of allocating new ones."""
+        st = out if out is not None else {k: torch.zeros(shape, dtype=dt, device=self.device)
+                                          for k, (shape, dt) in _state_spec(self.N, self.A).items()}
         view = nat.CatState(*[st[k].data_ptr() if st[k].numel() else None for k in nat.STATE_FIELDS])
         self._check(self._L.cat_get_state(self._h, C.byref(view), self._stream()), "cat_get_state")
         return st
