@@ -14,8 +14,8 @@ ROOT = PKG.parent
 LIB_PATH = PKG / "libcat_learn.so"
 if os.environ.get("CAT_LEARN_LIB"):         # diagnostic builds (A/B of kernel variants): another build of the same sources
     LIB_PATH = Path(os.environ["CAT_LEARN_LIB"]).resolve()
-SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes"))
-HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes"))
+SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes", "act"))
+HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes", "act"))
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared"]
 HIDDEN = 128
 EXPORTED_SYMBOLS = ("cat_lstm_abi_version", "cat_lstm_last_error", "cat_lstm_blocks", "cat_lstm_saved_acts_bytes", "cat_lstm_saved_cell_bytes",
@@ -74,6 +74,9 @@ DENSE_SYMBOLS = ("cat_dense_abi_version", "cat_dense_last_error", "cat_dense_bia
 PPO_SYMBOLS = ("cat_ppo_abi_version", "cat_ppo_last_error", "cat_ppo_loss_grad", "cat_ppo_adam_step", "cat_ppo_gae_scan")
 RENDER_SYMBOLS = ("cat_render_abi_version", "cat_render_last_error", "cat_render_frames")
 EPISODES_SYMBOLS = ("cat_episodes_abi_version", "cat_episodes_last_error", "cat_episodes_update", "cat_episodes_summary")
+ACT_SYMBOLS = ("cat_act_abi_version", "cat_act_last_error", "cat_act_supported", "cat_act_step")
+ACT_MAX_AGENTS = 8              # CAT_ACT_MAX_AGENTS
+ACT_SAMPLE, ACT_GREEDY = 0, 1   # cat_act_args.mode
 EPISODES_MAX_AGENTS = 8         # CAT_ROLLOUT_MAX_AGENTS
 EPISODES_HIST_BINS = 64
 EPISODES_MAX_TICKS = 65536      # of one cat_episodes_update launch (= CAT_MAX_ROLLOUT_TICKS)
@@ -215,6 +218,13 @@ def lib() -> C.CDLL:
             getattr(L, n).restype = C.c_int
             getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
         assert L.cat_episodes_abi_version() == 1
+        L.cat_act_abi_version.restype = C.c_int
+        L.cat_act_last_error.restype = C.c_char_p
+        L.cat_act_supported.restype = C.c_int
+        L.cat_act_supported.argtypes = [C.c_void_p]
+        L.cat_act_step.restype = C.c_int
+        L.cat_act_step.argtypes = [C.c_void_p, C.c_void_p]
+        assert L.cat_act_abi_version() == 1
         _lib = L
     return _lib
 
@@ -225,6 +235,7 @@ def _check(rc: int, what: str) -> None:
                else lib().cat_dense_last_error() if "dense" in what else lib().cat_rollout_last_error() if "rollout" in what
                else lib().cat_render_last_error() if "render" in what
                else lib().cat_episodes_last_error() if "episodes" in what
+               else lib().cat_act_last_error() if "cat_act" in what
                else lib().cat_lstm_last_error())
         raise RuntimeError(f"{what} failed ({rc}): {err.decode()}")
 
@@ -740,3 +751,72 @@ def episodes_summary(state, quota, block) -> None:
     assert block.dtype == torch.uint8 and block.is_contiguous() and block.numel() >= C.sizeof(EpisodesSummaryBlock) and block.data_ptr() % 8 == 0
     a = EpisodesSummary(N, A, _ptr(quota), _episodes_state(state), block.data_ptr())
     _check(lib().cat_episodes_summary(C.byref(a), _stream()), "cat_episodes_summary")
+
+
+# ---------------------------------------------------------------------------------------------- the fused act tick
+ACT_PARAM_FIELDS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "fc_w", "fc_b", "w_ih", "w_hh", "b_ih", "b_hh",
+                    "head0_w", "head0_b", "head1_w", "head1_b", "head2_w", "head2_b")
+# models.LSTMPolicy's parameter names in the order of ACT_PARAM_FIELDS
+ACT_PARAM_NAMES = ("features_extractor.0.weight", "features_extractor.0.bias", "features_extractor.2.weight", "features_extractor.2.bias",
+                   "features_extractor.5.weight", "features_extractor.5.bias", "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0",
+                   "lstm.bias_hh_l0", "policy_head.0.weight", "policy_head.0.bias", "policy_head.2.weight", "policy_head.2.bias",
+                   "policy_head.4.weight", "policy_head.4.bias")
+
+
+class ActDims(C.Structure):
+    _fields_ = [("G", C.c_int32), ("N", C.c_int32), ("A", C.c_int32), ("R", C.c_int32)]
+
+
+class ActParams(C.Structure):
+    """include/cat_act.h cat_act_params."""
+    _fields_ = [(n, C.c_void_p) for n in ACT_PARAM_FIELDS] + [("stride", C.c_int64)]
+
+
+class ActArgs(C.Structure):
+    """include/cat_act.h cat_act_args."""
+    _fields_ = [("d", ActDims), ("agent", C.c_int32 * ACT_MAX_AGENTS), ("mode", C.c_int32), ("random_mask", C.c_uint32), ("row_tile", C.c_int32),
+                ("distance_scale", C.c_float), ("type_scale", C.c_float), ("pad", C.c_int32),
+                ("obs_distance", C.c_void_p), ("obs_type", C.c_void_p), ("p", ActParams), ("h", C.c_void_p), ("c", C.c_void_p),
+                ("keep", C.c_void_p), ("uniform", C.c_void_p), ("actions", C.c_void_p), ("logits_out", C.c_void_p), ("logp_out", C.c_void_p)]
+
+
+def act_supported(G: int, N: int, A: int, R: int) -> bool:
+    d = ActDims(G, N, A, R)
+    return bool(lib().cat_act_supported(C.byref(d)))
+
+
+def act_params(params) -> ActParams:
+    """``params``: models.LSTMPolicy's parameter name -> stacked bf16 view [G, ...] (``FlatParams.views`` without the ``policy.`` prefix)
+    whose per-network blocks are contiguous and share ONE stride between the networks (rows of one flat buffer)."""
+    import torch
+    ts = [params[n] for n in ACT_PARAM_NAMES]
+    stride = ts[0].stride(0)
+    for t in ts:
+        assert t.dtype == torch.bfloat16 and t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) == stride) and t.data_ptr() % 16 == 0
+    return ActParams(*[t.data_ptr() for t in ts], stride)
+
+
+def act_step(raw, agent_indices, params, h, c, keep, uniform, actions, distance_scale: float = 1.0, type_scale: float = 1.0, greedy: bool = False,
+             random_mask: int = 0, logits_out=None, logp_out=None, row_tile: int = 0) -> None:
+    """One act tick of the G stacked recurrent policies in one launch (include/cat_act.h).  raw = the env core's output buffers
+    (``VecCopsEnv.raw_outputs()``: obs_distance f16 / obs_type u8 [N, A, R]); params = ``act_params(...)`` (or the mapping it takes); h, c bf16
+    [G, N, 128] updated in place; keep fp32 [N] or None; uniform fp32 [G, N]; actions int32 [N, A]: column ``agent_indices[g]`` receives
+    policy g's action; logits_out bf16 [G, N, 4] / logp_out fp32 [G, N] optional."""
+    import torch
+    od, ot = raw["obs_distance"], raw["obs_type"]
+    N, A, R = od.shape
+    G = len(agent_indices)
+    assert od.dtype == torch.float16 and ot.dtype == torch.uint8 and od.is_contiguous() and ot.is_contiguous() and ot.shape == od.shape
+    assert 1 <= G <= ACT_MAX_AGENTS and act_supported(G, N, A, R), f"cat_act_step does not take G={G}, A={A}, R={R}"
+    for t in (h, c):
+        assert t.dtype == torch.bfloat16 and t.shape == (G, N, HIDDEN) and t.is_contiguous()
+    assert keep is None or (keep.dtype == torch.float32 and keep.numel() == N and keep.is_contiguous())
+    assert uniform.dtype == torch.float32 and uniform.shape == (G, N) and uniform.is_contiguous()
+    assert actions.dtype == torch.int32 and actions.shape == (N, A) and actions.is_contiguous()
+    assert logits_out is None or (logits_out.dtype == torch.bfloat16 and logits_out.shape == (G, N, 4) and logits_out.is_contiguous())
+    assert logp_out is None or (logp_out.dtype == torch.float32 and logp_out.shape == (G, N) and logp_out.is_contiguous())
+    p = params if isinstance(params, ActParams) else act_params(params)
+    a = ActArgs(ActDims(G, N, A, R), (C.c_int32 * ACT_MAX_AGENTS)(*agent_indices), ACT_GREEDY if greedy else ACT_SAMPLE, int(random_mask), int(row_tile),
+                distance_scale, type_scale, 0, od.data_ptr(), ot.data_ptr(), p, h.data_ptr(), c.data_ptr(), _ptr(keep), uniform.data_ptr(),
+                actions.data_ptr(), _ptr(logits_out), _ptr(logp_out))
+    _check(lib().cat_act_step(C.byref(a), _stream()), "cat_act_step")

@@ -1,0 +1,363 @@
+// cat_act.hip -- libcat_learn.so, part 8: the act tick of the stacked recurrent policies in one launch (include/cat_act.h).
+//
+// A workgroup of four waves owns TM = 32 or 64 rows (envs) of ONE network and carries them from the env core's observation
+// buffers to the action.  Every layer is Y^T = W X^T on mfma_f32_16x16x32_bf16 with the WEIGHTS as the A operand: a lane's
+// fragment is 16 contiguous bytes of one weight row, loaded straight from global memory (the parameters of a network, ~0.6 MB,
+// are shared by all its workgroups and stay in L2; they never pass through the LDS), the activations are the B operand, read
+// from a bf16 LDS image [row][feature], and a lane's four accumulator registers are four consecutive output features of one
+// row: one 8-byte LDS store after bias and activation.  The waves split the OUTPUT features of a layer and each keeps all
+// TM / 16 row tiles in its accumulators, so a weight fragment is fetched once per workgroup.
+//
+//  - the two convolutions run by direct taps, one conv2 output position at a time: the five conv1 positions it reads are
+//    computed into a [TM][5 * 64] image (wave w owns conv1 channels 16 w .. 16 w + 15, its one weight fragment lives in
+//    registers: K = 10 padded to 32), then conv2 is a [TM x 320] x [320 x 32] product whose ten weight fragments per wave
+//    also stay in registers for the whole loop.  The 64-channel intermediate of all positions never exists;
+//  - conv2 writes its output in (channel, position) order, the column order of the 256-wide layer's weight;
+//  - the LSTM: a wave takes 16 hidden units at a time and accumulates their four gates (rows u, 128 + u, 256 + u, 384 + u of
+//    W_ih | W_hh over the [f | h] image), so the cell runs on the accumulators and only h', c' leave;
+//  - the last layer (4 logits) is one zero-padded 16-row tile; the lanes that hold a row's four logits draw the action.
+//
+// LDS: two regions that the stages reuse -- A: observation rows + conv1 image, later [f | h], later head layer 1;
+// B: conv2 output, later h' and head layer 2.
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "cat_act.h"
+
+namespace {
+
+constexpr int BLOCK = 256, HID = CAT_ACT_HIDDEN;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+enum { A_NONE = 0, A_RELU = 1, A_TANH = 2 };
+
+template <int R> struct Geo {
+    static constexpr int L1 = (R - 5) / 2 + 1, L2 = (L1 - 5) / 3 + 1, KFC = 32 * L2;
+    static constexpr int XIN_LD = 2 * R + 8, C1_LD = 5 * 64 + 8, X2_LD = KFC + 8, FH_LD = 256 + HID + 8, HN_LD = HID + 8, H2_LD = 64 + 8;
+    static constexpr int A_LD = (XIN_LD + C1_LD > FH_LD ? XIN_LD + C1_LD : FH_LD);          // elements per row of region A
+    static constexpr int B_LD = (X2_LD > HN_LD + H2_LD ? X2_LD : HN_LD + H2_LD);            // and of region B
+    static constexpr size_t lds_bytes(int tm) { return (size_t)tm * (A_LD + B_LD) * 2; }
+};
+
+__device__ __forceinline__ float sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+template <int ACT> __device__ __forceinline__ float act_fwd(float x)
+{
+    if (ACT == A_RELU) return fmaxf(x, 0.0f);
+    if (ACT == A_TANH) return tanh_fast(x);
+    return x;
+}
+__device__ __forceinline__ f32x4 ld4(const __bf16 *p) { return __builtin_convertvector(*(const bf16x4 *)p, f32x4); }
+
+// Y[m][n] = act(sum_k X[m][k] W[n][k] + bias[n]) for the TM rows of the workgroup: X, Y bf16 LDS images, W [nout][K] global.
+template <int K, int MT, int ACT>
+__device__ __forceinline__ void layer(const __bf16 *W, const __bf16 *bias, int nout, const __bf16 *X, int ldx, __bf16 *Y, int ldy,
+                                      int w, int q, int r)
+{
+    for (int nt = w; nt < nout / 16; nt += 4) {
+        f32x4 acc[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const __bf16 *wrow = W + (size_t)(nt * 16 + r) * K + 8 * q;
+#pragma unroll
+        for (int s = 0; s < K / 32; ++s) {
+            const bf16x8 wf = *(const bf16x8 *)(wrow + 32 * s);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const bf16x8 xf = *(const bf16x8 *)(X + (mt * 16 + r) * ldx + 32 * s + 8 * q);
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc[mt], 0, 0, 0);
+            }
+        }
+        const f32x4 b = ld4(bias + nt * 16 + 4 * q);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = act_fwd<ACT>(acc[mt][e] + b[e]);
+            *(bf16x4 *)(Y + (mt * 16 + r) * ldy + nt * 16 + 4 * q) = __builtin_convertvector(v, bf16x4);
+        }
+    }
+}
+
+template <int R, int MT>
+__global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
+{
+    using G = Geo<R>;
+    constexpr int TM = 16 * MT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __bf16 *regA = (__bf16 *)smem, *regB = regA + TM * G::A_LD;
+    __bf16 *xin = regA, *c1 = regA + TM * G::XIN_LD, *fh = regA, *h1 = regA;       // region A over time
+    __bf16 *x2 = regB, *hn = regB, *h2 = regB + TM * G::HN_LD;                      // region B over time
+
+    const int g = blockIdx.y, row0 = blockIdx.x * TM, N = a.d.N, A = a.d.A, ai = a.agent[g];
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, q = l >> 4, r = l & 15;
+    const float *uni = a.uniform + (size_t)g * N;
+
+    if ((a.random_mask >> g) & 1u) {                 // a uniformly random agent: no network, no state
+        for (int m = tid; m < TM; m += BLOCK) {
+            const int n = row0 + m;
+            if (n < N) {
+                const int act = (int)(4.0f * uni[n]);
+                a.actions[(size_t)n * A + ai] = act < 3 ? act : 3;
+            }
+        }
+        return;
+    }
+
+    const size_t po = (size_t)g * a.p.stride;
+    const __bf16 *w1 = (const __bf16 *)a.p.conv1_w + po, *b1 = (const __bf16 *)a.p.conv1_b + po;
+    const __bf16 *w2 = (const __bf16 *)a.p.conv2_w + po, *b2 = (const __bf16 *)a.p.conv2_b + po;
+    const __bf16 *wfc = (const __bf16 *)a.p.fc_w + po, *bfc = (const __bf16 *)a.p.fc_b + po;
+    const __bf16 *wih = (const __bf16 *)a.p.w_ih + po, *whh = (const __bf16 *)a.p.w_hh + po;
+    const __bf16 *bih = (const __bf16 *)a.p.b_ih + po, *bhh = (const __bf16 *)a.p.b_hh + po;
+    const __bf16 *hw0 = (const __bf16 *)a.p.head0_w + po, *hb0 = (const __bf16 *)a.p.head0_b + po;
+    const __bf16 *hw1 = (const __bf16 *)a.p.head1_w + po, *hb1 = (const __bf16 *)a.p.head1_b + po;
+    const __bf16 *hw2 = (const __bf16 *)a.p.head2_w + po, *hb2 = (const __bf16 *)a.p.head2_b + po;
+
+    // ---- the observation rows: [distance (R) | type (R)], scaled, bf16 (cat_rollout_pack's policy row); rows >= N are zero
+    {
+        const __half *od = (const __half *)a.obs_distance;
+        const uint8_t *ot = (const uint8_t *)a.obs_type;
+        for (int i = tid; i < TM * R; i += BLOCK) {
+            const int m = i / R, rr = i - m * R, n = row0 + m;
+            float dv = 0.0f, tv = 0.0f;
+            if (n < N) {
+                const size_t o = ((size_t)n * A + ai) * R + rr;
+                dv = __half2float(od[o]) * a.distance_scale;
+                tv = (float)ot[o] * a.type_scale;
+            }
+            xin[m * G::XIN_LD + rr] = (__bf16)dv;
+            xin[m * G::XIN_LD + R + rr] = (__bf16)tv;
+        }
+    }
+    // ---- the convolutions' weights of this wave, in registers for the whole trunk
+    const int nt2 = w & 1;                            // conv2: this wave's 16 output channels
+    bf16x8 w1f, w2f[10];
+    {
+        const __bf16 zero = (__bf16)0.0f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {                 // conv1 weight [64][2][5]: row = channel 16 w + r, k = c * 5 + tap < 10
+            const int k = 8 * q + j;
+            w1f[j] = k < 10 ? w1[(16 * w + r) * 10 + k] : zero;
+        }
+#pragma unroll
+        for (int s = 0; s < 10; ++s)                  // conv2 weight [32][64][5] as k = tap * 64 + c_in: step s = (tap, half of c_in)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) w2f[s][j] = w2[((16 * nt2 + r) * 64 + (s & 1) * 32 + 8 * q + j) * 5 + (s >> 1)];
+    }
+    const f32x4 b1v = ld4(b1 + 16 * w + 4 * q), b2v = ld4(b2 + 16 * nt2 + 4 * q);
+    __syncthreads();
+
+    for (int p = 0; p < G::L2; ++p) {
+        // conv1 at positions 3 p .. 3 p + 4 -> c1[m][tap * 64 + channel]
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            const int c0 = 2 * (3 * p + t);           // first ray of the window
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const __bf16 *xr = xin + (mt * 16 + r) * G::XIN_LD + c0;
+                bf16x8 xf = {};
+                if (q == 0) {
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) xf[j] = xr[j];
+#pragma unroll
+                    for (int j = 5; j < 8; ++j) xf[j] = xr[R + j - 5];
+                } else if (q == 1) {
+                    xf[0] = xr[R + 3];
+                    xf[1] = xr[R + 4];
+                }
+                const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f, xf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[e] + b1v[e], 0.0f);
+                *(bf16x4 *)(c1 + (mt * 16 + r) * G::C1_LD + t * 64 + 16 * w + 4 * q) = __builtin_convertvector(v, bf16x4);
+            }
+        }
+        __syncthreads();
+        // conv2 at position p -> x2[m][channel * L2 + p]
+        for (int mt = w >> 1; mt < MT; mt += 2) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 10; ++s) {
+                const bf16x8 xf = *(const bf16x8 *)(c1 + (mt * 16 + r) * G::C1_LD + 32 * s + 8 * q);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[s], xf, acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                x2[(mt * 16 + r) * G::X2_LD + (16 * nt2 + 4 * q + e) * G::L2 + p] = (__bf16)fmaxf(acc[e] + b2v[e], 0.0f);
+        }
+        __syncthreads();                              // c1 is rewritten by the next position
+    }
+
+    // ---- h entering the tick (zero where an episode starts) next to f: the LSTM's input image [f (256) | h (128)]
+    const __bf16 *hg = (const __bf16 *)a.h + (size_t)g * N * HID, *cg = (const __bf16 *)a.c + (size_t)g * N * HID;
+    for (int i = tid; i < TM * (HID / 8); i += BLOCK) {
+        const int m = i / (HID / 8), ch = i % (HID / 8), n = row0 + m;
+        bf16x8 v = {};
+        if (n < N && (!a.keep || a.keep[n] != 0.0f)) v = *(const bf16x8 *)(hg + (size_t)n * HID + 8 * ch);
+        *(bf16x8 *)(fh + m * G::FH_LD + 256 + 8 * ch) = v;
+    }
+    layer<G::KFC, MT, A_TANH>(wfc, bfc, 256, x2, G::X2_LD, fh, G::FH_LD, w, q, r);
+    __syncthreads();
+
+    // ---- LSTM cell: 16 hidden units x 4 gates per pass
+    for (int j = w; j < HID / 16; j += 4) {
+        f32x4 acc[4][MT];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) acc[k][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int s = 0; s < 8; ++s) {
+            bf16x8 wf[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wf[k] = *(const bf16x8 *)(wih + (size_t)(k * HID + 16 * j + r) * 256 + 32 * s + 8 * q);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const bf16x8 xf = *(const bf16x8 *)(fh + (mt * 16 + r) * G::FH_LD + 32 * s + 8 * q);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[k], xf, acc[k][mt], 0, 0, 0);
+            }
+        }
+#pragma unroll 2
+        for (int s = 0; s < 4; ++s) {
+            bf16x8 wf[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wf[k] = *(const bf16x8 *)(whh + (size_t)(k * HID + 16 * j + r) * HID + 32 * s + 8 * q);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const bf16x8 xf = *(const bf16x8 *)(fh + (mt * 16 + r) * G::FH_LD + 256 + 32 * s + 8 * q);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[k][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[k], xf, acc[k][mt], 0, 0, 0);
+            }
+        }
+        const int u0 = 16 * j + 4 * q;                // this lane's four hidden units
+        f32x4 bi[4], bh[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { bi[k] = ld4(bih + k * HID + u0); bh[k] = ld4(bhh + k * HID + u0); }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int m = mt * 16 + r, n = row0 + m;
+            f32x4 cp = {0.f, 0.f, 0.f, 0.f};
+            if (n < N && (!a.keep || a.keep[n] != 0.0f)) cp = ld4(cg + (size_t)n * HID + u0);
+            f32x4 cn, hv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float gi = sigmoidf(acc[0][mt][e] + bi[0][e] + bh[0][e]), gf = sigmoidf(acc[1][mt][e] + bi[1][e] + bh[1][e]);
+                const float gg = tanh_fast(acc[2][mt][e] + bi[2][e] + bh[2][e]), go = sigmoidf(acc[3][mt][e] + bi[3][e] + bh[3][e]);
+                cn[e] = gf * cp[e] + gi * gg;
+                hv[e] = go * tanh_fast(cn[e]);
+            }
+            const bf16x4 hb = __builtin_convertvector(hv, bf16x4);
+            *(bf16x4 *)(hn + m * G::HN_LD + u0) = hb;
+            if (n < N) {
+                *(bf16x4 *)((__bf16 *)a.h + ((size_t)g * N + n) * HID + u0) = hb;
+                *(bf16x4 *)((__bf16 *)a.c + ((size_t)g * N + n) * HID + u0) = __builtin_convertvector(cn, bf16x4);
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- the head
+    layer<HID, MT, A_RELU>(hw0, hb0, 128, hn, G::HN_LD, h1, G::HN_LD, w, q, r);
+    __syncthreads();
+    layer<HID, MT, A_RELU>(hw1, hb1, 64, h1, G::HN_LD, h2, G::H2_LD, w, q, r);
+    __syncthreads();
+    for (int mt = w; mt < MT; mt += 4) {              // 4 logits: one 16-row tile whose rows 4 .. 15 are zero
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            bf16x8 wf = {};
+            if (r < 4) wf = *(const bf16x8 *)(hw2 + r * 64 + 32 * s + 8 * q);
+            const bf16x8 xf = *(const bf16x8 *)(h2 + (mt * 16 + r) * G::H2_LD + 32 * s + 8 * q);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc, 0, 0, 0);
+        }
+        const int n = row0 + mt * 16 + r;
+        if (q != 0 || n >= N) continue;               // lanes 0 .. 15 hold the four logits of row r
+        const f32x4 bz = ld4(hb2);
+        f32x4 zf;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) zf[e] = acc[e] + bz[e];
+        const bf16x4 zb = __builtin_convertvector(zf, bf16x4);
+        const f32x4 z = __builtin_convertvector(zb, f32x4);
+        const size_t sidx = (size_t)g * N + n;
+        // cat_rollout_sample's rule on the bf16 logits
+        const float zmax = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+        const float e0 = __expf(z[0] - zmax), e1 = __expf(z[1] - zmax), e2 = __expf(z[2] - zmax), e3 = __expf(z[3] - zmax);
+        float sum = 0.f;
+        sum += e0; sum += e1; sum += e2; sum += e3;
+        int act;
+        if (a.mode == CAT_ACT_GREEDY) {
+            act = 0;
+            float best = z[0];
+            if (z[1] > best) { best = z[1]; act = 1; }
+            if (z[2] > best) { best = z[2]; act = 2; }
+            if (z[3] > best) { best = z[3]; act = 3; }
+        } else {
+            const float u = uni[n] * sum;             // inverse CDF on the unnormalised masses
+            act = (u >= e0) + (u >= e0 + e1) + (u >= e0 + e1 + e2);
+        }
+        const float zact = act == 0 ? z[0] : act == 1 ? z[1] : act == 2 ? z[2] : z[3];
+        a.actions[(size_t)n * A + ai] = act;
+        if (a.logits_out) *(bf16x4 *)((__bf16 *)a.logits_out + 4 * sidx) = zb;
+        if (a.logp_out) a.logp_out[sidx] = zact - zmax - __logf(sum);
+    }
+}
+
+thread_local char g_err[256] = "";
+int fail(int code, const char *msg)
+{
+    snprintf(g_err, sizeof g_err, "%s", msg);
+    return code;
+}
+
+bool dims_ok(const cat_act_dims &d)
+{
+    return d.G >= 1 && d.G <= CAT_ACT_MAX_AGENTS && d.N >= 1 && d.A >= 1 && d.A <= CAT_ACT_MAX_AGENTS && (d.R == 64 || d.R == 90);
+}
+
+template <int R, int MT> int launch(const cat_act_args &a, hipStream_t stream)
+{
+    constexpr int TM = 16 * MT;
+    const size_t lds = Geo<R>::lds_bytes(TM);
+    // the 64-row tiles take more than the default 64 KB of dynamic LDS: raised on every launch (per device, not a stream operation)
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(act_kernel<R, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return fail(CAT_ACT_ERR_HIP, "cat_act_step: hipFuncSetAttribute failed");
+    hipLaunchKernelGGL((act_kernel<R, MT>), dim3((a.d.N + TM - 1) / TM, a.d.G), dim3(BLOCK), lds, stream, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CAT_ACT_OK : fail(CAT_ACT_ERR_HIP, hipGetErrorString(e));
+}
+
+}   // namespace
+
+extern "C" int cat_act_abi_version(void) { return CAT_ACT_ABI_VERSION; }
+extern "C" const char *cat_act_last_error(void) { return g_err; }
+extern "C" int cat_act_supported(const cat_act_dims *d) { return d && dims_ok(*d) ? 1 : 0; }
+
+extern "C" int cat_act_step(const cat_act_args *a, void *stream)
+{
+    if (!a || !dims_ok(a->d)) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: bad dimensions (G 1..8, A 1..8, N >= 1, R 64 or 90)");
+    for (int g = 0; g < a->d.G; ++g)
+        if (a->agent[g] < 0 || a->agent[g] >= a->d.A) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: agent index out of range");
+    if ((a->mode != CAT_ACT_SAMPLE && a->mode != CAT_ACT_GREEDY) || (a->random_mask >> a->d.G) != 0 ||
+        (a->row_tile != 0 && a->row_tile != 32 && a->row_tile != 64))
+        return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: bad mode, random_mask or row_tile");
+    if (!a->obs_distance || !a->obs_type || !a->uniform || !a->actions) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: a required buffer is NULL");
+    const bool all_random = a->random_mask == (1u << a->d.G) - 1u;
+    if (!all_random) {
+        const void *ps[] = {a->p.conv1_w, a->p.conv1_b, a->p.conv2_w, a->p.conv2_b, a->p.fc_w, a->p.fc_b, a->p.w_ih, a->p.w_hh, a->p.b_ih, a->p.b_hh,
+                            a->p.head0_w, a->p.head0_b, a->p.head1_w, a->p.head1_b, a->p.head2_w, a->p.head2_b, a->h, a->c};
+        for (const void *p : ps)
+            if (!p || ((uintptr_t)p % 16)) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: a parameter or state pointer is NULL or not 16-byte aligned");
+        if (a->p.stride % 8) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: the parameter stride must be a multiple of 8 elements");
+        if (a->logits_out && ((uintptr_t)a->logits_out % 8)) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: logits_out must be 8-byte aligned");
+    }
+    const int tile = a->row_tile ? a->row_tile : 32;
+    hipStream_t s = (hipStream_t)stream;
+    if (a->d.R == 64) return tile == 32 ? launch<64, 2>(*a, s) : launch<64, 4>(*a, s);
+    return tile == 32 ? launch<90, 2>(*a, s) : launch<90, 4>(*a, s);
+}

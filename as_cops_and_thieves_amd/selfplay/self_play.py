@@ -68,36 +68,30 @@ class TrainingConfig:
 
 
 @torch.no_grad()
-def evaluate_agents(env, runner: MAPPOTrainer, n_episodes: int, random_roles: Tuple[str, ...] = ()) -> Tuple[float, float]:
+def evaluate_agents(env, runner: Optional[MAPPOTrainer], n_episodes: int, random_roles: Tuple[str, ...] = (), actor=None) -> Tuple[float, float]:
     """``src/utils/eval_pfsp_agents.py:7-59``: ``n_episodes`` episodes with every model frozen, actions sampled from
     the policies (skrl ``policy.act``), an episode ends at its first termination and is a win of ``infos["winner"]``.
     Returns (cop wins / n, thief wins / n).  The batched form plays the episodes in parallel, one per env slot
     (``env.num_envs >= n_episodes``; the first episode of the first ``n_episodes`` slots counts).  ``random_roles``:
-    these roles act uniformly at random instead (a fixed yardstick opponent; not part of the reference protocol)."""
+    these roles act uniformly at random instead (a fixed yardstick opponent; not part of the reference protocol).
+    ``actor`` (``actor.PolicyActor``): the policies act through it instead of through ``runner`` (which may then be None)."""
     N = env.num_envs
-    assert N >= n_episodes and N == runner.N
+    who = actor if actor is not None else runner          # sizes, device and agent names: the actor's or the trainer's
+    assert N >= n_episodes and N == who.N
     obs, _ = env.reset()
-    starts = torch.ones(N, dtype=torch.bool, device=runner.device)
-    state = {r: rl.policy.initial_state(N) for r, rl in runner.roles.items()}
-    winner = torch.full((N,), -1, dtype=torch.int8, device=runner.device)
-    open_ = torch.ones(N, dtype=torch.bool, device=runner.device)
+    starts = torch.ones(N, dtype=torch.bool, device=who.device)
+    state = _initial_states(runner, actor, N)
+    winner = torch.full((N,), -1, dtype=torch.int8, device=who.device)
+    open_ = torch.ones(N, dtype=torch.bool, device=who.device)
     open_[n_episodes:] = False
-    actions = torch.zeros(N, len(runner.agents), dtype=torch.int32, device=runner.device)
+    actions = torch.zeros(N, len(who.agents), dtype=torch.int32, device=who.device)
     for _ in range(env.max_step_count + 2):
-        keep = (~starts).view(1, N)
-        for r, rl in runner.roles.items():
-            pin = torch.stack([runner_pack(obs[a]) for a in rl.agents])
-            if runner.tcfg.normalize_inputs:
-                pin = pin * runner._pin_scale
-            logits, state[r] = rl.policy.forward(pin.unsqueeze(1), state[r], keep)
-            act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
-            rnd = [ar in random_roles for ar in rl.agent_roles]
-            if any(rnd):                                # a uniformly random opponent (not part of the reference protocol)
-                rows = torch.tensor(rnd, device=runner.device).view(rl.G, 1)
-                act = torch.where(rows, torch.randint(0, 4, (rl.G, N), device=runner.device), act)
-            actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))
+        if actor is not None:
+            actions = actor.act(env, starts, random_roles=random_roles, obs=obs)
+        else:
+            _trainer_actions(runner, obs, state, starts, actions, random_roles)
         obs, _, terms, _, infos = env.step(actions)
-        done = terms[runner.agents[0]]
+        done = terms[who.agents[0]]
         first = open_ & done
         winner = torch.where(first, infos["winner"].to(torch.int8), winner)
         open_ = open_ & ~done
@@ -108,32 +102,61 @@ def evaluate_agents(env, runner: MAPPOTrainer, n_episodes: int, random_roles: Tu
     return float((w == 0).sum()) / n_episodes, float((w == 1).sum()) / n_episodes
 
 
+def _initial_states(runner, actor, N: int):
+    """The recurrent states an evaluation loop carries for the trainer's policies; with an actor the actor carries its own (zeroed here)."""
+    if actor is not None:
+        actor.reset()
+        return {}
+    return {r: rl.policy.initial_state(N) for r, rl in runner.roles.items()}
+
+
+def _trainer_actions(runner: MAPPOTrainer, obs, state, starts: torch.Tensor, actions: torch.Tensor, random_roles: Tuple[str, ...]) -> None:
+    """One tick's action selection through the trainer's stacked policies, into ``actions`` [N, A]: sampled from the policies (skrl
+    ``policy.act``), ``random_roles`` uniformly at random; ``state`` (role -> recurrent state) is advanced in place."""
+    N = runner.N
+    keep = (~starts).view(1, N)
+    for r, rl in runner.roles.items():
+        pin = torch.stack([runner_pack(obs[a]) for a in rl.agents])
+        if runner.tcfg.normalize_inputs:
+            pin = pin * runner._pin_scale
+        logits, state[r] = rl.policy.forward(pin.unsqueeze(1), state[r], keep)
+        act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
+        rnd = [ar in random_roles for ar in rl.agent_roles]
+        if any(rnd):                                # a uniformly random opponent (not part of the reference protocol)
+            rows = torch.tensor(rnd, device=runner.device).view(rl.G, 1)
+            act = torch.where(rows, torch.randint(0, 4, (rl.G, N), device=runner.device), act)
+        actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))
+
+
 class _Rewind:
     """What a later evaluation on the same env can see of this one, kept per tick for the ticks since the last poll: the global
     generators ``_sample`` / ``torch.randint`` draw from (host-side reads) and a device-side copy of the env's state
     (``get_env_state``: no synchronisation; the copies of a tick ``window`` ticks back are overwritten in place).  ``restore(tick)`` puts
     both back to where they stood after that tick."""
 
-    def __init__(self, env, device, window: int):
-        self.env, self.device, self.window, self.kept = env, device, window, {}
+    def __init__(self, env, device, window: int, actor=None):
+        self.env, self.device, self.window, self.kept, self.actor = env, device, window, {}, actor
 
     def keep(self, tick: int) -> None:
         old = self.kept.get(tick % self.window)
         rng = (torch.get_rng_state(), torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None)
-        self.kept[tick % self.window] = (tick, rng, self.env.get_env_state(out=None if old is None else old[2]))
+        held = None if self.actor is None else self.actor.get_state(out=None if old is None else old[3])   # the actor's h / c after this tick
+        self.kept[tick % self.window] = (tick, rng, self.env.get_env_state(out=None if old is None else old[2]), held)
 
     def restore(self, tick: int) -> None:
-        kept_tick, rng, state = self.kept[tick % self.window]
+        kept_tick, rng, state, held = self.kept[tick % self.window]
         assert kept_tick == tick, (kept_tick, tick)
         self.env.set_env_state(**state)
+        if held is not None:
+            self.actor.set_state(held)
         torch.set_rng_state(rng[0])
         if rng[1] is not None:
             torch.cuda.set_rng_state(rng[1], self.device)
 
 
 @torch.no_grad()
-def evaluate_agents_tracked(env, runner: MAPPOTrainer, n_episodes: int, random_roles: Tuple[str, ...] = (),
-                            poll_every: int = 32) -> Tuple[float, float]:
+def evaluate_agents_tracked(env, runner: Optional[MAPPOTrainer], n_episodes: int, random_roles: Tuple[str, ...] = (),
+                            poll_every: int = 32, actor=None) -> Tuple[float, float]:
     """``evaluate_agents`` with the book-keeping done on the device by the env's ``episode_tracker`` (``episodes.EpisodeTracker``,
     which the env feeds on every ``step``): the same tick loop, but the host looks at the number of slots still owing an episode only
     every ``poll_every`` ticks instead of every tick, and a slot plays several episodes in a row, so any ``n_episodes`` is allowed.
@@ -144,9 +167,11 @@ def evaluate_agents_tracked(env, runner: MAPPOTrainer, n_episodes: int, random_r
     ``evaluate_agents`` stops, so a later evaluation on the same env starts from the same state either way.  Beyond the surface
     ``evaluate_agents`` uses, the env must offer ``episode_tracker`` and ``get_env_state(out=None)`` / ``set_env_state(**state)``.
     Cost of ``poll_every``: the window holds that many full copies of the env state on the device (a few hundred bytes per slot
-    each), and every tick makes one state-copy launch and two host reads of generator state (a new 5 KB CPU snapshot each)."""
+    each), and every tick makes one state-copy launch and two host reads of generator state (a new 5 KB CPU snapshot each).
+    ``actor``: as in ``evaluate_agents``; its recurrent state is kept and put back with the env's."""
     N = env.num_envs
-    assert N == runner.N and n_episodes >= 1 and poll_every >= 1
+    who = actor if actor is not None else runner          # sizes, device and agent names: the actor's or the trainer's
+    assert N == who.N and n_episodes >= 1 and poll_every >= 1
     tracker = env.episode_tracker
     obs, _ = env.reset()
     quota = torch.full((N,), n_episodes // N, dtype=torch.int32)
@@ -154,27 +179,19 @@ def evaluate_agents_tracked(env, runner: MAPPOTrainer, n_episodes: int, random_r
     tracker.set_quota(quota)
     tracker.abandon()
     tracker.clear()
-    starts = torch.ones(N, dtype=torch.bool, device=runner.device)
-    state = {r: rl.policy.initial_state(N) for r, rl in runner.roles.items()}
-    actions = torch.zeros(N, len(runner.agents), dtype=torch.int32, device=runner.device)
+    starts = torch.ones(N, dtype=torch.bool, device=who.device)
+    state = _initial_states(runner, actor, N)
+    actions = torch.zeros(N, len(who.agents), dtype=torch.int32, device=who.device)
     limit = int(quota.max()) * env.max_step_count + 2
-    rewind = _Rewind(env, runner.device, poll_every)
+    rewind = _Rewind(env, who.device, poll_every, actor)
     stats, tick = None, 0
     while tick < limit:
-        keep = (~starts).view(1, N)
-        for r, rl in runner.roles.items():
-            pin = torch.stack([runner_pack(obs[a]) for a in rl.agents])
-            if runner.tcfg.normalize_inputs:
-                pin = pin * runner._pin_scale
-            logits, state[r] = rl.policy.forward(pin.unsqueeze(1), state[r], keep)
-            act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
-            rnd = [ar in random_roles for ar in rl.agent_roles]
-            if any(rnd):                                # a uniformly random opponent (not part of the reference protocol)
-                rows = torch.tensor(rnd, device=runner.device).view(rl.G, 1)
-                act = torch.where(rows, torch.randint(0, 4, (rl.G, N), device=runner.device), act)
-            actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))
+        if actor is not None:
+            actions = actor.act(env, starts, random_roles=random_roles, obs=obs)
+        else:
+            _trainer_actions(runner, obs, state, starts, actions, random_roles)
         obs, _, terms, _, _ = env.step(actions)
-        starts = terms[runner.agents[0]].clone()
+        starts = terms[who.agents[0]].clone()
         tick += 1
         rewind.keep(tick)
         if tick % poll_every == 0 or tick == limit:
@@ -189,33 +206,27 @@ def evaluate_agents_tracked(env, runner: MAPPOTrainer, n_episodes: int, random_r
 
 
 @torch.no_grad()
-def mean_reward_per_tick(env, runner: MAPPOTrainer, ticks: int, random_roles: Tuple[str, ...] = ()) -> Dict[str, float]:
+def mean_reward_per_tick(env, runner: Optional[MAPPOTrainer], ticks: int, random_roles: Tuple[str, ...] = (), actor=None) -> Dict[str, float]:
     """Diagnostic (not part of the reference protocol): reset ``env``, act for ``ticks`` ticks with sampled actions
     (``random_roles`` uniformly at random) and return every agent's mean reward per tick -- the quantity PPO maximises,
-    measured from the same starting conditions whenever it is called."""
+    measured from the same starting conditions whenever it is called.  ``actor``: as in ``evaluate_agents``."""
     N = env.num_envs
-    assert N == runner.N
+    who = actor if actor is not None else runner          # sizes, device and agent names: the actor's or the trainer's
+    assert N == who.N
     obs, _ = env.reset()
-    starts = torch.ones(N, dtype=torch.bool, device=runner.device)
-    state = {r: rl.policy.initial_state(N) for r, rl in runner.roles.items()}
-    actions = torch.zeros(N, len(runner.agents), dtype=torch.int32, device=runner.device)
-    total = {a: torch.zeros((), device=runner.device) for a in runner.agents}
+    starts = torch.ones(N, dtype=torch.bool, device=who.device)
+    state = _initial_states(runner, actor, N)
+    actions = torch.zeros(N, len(who.agents), dtype=torch.int32, device=who.device)
+    total = {a: torch.zeros((), device=who.device) for a in who.agents}
     for _ in range(ticks):
-        keep = (~starts).view(1, N)
-        for r, rl in runner.roles.items():
-            pin = torch.stack([runner_pack(obs[a]) for a in rl.agents])
-            if runner.tcfg.normalize_inputs:
-                pin = pin * runner._pin_scale
-            logits, state[r] = rl.policy.forward(pin.unsqueeze(1), state[r], keep)
-            act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
-            rnd = [ar in random_roles for ar in rl.agent_roles]
-            if any(rnd):
-                act = torch.where(torch.tensor(rnd, device=runner.device).view(rl.G, 1), torch.randint(0, 4, (rl.G, N), device=runner.device), act)
-            actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))
+        if actor is not None:
+            actions = actor.act(env, starts, random_roles=random_roles, obs=obs)
+        else:
+            _trainer_actions(runner, obs, state, starts, actions, random_roles)
         obs, rewards, terms, _, _ = env.step(actions)
-        for a in runner.agents:
+        for a in who.agents:
             total[a] += rewards[a].float().mean()
-        starts = terms[runner.agents[0]].clone()
+        starts = terms[who.agents[0]].clone()
     return {a: float(v) / ticks for a, v in total.items()}
 
 
@@ -225,12 +236,17 @@ def runner_pack(obs_agent):
 
 
 def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, learned_role: str, opponent_role: str,
-                   opponent_archive: Path, tc: TrainingConfig, rng: random.Random, log=print, tracked: bool = False) -> Dict[str, bool]:
+                   opponent_archive: Path, tc: TrainingConfig, rng: random.Random, log=print, tracked: bool = False,
+                   fused_eval: bool = False) -> Dict[str, bool]:
     """``agent_learning_utils.py:233-380``: the newly trained ``learned_role`` against up to
     ``tc.num_opponents_to_evaluate`` distinct archived ``opponent_role`` policies.  Returns {opponent file: opponent won}.
-    ``tracked``: play the episodes through ``evaluate_agents_tracked`` (``eval_env`` must feed an ``episode_tracker``)."""
+    ``tracked``: play the episodes through ``evaluate_agents_tracked`` (``eval_env`` must feed an ``episode_tracker``).
+    ``fused_eval``: ``evaluator`` is a ``PolicyActor`` (``from_checkpoint(None, eval_env, ...)``) and the episodes are played through it."""
     results: Dict[str, bool] = {}
-    evaluator.load_state_dict(learned.state_dict(), roles=[learned_role], optimizer=False)
+    if fused_eval:
+        evaluator.load({a: learned.agent_models(a) for a in learned.agents}, roles=[learned_role])
+    else:
+        evaluator.load_state_dict(learned.state_dict(), roles=[learned_role], optimizer=False)
     seen = set()
     for i in range(tc.num_opponents_to_evaluate):
         path = None
@@ -249,9 +265,14 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
             break
         name = Path(path).name
         seen.add(name)
-        evaluator.load_state_dict(torch.load(path, map_location=evaluator.device, weights_only=True), roles=[opponent_role],
-                                  optimizer=False)                       # copy_role_models: policy + value weights
-        cop_rate, thief_rate = (evaluate_agents_tracked if tracked else evaluate_agents)(eval_env, evaluator, tc.n_trial_episodes)
+        if fused_eval:
+            evaluator.load(path, roles=[opponent_role])                  # the policy blocks only
+        else:
+            evaluator.load_state_dict(torch.load(path, map_location=evaluator.device, weights_only=True), roles=[opponent_role],
+                                      optimizer=False)                   # copy_role_models: policy + value weights
+        play = evaluate_agents_tracked if tracked else evaluate_agents
+        cop_rate, thief_rate = (play(eval_env, None, tc.n_trial_episodes, actor=evaluator) if fused_eval
+                                else play(eval_env, evaluator, tc.n_trial_episodes))
         opponent_won = (thief_rate > cop_rate) if learned_role == tc.cop_role_prefix else (cop_rate > thief_rate)
         archive.update_policy_win_rate(opponent_archive, name, opponent_won, tc.win_rate_buffer_size)
         results[name] = opponent_won
@@ -264,12 +285,15 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   role_cfg: Optional[Dict[str, RoleConfig]] = None, num_rays: int = 64, n_cops: Optional[int] = None,
                   n_thieves: Optional[int] = None, max_step_count: int = 2000, eval_envs: Optional[int] = None,
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
-                  query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False) -> Dict[str, object]:
+                  query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False,
+                  fused_eval: bool = False) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
     ``env_factory(num_envs, seed[, env_id_offset])``: build the envs some other way (the CPU tests pass a stand-in env with the
     same surface).
+    ``fused_eval``: the evaluator is a ``PolicyActor`` instead of a second ``MAPPOTrainer``: policy blocks and recurrent state only, and on a
+    GPU the act tick of all policies is one launch (``include/cat_act.h``).
     ``tracked_eval``: the evaluation env is built with ``track_episodes=True`` and evaluation goes through
     ``evaluate_agents_tracked``.  ``episode_stats``: the training env is built with ``track_episodes=True``, the trainer reports the
     training episodes (``TrainerConfig.episode_stats``), every iteration's log line carries their win rate and mean length, and rank
@@ -335,8 +359,13 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
             raise TypeError(f"{what}=True needs envs with an {attr!r} (VecCopsEnv(track_episodes=True)); the env_factory's have none")
     role_cfg = role_cfg or {"cop": CFG_AGENT, "thief": CFG_AGENT}        # self_play_driver.py passes CFG_AGENT
     trainer = MAPPOTrainer(env, role_cfg, trainer_cfg, seed=seed)
-    evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False),
-                             seed=seed + 1)
+    if fused_eval:   # policy blocks and recurrent state only; on a GPU the act tick is one launch (include/cat_act.h)
+        from .actor import PolicyActor
+        evaluator = PolicyActor.from_checkpoint(None, eval_env, fused="kernel", compute_bf16=trainer_cfg.compute_bf16, normalize_inputs=trainer_cfg.normalize_inputs,
+                                                recurrent=trainer_cfg.recurrent, seed=seed + 1, device=trainer.device)
+    else:
+        evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False),
+                                 seed=seed + 1)
     rng = random.Random(seed)
     start = 0
     if resume:
@@ -363,8 +392,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         if chief:
             try:
                 # ---- 3. evaluation against archived opponents (:199-228)
-                ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval),
-                      thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval)}
+                ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval),
+                      thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval)}
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -466,6 +495,8 @@ def main() -> None:
                     help="visiting order of the walls in segment queries: index order (default) or Chipmunk's static tree (DESIGN.md D2)")
     ap.add_argument("--tracked-eval", action="store_true", help="evaluate through evaluate_agents_tracked: episode book-keeping on the device, "
                     "the host polls every 32 ticks instead of every tick")
+    ap.add_argument("--fused-eval", action="store_true", help="evaluate through a PolicyActor (policy blocks only; on a GPU one launch per act tick) "
+                    "instead of a second trainer")
     ap.add_argument("--episode-stats", action="store_true", help="account the training episodes on the device: win rate and mean length in "
                     "every iteration's log line, episode_stats.json in --out (with --gpus N: of rank 0's shard)")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
@@ -490,7 +521,7 @@ def main() -> None:
     res = run_self_play(args.map, args.envs, args.out, iterations=args.iterations, training=tc, trainer_cfg=tcfg, role_cfg=role_cfg,
                         num_rays=args.rays, n_cops=args.cops, n_thieves=args.thieves, max_step_count=args.max_step_count,
                         eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
-                        query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats)
+                        query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval)
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

@@ -23,8 +23,8 @@ import torch
 from ..environments import WINNER_NAMES, VecCopsEnv
 from ..maps import load_preset
 from ..render import write_png
-from .mappo import CFG_AGENT, MAPPOTrainer, TrainerConfig, _sample
-from .self_play import runner_pack
+from .mappo import CFG_AGENT, MAPPOTrainer, TrainerConfig
+from .self_play import _initial_states, _trainer_actions
 
 
 def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None,
@@ -37,13 +37,22 @@ def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_st
 @torch.no_grad()
 def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, ticks: int = 2000, rays: bool = False, seed: int = 0,
           num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None, n_thieves: Optional[int] = None, device=None,
-          log=print) -> Dict[str, object]:
+          log=print, fused_act: bool = False, greedy: bool = False) -> Dict[str, object]:
+    """``fused_act``: no trainer is built -- a ``PolicyActor`` reads the checkpoint's policy blocks and acts (on a GPU: one launch per tick,
+    ``include/cat_act.h``).  ``greedy`` (with ``fused_act``): the most probable action instead of a draw."""
     out_dir = Path(out_dir)
     torch.manual_seed(seed)
     env = make_env(map_name, envs, seed, num_rays, max_step_count, n_cops, n_thieves, device)
-    runner = MAPPOTrainer(env, {"cop": CFG_AGENT, "thief": CFG_AGENT}, TrainerConfig(graph_rollout=False, graph_update=False), seed=seed)
-    if checkpoint:
-        runner.load_state_dict(torch.load(checkpoint, map_location=runner.device, weights_only=True), optimizer=False)
+    if greedy and not fused_act:
+        raise ValueError("greedy=True needs fused_act=True (the default path samples, as self_play.evaluate_agents)")
+    actor = None
+    if fused_act:
+        from .actor import PolicyActor
+        actor, runner = PolicyActor.from_checkpoint(checkpoint, env, fused="kernel", seed=seed), None
+    else:
+        runner = MAPPOTrainer(env, {"cop": CFG_AGENT, "thief": CFG_AGENT}, TrainerConfig(graph_rollout=False, graph_update=False), seed=seed)
+        if checkpoint:
+            runner.load_state_dict(torch.load(checkpoint, map_location=runner.device, weights_only=True), optimizer=False)
     N = env.num_envs
     W, H = (int(v) for v in env.maps[0].window_dimensions)
     slots = list(range(N))
@@ -58,25 +67,22 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
                 write_png(dirs[k] / f"frame_{t:05d}.png", frames[k, :W, :H])
 
     obs, _ = env.reset()
-    starts = torch.ones(N, dtype=torch.bool, device=runner.device)
-    state = {r: rl.policy.initial_state(N) for r, rl in runner.roles.items()}
-    actions = torch.zeros(N, len(runner.agents), dtype=torch.int32, device=runner.device)
+    who = actor if actor is not None else runner
+    starts = torch.ones(N, dtype=torch.bool, device=who.device)
+    state = _initial_states(runner, actor, N)
+    actions = torch.zeros(N, len(who.agents), dtype=torch.int32, device=who.device)
     open_host = [True] * N
     winner, length, ended = [None] * N, [ticks] * N, [False] * N
     save(0, open_host)
     for t in range(1, ticks + 1):
-        keep = (~starts).view(1, N)
-        for r, rl in runner.roles.items():                           # self_play.evaluate_agents' action selection
-            pin = torch.stack([runner_pack(obs[a]) for a in rl.agents])
-            if runner.tcfg.normalize_inputs:
-                pin = pin * runner._pin_scale
-            logits, state[r] = rl.policy.forward(pin.unsqueeze(1), state[r], keep)
-            act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
-            actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))
+        if actor is not None:
+            actions = actor.act(env, starts, greedy=greedy, obs=obs)
+        else:
+            _trainer_actions(runner, obs, state, starts, actions, ())     # self_play.evaluate_agents' action selection
         obs, _, terms, _, infos = env.step(actions)
         starts = torch.zeros_like(starts)
         save(t, open_host)
-        done = terms[runner.agents[0]].cpu().tolist()
+        done = terms[who.agents[0]].cpu().tolist()
         win = infos["winner"].cpu().tolist()
         for k in slots:
             if open_host[k] and done[k]:
@@ -85,6 +91,7 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
             break
     env.check_errors()
     result = {"map": map_name, "envs": N, "ticks": ticks, "checkpoint": checkpoint, "seed": seed, "rays": bool(rays),
+              **({"fused_act": True, "greedy": bool(greedy)} if fused_act else {}),
               "slots": [{"env": k, "winner": winner[k], "length": length[k], "terminated": ended[k],
                          "frames": (length[k] + 1) if ended[k] else (t + 1)} for k in slots]}
     (out_dir / "episode.json").write_text(json.dumps(result, indent=1))
@@ -105,10 +112,16 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--num-rays", type=int, default=64)
     ap.add_argument("--max-steps", type=int, default=2000, help="episode length limit of the env (the self-play driver's 2000)")
+    ap.add_argument("--fused-act", action="store_true", help="act through a PolicyActor built straight from the checkpoint (no trainer; on a "
+                    "GPU one launch per tick)")
+    ap.add_argument("--greedy", action="store_true", help="with --fused-act: the most probable action instead of a draw")
     args = ap.parse_args(argv)
     if args.envs < 1 or args.ticks < 1:
         ap.error("--envs and --ticks must be >= 1")
-    watch(args.map, args.envs, args.out, args.checkpoint, args.ticks, args.rays, args.seed, args.num_rays, args.max_steps)
+    if args.greedy and not args.fused_act:
+        ap.error("--greedy needs --fused-act")
+    watch(args.map, args.envs, args.out, args.checkpoint, args.ticks, args.rays, args.seed, args.num_rays, args.max_steps,
+          fused_act=args.fused_act, greedy=args.greedy)
     return 0
 
 
