@@ -74,8 +74,9 @@ DENSE_SYMBOLS = ("cat_dense_abi_version", "cat_dense_last_error", "cat_dense_bia
 PPO_SYMBOLS = ("cat_ppo_abi_version", "cat_ppo_last_error", "cat_ppo_loss_grad", "cat_ppo_adam_step", "cat_ppo_gae_scan")
 RENDER_SYMBOLS = ("cat_render_abi_version", "cat_render_last_error", "cat_render_frames")
 EPISODES_SYMBOLS = ("cat_episodes_abi_version", "cat_episodes_last_error", "cat_episodes_update", "cat_episodes_summary")
-ACT_SYMBOLS = ("cat_act_abi_version", "cat_act_last_error", "cat_act_supported", "cat_act_step")
+ACT_SYMBOLS = ("cat_act_abi_version", "cat_act_last_error", "cat_act_supported", "cat_act_step", "cat_act_league_step")
 ACT_MAX_AGENTS = 8              # CAT_ACT_MAX_AGENTS
+ACT_MAX_SEGMENTS = 32           # CAT_ACT_MAX_SEGMENTS
 ACT_SAMPLE, ACT_GREEDY = 0, 1   # cat_act_args.mode
 EPISODES_MAX_AGENTS = 8         # CAT_ROLLOUT_MAX_AGENTS
 EPISODES_HIST_BINS = 64
@@ -224,6 +225,8 @@ def lib() -> C.CDLL:
         L.cat_act_supported.argtypes = [C.c_void_p]
         L.cat_act_step.restype = C.c_int
         L.cat_act_step.argtypes = [C.c_void_p, C.c_void_p]
+        L.cat_act_league_step.restype = C.c_int
+        L.cat_act_league_step.argtypes = [C.c_void_p, C.c_void_p]
         assert L.cat_act_abi_version() == 1
         _lib = L
     return _lib
@@ -780,6 +783,12 @@ class ActArgs(C.Structure):
                 ("keep", C.c_void_p), ("uniform", C.c_void_p), ("actions", C.c_void_p), ("logits_out", C.c_void_p), ("logp_out", C.c_void_p)]
 
 
+class ActLeagueArgs(C.Structure):
+    """include/cat_act.h cat_act_league_args."""
+    _fields_ = [("base", ActArgs), ("S", C.c_int32), ("sets", C.c_int32), ("seg_start", C.c_int32 * (ACT_MAX_SEGMENTS + 1)),
+                ("seg_set", (C.c_int32 * ACT_MAX_SEGMENTS) * ACT_MAX_AGENTS)]
+
+
 def act_supported(G: int, N: int, A: int, R: int) -> bool:
     d = ActDims(G, N, A, R)
     return bool(lib().cat_act_supported(C.byref(d)))
@@ -802,6 +811,13 @@ def act_step(raw, agent_indices, params, h, c, keep, uniform, actions, distance_
     (``VecCopsEnv.raw_outputs()``: obs_distance f16 / obs_type u8 [N, A, R]); params = ``act_params(...)`` (or the mapping it takes); h, c bf16
     [G, N, 128] updated in place; keep fp32 [N] or None; uniform fp32 [G, N]; actions int32 [N, A]: column ``agent_indices[g]`` receives
     policy g's action; logits_out bf16 [G, N, 4] / logp_out fp32 [G, N] optional."""
+    _check(lib().cat_act_step(C.byref(_act_args(raw, agent_indices, params, h, c, keep, uniform, actions, distance_scale, type_scale, greedy, random_mask,
+                                                logits_out, logp_out, row_tile)), _stream()), "cat_act_step")
+
+
+def _act_args(raw, agent_indices, params, h, c, keep, uniform, actions, distance_scale, type_scale, greedy, random_mask, logits_out, logp_out,
+              row_tile) -> ActArgs:
+    """The checked ``cat_act_args`` of ``act_step`` / ``act_league_step``."""
     import torch
     od, ot = raw["obs_distance"], raw["obs_type"]
     N, A, R = od.shape
@@ -816,7 +832,52 @@ def act_step(raw, agent_indices, params, h, c, keep, uniform, actions, distance_
     assert logits_out is None or (logits_out.dtype == torch.bfloat16 and logits_out.shape == (G, N, 4) and logits_out.is_contiguous())
     assert logp_out is None or (logp_out.dtype == torch.float32 and logp_out.shape == (G, N) and logp_out.is_contiguous())
     p = params if isinstance(params, ActParams) else act_params(params)
-    a = ActArgs(ActDims(G, N, A, R), (C.c_int32 * ACT_MAX_AGENTS)(*agent_indices), ACT_GREEDY if greedy else ACT_SAMPLE, int(random_mask), int(row_tile),
-                distance_scale, type_scale, 0, od.data_ptr(), ot.data_ptr(), p, h.data_ptr(), c.data_ptr(), _ptr(keep), uniform.data_ptr(),
-                actions.data_ptr(), _ptr(logits_out), _ptr(logp_out))
-    _check(lib().cat_act_step(C.byref(a), _stream()), "cat_act_step")
+    return ActArgs(ActDims(G, N, A, R), (C.c_int32 * ACT_MAX_AGENTS)(*agent_indices), ACT_GREEDY if greedy else ACT_SAMPLE, int(random_mask), int(row_tile),
+                   distance_scale, type_scale, 0, od.data_ptr(), ot.data_ptr(), p, h.data_ptr(), c.data_ptr(), _ptr(keep), uniform.data_ptr(),
+                   actions.data_ptr(), _ptr(logits_out), _ptr(logp_out))
+
+
+class LeagueTable:
+    """A checked segment table in the C struct's own arrays (``league_table`` makes it; ``act_league_step`` copies it in whole)."""
+
+    def __init__(self, S: int, sets: int, start, table):
+        self.S, self.sets, self.start, self.table = S, sets, start, table
+        self.seg_start = (C.c_int32 * (ACT_MAX_SEGMENTS + 1))(*start)
+        self.seg_set = ((C.c_int32 * ACT_MAX_SEGMENTS) * ACT_MAX_AGENTS)(*[(C.c_int32 * ACT_MAX_SEGMENTS)(*row) for row in table])
+
+
+def league_table(N: int, G: int, sets: int, seg_start, seg_set) -> LeagueTable:
+    """The segment table of ``cat_act_league_args`` checked by the C entry's rules: ``seg_start`` S + 1 row bounds (0 first, N last, strictly
+    increasing, 1 <= S <= ACT_MAX_SEGMENTS), ``seg_set`` [G][S] set indices in [-1, sets) (-1: uniformly random).  Raises ValueError."""
+    start = [int(v) for v in seg_start]
+    S = len(start) - 1
+    if not 1 <= S <= ACT_MAX_SEGMENTS:
+        raise ValueError(f"{S} segments: 1..{ACT_MAX_SEGMENTS} are allowed")
+    if sets < 1:
+        raise ValueError("the bank needs at least one parameter set")
+    if start[0] != 0 or start[-1] != N:
+        raise ValueError(f"the segments must begin at row 0 and end at row {N}: {start}")
+    if any(b <= a for a, b in zip(start, start[1:])):
+        raise ValueError(f"the segment bounds must be strictly increasing: {start}")
+    table = [[int(v) for v in row] for row in seg_set]
+    if len(table) != G or any(len(row) != S for row in table):
+        raise ValueError(f"seg_set must be [{G}][{S}]")
+    if any(not -1 <= v < sets for row in table for v in row):
+        raise ValueError(f"a set index outside [-1, {sets})")
+    return LeagueTable(S, int(sets), start, table)
+
+
+def act_league_step(raw, agent_indices, bank_params, sets: int, seg_start, seg_set, h, c, keep, uniform, actions, distance_scale: float = 1.0,
+                    type_scale: float = 1.0, greedy: bool = False, logits_out=None, logp_out=None, row_tile: int = 0) -> None:
+    """``act_step`` with per-segment parameter sets in one launch (include/cat_act.h, ``cat_act_league_step``).  bank_params =
+    ``act_params(...)`` over the bank's ``[sets, ...]`` views: set k of every block at pointer + k * stride.  Rows ``seg_start[s] ..
+    seg_start[s + 1] - 1`` of policy g are played by set ``seg_set[g][s]``, or uniformly at random where that is -1 (state and optional
+    outputs of those rows untouched).  ``seg_start`` may be a ``LeagueTable`` made for these N, G and sets (``seg_set`` is then ignored).
+    Everything else as in ``act_step``; there is no ``random_mask``."""
+    G, N = uniform.shape
+    t = seg_start if isinstance(seg_start, LeagueTable) else league_table(N, len(agent_indices), sets, seg_start, seg_set)
+    assert G == len(agent_indices) and t.start[-1] == N and len(t.table) == G and t.sets == sets
+    a = ActLeagueArgs()
+    a.base = _act_args(raw, agent_indices, bank_params, h, c, keep, uniform, actions, distance_scale, type_scale, greedy, 0, logits_out, logp_out, row_tile)
+    a.S, a.sets, a.seg_start, a.seg_set = t.S, t.sets, t.seg_start, t.seg_set
+    _check(lib().cat_act_league_step(C.byref(a), _stream()), "cat_act_league_step")

@@ -83,8 +83,11 @@ __device__ __forceinline__ void layer(const __bf16 *W, const __bf16 *bias, int n
     }
 }
 
+// The chain for the rows row0 .. rend - 1 (at most TM of them) of policy g: the parameters at element offset po of every block, or no
+// network at all where ``random``.  Rows at and beyond rend are neither read nor written (their LDS images are zero): in the league
+// form they belong to another segment, whose workgroup updates them in place.
 template <int R, int MT>
-__global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
+__device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, const int row0, const int rend, const size_t po, const bool random)
 {
     using G = Geo<R>;
     constexpr int TM = 16 * MT;
@@ -93,14 +96,14 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
     __bf16 *xin = regA, *c1 = regA + TM * G::XIN_LD, *fh = regA, *h1 = regA;       // region A over time
     __bf16 *x2 = regB, *hn = regB, *h2 = regB + TM * G::HN_LD;                      // region B over time
 
-    const int g = blockIdx.y, row0 = blockIdx.x * TM, N = a.d.N, A = a.d.A, ai = a.agent[g];
+    const int N = a.d.N, A = a.d.A, ai = a.agent[g];
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, q = l >> 4, r = l & 15;
     const float *uni = a.uniform + (size_t)g * N;
 
-    if ((a.random_mask >> g) & 1u) {                 // a uniformly random agent: no network, no state
+    if (random) {                                    // a uniformly random agent: no network, no state
         for (int m = tid; m < TM; m += BLOCK) {
             const int n = row0 + m;
-            if (n < N) {
+            if (n < rend) {
                 const int act = (int)(4.0f * uni[n]);
                 a.actions[(size_t)n * A + ai] = act < 3 ? act : 3;
             }
@@ -108,7 +111,6 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
         return;
     }
 
-    const size_t po = (size_t)g * a.p.stride;
     const __bf16 *w1 = (const __bf16 *)a.p.conv1_w + po, *b1 = (const __bf16 *)a.p.conv1_b + po;
     const __bf16 *w2 = (const __bf16 *)a.p.conv2_w + po, *b2 = (const __bf16 *)a.p.conv2_b + po;
     const __bf16 *wfc = (const __bf16 *)a.p.fc_w + po, *bfc = (const __bf16 *)a.p.fc_b + po;
@@ -118,14 +120,14 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
     const __bf16 *hw1 = (const __bf16 *)a.p.head1_w + po, *hb1 = (const __bf16 *)a.p.head1_b + po;
     const __bf16 *hw2 = (const __bf16 *)a.p.head2_w + po, *hb2 = (const __bf16 *)a.p.head2_b + po;
 
-    // ---- the observation rows: [distance (R) | type (R)], scaled, bf16 (cat_rollout_pack's policy row); rows >= N are zero
+    // ---- the observation rows: [distance (R) | type (R)], scaled, bf16 (cat_rollout_pack's policy row); rows >= rend are zero
     {
         const __half *od = (const __half *)a.obs_distance;
         const uint8_t *ot = (const uint8_t *)a.obs_type;
         for (int i = tid; i < TM * R; i += BLOCK) {
             const int m = i / R, rr = i - m * R, n = row0 + m;
             float dv = 0.0f, tv = 0.0f;
-            if (n < N) {
+            if (n < rend) {
                 const size_t o = ((size_t)n * A + ai) * R + rr;
                 dv = __half2float(od[o]) * a.distance_scale;
                 tv = (float)ot[o] * a.type_scale;
@@ -198,7 +200,7 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
     for (int i = tid; i < TM * (HID / 8); i += BLOCK) {
         const int m = i / (HID / 8), ch = i % (HID / 8), n = row0 + m;
         bf16x8 v = {};
-        if (n < N && (!a.keep || a.keep[n] != 0.0f)) v = *(const bf16x8 *)(hg + (size_t)n * HID + 8 * ch);
+        if (n < rend && (!a.keep || a.keep[n] != 0.0f)) v = *(const bf16x8 *)(hg + (size_t)n * HID + 8 * ch);
         *(bf16x8 *)(fh + m * G::FH_LD + 256 + 8 * ch) = v;
     }
     layer<G::KFC, MT, A_TANH>(wfc, bfc, 256, x2, G::X2_LD, fh, G::FH_LD, w, q, r);
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
         for (int mt = 0; mt < MT; ++mt) {
             const int m = mt * 16 + r, n = row0 + m;
             f32x4 cp = {0.f, 0.f, 0.f, 0.f};
-            if (n < N && (!a.keep || a.keep[n] != 0.0f)) cp = ld4(cg + (size_t)n * HID + u0);
+            if (n < rend && (!a.keep || a.keep[n] != 0.0f)) cp = ld4(cg + (size_t)n * HID + u0);
             f32x4 cn, hv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -254,7 +256,7 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
             }
             const bf16x4 hb = __builtin_convertvector(hv, bf16x4);
             *(bf16x4 *)(hn + m * G::HN_LD + u0) = hb;
-            if (n < N) {
+            if (n < rend) {
                 *(bf16x4 *)((__bf16 *)a.h + ((size_t)g * N + n) * HID + u0) = hb;
                 *(bf16x4 *)((__bf16 *)a.c + ((size_t)g * N + n) * HID + u0) = __builtin_convertvector(cn, bf16x4);
             }
@@ -277,7 +279,7 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc, 0, 0, 0);
         }
         const int n = row0 + mt * 16 + r;
-        if (q != 0 || n >= N) continue;               // lanes 0 .. 15 hold the four logits of row r
+        if (q != 0 || n >= rend) continue;               // lanes 0 .. 15 hold the four logits of row r
         const f32x4 bz = ld4(hb2);
         f32x4 zf;
 #pragma unroll
@@ -308,10 +310,35 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
     }
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char *msg)
+template <int R, int MT>
+__global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
 {
-    snprintf(g_err, sizeof g_err, "%s", msg);
+    const int g = blockIdx.y;
+    act_rows<R, MT>(a, g, blockIdx.x * (16 * MT), a.d.N, (size_t)g * a.p.stride, (a.random_mask >> g) & 1u);
+}
+
+// The league form: workgroup blockIdx.x is tile t of segment s, found by a uniform scan of the (at most 32) segment lengths -- the
+// host's grid.x is the sum of ceil(len_s / TM) -- and plays parameter set seg_set[g][s] of the bank on the rows of that segment only.
+template <int R, int MT>
+__global__ __launch_bounds__(BLOCK) void act_league_kernel(const cat_act_league_args a)
+{
+    constexpr int TM = 16 * MT;
+    const int g = blockIdx.y;
+    int t = blockIdx.x, s = 0;
+    for (; s < a.S - 1; ++s) {
+        const int tiles = (a.seg_start[s + 1] - a.seg_start[s] + TM - 1) / TM;
+        if (t < tiles) break;
+        t -= tiles;
+    }
+    const int row0 = a.seg_start[s] + t * TM, send = a.seg_start[s + 1], set = a.seg_set[g][s];
+    if (row0 >= send) return;                        // a grid larger than the table's tiles: nothing to do
+    act_rows<R, MT>(a.base, g, row0, row0 + TM < send ? row0 + TM : send, (size_t)(set < 0 ? 0 : set) * a.base.p.stride, set < 0);
+}
+
+thread_local char g_err[256] = "";
+int fail(int code, const char *who, const char *msg)
+{
+    snprintf(g_err, sizeof g_err, "%s: %s", who, msg);
     return code;
 }
 
@@ -320,16 +347,37 @@ bool dims_ok(const cat_act_dims &d)
     return d.G >= 1 && d.G <= CAT_ACT_MAX_AGENTS && d.N >= 1 && d.A >= 1 && d.A <= CAT_ACT_MAX_AGENTS && (d.R == 64 || d.R == 90);
 }
 
-template <int R, int MT> int launch(const cat_act_args &a, hipStream_t stream)
+// The checks both entries share, before any device call.  ``need_params``: some policy evaluates a network.
+int check_args(const cat_act_args *a, const char *who, bool need_params)
 {
-    constexpr int TM = 16 * MT;
-    const size_t lds = Geo<R>::lds_bytes(TM);
+    if (!a || !dims_ok(a->d)) return fail(CAT_ACT_ERR_BAD_ARG, who, "bad dimensions (G 1..8, A 1..8, N >= 1, R 64 or 90)");
+    for (int g = 0; g < a->d.G; ++g)
+        if (a->agent[g] < 0 || a->agent[g] >= a->d.A) return fail(CAT_ACT_ERR_BAD_ARG, who, "agent index out of range");
+    if ((a->mode != CAT_ACT_SAMPLE && a->mode != CAT_ACT_GREEDY) || (a->random_mask >> a->d.G) != 0 ||
+        (a->row_tile != 0 && a->row_tile != 32 && a->row_tile != 64))
+        return fail(CAT_ACT_ERR_BAD_ARG, who, "bad mode, random_mask or row_tile");
+    if (!a->obs_distance || !a->obs_type || !a->uniform || !a->actions) return fail(CAT_ACT_ERR_BAD_ARG, who, "a required buffer is NULL");
+    if (need_params) {
+        const void *ps[] = {a->p.conv1_w, a->p.conv1_b, a->p.conv2_w, a->p.conv2_b, a->p.fc_w, a->p.fc_b, a->p.w_ih, a->p.w_hh, a->p.b_ih, a->p.b_hh,
+                            a->p.head0_w, a->p.head0_b, a->p.head1_w, a->p.head1_b, a->p.head2_w, a->p.head2_b, a->h, a->c};
+        for (const void *p : ps)
+            if (!p || ((uintptr_t)p % 16)) return fail(CAT_ACT_ERR_BAD_ARG, who, "a parameter or state pointer is NULL or not 16-byte aligned");
+        if (a->p.stride % 8) return fail(CAT_ACT_ERR_BAD_ARG, who, "the parameter stride must be a multiple of 8 elements");
+        if (a->logits_out && ((uintptr_t)a->logits_out % 8)) return fail(CAT_ACT_ERR_BAD_ARG, who, "logits_out must be 8-byte aligned");
+    }
+    return CAT_ACT_OK;
+}
+
+// ``tiles``: grid.x -- the row tiles of the N rows, or of all segments of the league form
+template <int R, int MT, typename Args> int launch(void (*kernel)(const Args), const Args &a, int tiles, int G, const char *who, hipStream_t stream)
+{
+    const size_t lds = Geo<R>::lds_bytes(16 * MT);
     // the 64-row tiles take more than the default 64 KB of dynamic LDS: raised on every launch (per device, not a stream operation)
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(act_kernel<R, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return fail(CAT_ACT_ERR_HIP, "cat_act_step: hipFuncSetAttribute failed");
-    hipLaunchKernelGGL((act_kernel<R, MT>), dim3((a.d.N + TM - 1) / TM, a.d.G), dim3(BLOCK), lds, stream, a);
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return fail(CAT_ACT_ERR_HIP, who, "hipFuncSetAttribute failed");
+    hipLaunchKernelGGL(kernel, dim3(tiles, G), dim3(BLOCK), lds, stream, a);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_ACT_OK : fail(CAT_ACT_ERR_HIP, hipGetErrorString(e));
+    return e == hipSuccess ? CAT_ACT_OK : fail(CAT_ACT_ERR_HIP, who, hipGetErrorString(e));
 }
 
 }   // namespace
@@ -340,24 +388,37 @@ extern "C" int cat_act_supported(const cat_act_dims *d) { return d && dims_ok(*d
 
 extern "C" int cat_act_step(const cat_act_args *a, void *stream)
 {
-    if (!a || !dims_ok(a->d)) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: bad dimensions (G 1..8, A 1..8, N >= 1, R 64 or 90)");
-    for (int g = 0; g < a->d.G; ++g)
-        if (a->agent[g] < 0 || a->agent[g] >= a->d.A) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: agent index out of range");
-    if ((a->mode != CAT_ACT_SAMPLE && a->mode != CAT_ACT_GREEDY) || (a->random_mask >> a->d.G) != 0 ||
-        (a->row_tile != 0 && a->row_tile != 32 && a->row_tile != 64))
-        return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: bad mode, random_mask or row_tile");
-    if (!a->obs_distance || !a->obs_type || !a->uniform || !a->actions) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: a required buffer is NULL");
-    const bool all_random = a->random_mask == (1u << a->d.G) - 1u;
-    if (!all_random) {
-        const void *ps[] = {a->p.conv1_w, a->p.conv1_b, a->p.conv2_w, a->p.conv2_b, a->p.fc_w, a->p.fc_b, a->p.w_ih, a->p.w_hh, a->p.b_ih, a->p.b_hh,
-                            a->p.head0_w, a->p.head0_b, a->p.head1_w, a->p.head1_b, a->p.head2_w, a->p.head2_b, a->h, a->c};
-        for (const void *p : ps)
-            if (!p || ((uintptr_t)p % 16)) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: a parameter or state pointer is NULL or not 16-byte aligned");
-        if (a->p.stride % 8) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: the parameter stride must be a multiple of 8 elements");
-        if (a->logits_out && ((uintptr_t)a->logits_out % 8)) return fail(CAT_ACT_ERR_BAD_ARG, "cat_act_step: logits_out must be 8-byte aligned");
-    }
-    const int tile = a->row_tile ? a->row_tile : 32;
+    const char *who = "cat_act_step";
+    const bool all_random = a && dims_ok(a->d) && a->random_mask == (1u << a->d.G) - 1u;
+    if (const int rc = check_args(a, who, !all_random)) return rc;
+    const int TM = a->row_tile ? a->row_tile : 32, tiles = (a->d.N + TM - 1) / TM, G = a->d.G;
     hipStream_t s = (hipStream_t)stream;
-    if (a->d.R == 64) return tile == 32 ? launch<64, 2>(*a, s) : launch<64, 4>(*a, s);
-    return tile == 32 ? launch<90, 2>(*a, s) : launch<90, 4>(*a, s);
+    if (a->d.R == 64) return TM == 32 ? launch<64, 2>(act_kernel<64, 2>, *a, tiles, G, who, s) : launch<64, 4>(act_kernel<64, 4>, *a, tiles, G, who, s);
+    return TM == 32 ? launch<90, 2>(act_kernel<90, 2>, *a, tiles, G, who, s) : launch<90, 4>(act_kernel<90, 4>, *a, tiles, G, who, s);
+}
+
+extern "C" int cat_act_league_step(const cat_act_league_args *a, void *stream)
+{
+    const char *who = "cat_act_league_step";
+    if (!a || !dims_ok(a->base.d)) return fail(CAT_ACT_ERR_BAD_ARG, who, "bad dimensions (G 1..8, A 1..8, N >= 1, R 64 or 90)");
+    if (a->S < 1 || a->S > CAT_ACT_MAX_SEGMENTS) return fail(CAT_ACT_ERR_BAD_ARG, who, "S outside 1..32 segments");
+    if (a->sets < 1) return fail(CAT_ACT_ERR_BAD_ARG, who, "the bank needs at least one parameter set");
+    if (a->base.random_mask != 0) return fail(CAT_ACT_ERR_BAD_ARG, who, "random_mask must be 0 (a random policy is set index -1 of its segment)");
+    if (a->seg_start[0] != 0 || a->seg_start[a->S] != a->base.d.N) return fail(CAT_ACT_ERR_BAD_ARG, who, "seg_start must begin at 0 and end at N");
+    const int TM = a->base.row_tile == 64 ? 64 : 32, G = a->base.d.G;
+    int tiles = 0;
+    bool any_net = false;
+    for (int s = 0; s < a->S; ++s) {
+        if (a->seg_start[s + 1] <= a->seg_start[s]) return fail(CAT_ACT_ERR_BAD_ARG, who, "seg_start must be strictly increasing");
+        tiles += (a->seg_start[s + 1] - a->seg_start[s] + TM - 1) / TM;
+        for (int g = 0; g < G; ++g) {
+            if (a->seg_set[g][s] < -1 || a->seg_set[g][s] >= a->sets) return fail(CAT_ACT_ERR_BAD_ARG, who, "a set index outside [-1, sets)");
+            any_net |= a->seg_set[g][s] >= 0;
+        }
+    }
+    if (const int rc = check_args(&a->base, who, any_net)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (a->base.d.R == 64)
+        return TM == 32 ? launch<64, 2>(act_league_kernel<64, 2>, *a, tiles, G, who, st) : launch<64, 4>(act_league_kernel<64, 4>, *a, tiles, G, who, st);
+    return TM == 32 ? launch<90, 2>(act_league_kernel<90, 2>, *a, tiles, G, who, st) : launch<90, 4>(act_league_kernel<90, 4>, *a, tiles, G, who, st);
 }

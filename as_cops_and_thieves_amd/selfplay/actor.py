@@ -235,6 +235,155 @@ class PolicyActor:
         return self.actions
 
 
+class LeagueActor(PolicyActor):
+    """A ``PolicyActor`` whose env slots are cut into contiguous SEGMENTS, each naming per agent which parameter set of a BANK plays there
+    (or that the agent acts uniformly at random): one act tick plays many match-ups at once -- every archived opponent of an evaluation, or
+    a block of cells of a cross-play table.
+
+        actor = LeagueActor.from_env(env, sets=4)
+        actor.load_set(0, "cops/cop_iter_3.pt", "cop_0") ...
+        actor.set_matchups([(0, 8, {"cop_0": 0, "cop_1": 0, "thief_0": 2}), (8, 16, {"cop_0": 1, "cop_1": 1, "thief_0": "random"})])
+        actions = actor.act(env, starts)
+
+    fused: per tick one ``torch.rand(G, N)`` -- the draw a ``PolicyActor`` makes -- and ONE ``cat_act_league_step`` (include/cat_act.h).
+    unfused: per segment the ``StackedNet`` chain over the G parameter rows the segment names, on that segment's rows of the inputs and of
+    the state, then ``first_max_index`` / ``mappo._sample``; "random" draws ``torch.randint(0, 4, ...)`` and leaves its state rows alone."""
+
+    def __init__(self, group: _Group, bank: PolicyParams, agents: List[str], num_envs: int, num_rays: int, device, normalize_inputs: bool = False,
+                 fused: Union[str, bool] = "auto", row_tile: int = 0):
+        super().__init__([group], agents, num_envs, num_rays, device, normalize_inputs, fused, row_tile)
+        self.group, self.bank, self.sets = group, bank, bank.G
+        self.table = None                              # _learn_native.LeagueTable of the current match-ups
+        self._bank_params = None
+        self._nets = {}                                # unfused: (set index per agent) -> StackedNet over a copy of those bank rows
+
+    @classmethod
+    def from_env(cls, env, sets: int, fused: Union[str, bool] = "auto", compute_bf16: bool = True, normalize_inputs: bool = False,
+                 recurrent: bool = True, seed: int = 0, device=None, row_tile: int = 0) -> "LeagueActor":
+        """A bank of ``sets`` policy parameter rows for ``env``'s agents; set k starts from the weights ``torch.manual_seed(seed * 1000 + k)``
+        gives a fresh policy module.  The other arguments as in ``PolicyActor.from_checkpoint``."""
+        device = torch.device(device) if device is not None else getattr(env, "device", torch.device("cpu"))
+        agents = list(env.possible_agents)
+        R = env.observation_spaces[agents[0]]["distance"].shape[0]
+        dt = torch.bfloat16 if (compute_bf16 and device.type == "cuda") else torch.float32
+        arch = "lstm" if recurrent else "mlp"
+        if sets < 1:
+            raise ValueError("a bank needs at least one parameter set")
+        bank = PolicyParams(R, sets, device, dt, arch)
+        # the seeding below reaches every generator: the host's and this device's are put back (the actor's draws come from the latter)
+        forked = [torch.cuda.current_device() if device.index is None else device.index] if device.type == "cuda" else []
+        with torch.no_grad(), torch.random.fork_rng(devices=forked):
+            for k in range(sets):
+                torch.manual_seed(seed * 1000 + k)
+                for n, v in _module_for("policy", R, arch).state_dict().items():
+                    bank.views[f"policy.{n}"][k].copy_(v)
+        key = "+".join(r for r in ("cop", "thief") if any(a.startswith(r) for a in agents))
+        # the group's own G rows are scratch: what ``fusable`` / ``initial_state`` read of them is their shape, dtype and architecture
+        grp = _Group(key, agents, list(range(len(agents))), StackedNet("policy", R, PolicyParams(R, len(agents), device, dt, arch), arch), device)
+        return cls(grp, bank, agents, env.num_envs, R, device, normalize_inputs, fused, row_tile)
+
+    def load(self, source, roles=None) -> None:
+        raise TypeError("a LeagueActor holds a bank of parameter sets: load_set(k, source, agent)")
+
+    @torch.no_grad()
+    def load_set(self, k: int, source, agent: str) -> None:
+        """Copy the policy block of ``agent`` in ``source`` -- a checkpoint file or its loaded dict, in either layout ``PolicyActor.load``
+        reads, or ``{agent: {"policy": state_dict}}`` -- into set ``k`` of the bank."""
+        if not 0 <= k < self.sets:
+            raise IndexError(f"set {k} of a bank of {self.sets}")
+        sd = _load_file(source)
+        if agent not in sd:
+            raise KeyError(f"checkpoint holds no agent {agent!r} (it has {sorted(k_ for k_ in sd if k_ != META_KEY)})")
+        load_agent_state_dict(self.bank, k, sd[agent], kinds=("policy",))
+        self._nets.clear()
+
+    def set_matchups(self, segments) -> None:
+        """``segments``: [(start, stop, {agent: set index | "random"}), ...] -- contiguous row ranges that cover 0 .. N in order, at most
+        ``_learn_native.ACT_MAX_SEGMENTS`` of them, every agent named in each.  The rules of ``cat_act_league_step``; ValueError otherwise."""
+        segments = list(segments)
+        if not segments:
+            raise ValueError("no segments")
+        bounds = [segments[0][0]]
+        rows = [[] for _ in self.agents]
+        for lo, hi, who in segments:
+            if lo != bounds[-1]:
+                raise ValueError(f"segment ({lo}, {hi}) does not begin where the one before it ends ({bounds[-1]})")
+            bounds.append(hi)
+            if set(who) != set(self.agents):
+                raise ValueError(f"segment ({lo}, {hi}) must name exactly the agents {self.agents}: {sorted(who)}")
+            for g, a in enumerate(self.agents):
+                v = who[a]
+                if not (v == "random" or (isinstance(v, int) and not isinstance(v, bool) and v >= 0)):
+                    raise ValueError(f"segment ({lo}, {hi}), {a}: {v!r} is neither a set index nor \"random\"")
+                rows[g].append(-1 if v == "random" else v)
+        self.table = _learn_native.league_table(self.N, len(self.agents), self.sets, bounds, rows)
+
+    @property
+    def segments(self) -> List[Tuple[int, int]]:
+        """[(start, stop)] of the current match-ups."""
+        b = self.table.start
+        return list(zip(b[:-1], b[1:]))
+
+    @property
+    def parameter_bytes(self) -> int:
+        return sum(self.sets * k * self.bank.views[n].element_size() for n, (_, k, _) in self.bank.offsets.items())
+
+    def _segment_net(self, sets: Tuple[int, ...]) -> StackedNet:
+        """The stacked net whose row g holds bank set ``sets[g]`` (row 0's for a random agent: evaluated and thrown away)."""
+        if sets not in self._nets:
+            fp = PolicyParams(self.R, len(sets), self.device, self.bank.compute_dtype, self.group.policy.arch)
+            fp.lp.copy_(self.bank.lp[[max(k, 0) for k in sets]])
+            self._nets[sets] = StackedNet("policy", self.R, fp, self.group.policy.arch)
+        return self._nets[sets]
+
+    @torch.no_grad()
+    def act(self, env, starts: Optional[torch.Tensor] = None, greedy: bool = False, random_roles: Tuple[str, ...] = (), obs=None,
+            logits_out=None, logp_out=None) -> torch.Tensor:
+        """``PolicyActor.act`` under the current match-ups.  ``random_roles`` must stay empty: a random agent is "random" in its segments.
+        ``logits_out`` [G, N, 4] is filled on both paths, ``logp_out`` [G, N] by the kernel only."""
+        if random_roles:
+            raise ValueError("LeagueActor: name \"random\" in set_matchups instead of random_roles")
+        if self.table is None:
+            raise RuntimeError("LeagueActor.act before set_matchups")
+        g, N = self.group, self.N
+        h, c = self.state[g.role]
+        if self.fused:
+            raw = env.raw_outputs()
+            keep = None
+            if starts is not None:
+                keep = torch.logical_not(starts, out=self._keep)
+            if self._bank_params is None:
+                self._bank_params = _learn_native.act_params({n: self.bank.views[f"policy.{n}"] for n in _learn_native.ACT_PARAM_NAMES})
+            u = torch.rand(g.G, N, device=self.device)
+            _learn_native.act_league_step(raw, g.indices, self._bank_params, self.sets, self.table, None, h[0], c[0], keep, u, self.actions,
+                                          self._scales[0], self._scales[1], greedy, logits_out, logp_out, self.row_tile)
+            return self.actions
+        if obs is None:
+            obs = env.observations() if hasattr(env, "observations") else env._obs()
+        pin = torch.stack([packing.pack_policy_input(obs[a]) for a in g.agents])
+        if self.normalize_inputs:
+            pin = pin * self._pin_scale
+        for s, (lo, hi) in enumerate(self.segments):
+            sets = tuple(row[s] for row in self.table.table)
+            keep = None if starts is None else (~starts[lo:hi]).view(1, hi - lo)
+            logits, (hn, cn) = self._segment_net(sets).forward(pin[:, lo:hi].unsqueeze(1), (h[:, :, lo:hi], c[:, :, lo:hi]), keep)
+            if greedy:
+                act = first_max_index(logits[:, 0].float())
+            else:
+                act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
+            net = [i for i, k in enumerate(sets) if k >= 0]
+            if len(net) < g.G:
+                rows = torch.tensor([k < 0 for k in sets], device=self.device).view(g.G, 1)
+                act = torch.where(rows, torch.randint(0, 4, (g.G, hi - lo), device=self.device), act)
+            if logits_out is not None:                 # [G, N, 4]: the rows of the agents that evaluated a network, as the kernel
+                logits_out[net, lo:hi] = logits[net, 0].to(logits_out.dtype)
+            if hn.shape[0]:                            # the recurrent pair: the rows of the agents that evaluated a network move
+                h[:, net, lo:hi] = hn[:, net]
+                c[:, net, lo:hi] = cn[:, net]
+            self.actions[lo:hi].index_copy_(1, g.index_t, act.t().to(torch.int32))
+        return self.actions
+
+
 def first_max_index(z: torch.Tensor) -> torch.Tensor:
     """The lowest index of the largest entry along the last axis."""
     k = z.shape[-1]

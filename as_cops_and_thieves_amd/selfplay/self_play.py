@@ -235,6 +235,19 @@ def runner_pack(obs_agent):
     return packing.pack_policy_input(obs_agent)
 
 
+def _draw_new_opponent(opponent_archive: Path, opponent_role: str, tc: TrainingConfig, rng: random.Random, seen) -> Optional[str]:
+    """One archived ``opponent_role`` policy whose file name is not in ``seen``: 20 tries by the configured strategy, then 20 uniformly
+    (``agent_learning_utils.py:262-300``); None when none turned up."""
+    for strategy in (tc.policy_sample_strategy, "random"):
+        for _ in range(20):
+            cand = archive.sample_policy_from_archive(opponent_archive, opponent_role, strategy, rng=rng)
+            if cand is None:
+                break
+            if Path(cand).name not in seen:
+                return cand
+    return None
+
+
 def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, learned_role: str, opponent_role: str,
                    opponent_archive: Path, tc: TrainingConfig, rng: random.Random, log=print, tracked: bool = False,
                    fused_eval: bool = False) -> Dict[str, bool]:
@@ -249,17 +262,7 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
         evaluator.load_state_dict(learned.state_dict(), roles=[learned_role], optimizer=False)
     seen = set()
     for i in range(tc.num_opponents_to_evaluate):
-        path = None
-        for strategy in (tc.policy_sample_strategy, "random"):          # 20 tries for a new one, then 20 uniformly
-            for _ in range(20):
-                cand = archive.sample_policy_from_archive(opponent_archive, opponent_role, strategy, rng=rng)
-                if cand is None:
-                    break
-                if Path(cand).name not in seen:
-                    path = cand
-                    break
-            if path is not None:
-                break
+        path = _draw_new_opponent(opponent_archive, opponent_role, tc, rng, seen)
         if path is None:
             log(f"[self-play] no new distinct {opponent_role} opponent for evaluation round {i + 1}/{tc.num_opponents_to_evaluate}")
             break
@@ -280,13 +283,140 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
     return results
 
 
+@torch.no_grad()
+def evaluate_league(env, actor, episodes_per_segment=None) -> Dict[str, object]:
+    """``evaluate_agents``' loop -- the first episode of every slot, one poll per tick -- under the match-ups of a ``LeagueActor``: all its
+    segments play at once.  ``episodes_per_segment``: an int or one int per segment -- only the first that many slots of a segment count
+    (None: all of them; 0 for a segment that merely fills the env).  Returns per segment (lists in segment order) ``cop_wins`` (winner 0),
+    ``thief_wins`` (winner 1 before the step limit), ``timeouts`` (the step limit ran out; not the cops' win) -- the three add up to the
+    segment's counted slots -- and ``episodes``; per slot ``winner`` (int8, -1 where nothing counted) and ``length`` (ticks of the counted
+    episode, int32); and ``ticks``, the ticks played."""
+    N = env.num_envs
+    assert N == actor.N and actor.table is not None
+    segments = actor.segments
+    quota = episodes_per_segment
+    if quota is None or isinstance(quota, int):
+        quota = [quota] * len(segments)
+    assert len(quota) == len(segments)
+    dev = actor.device
+    open_ = torch.ones(N, dtype=torch.bool, device=dev)
+    for (lo, hi), q in zip(segments, quota):
+        if q is not None:
+            assert 0 <= q <= hi - lo, (lo, hi, q)
+            open_[lo + q:hi] = False
+    counted = open_.clone()
+    obs, _ = env.reset()
+    actor.reset()
+    starts = torch.ones(N, dtype=torch.bool, device=dev)
+    winner = torch.full((N,), -1, dtype=torch.int8, device=dev)
+    timeout = torch.zeros(N, dtype=torch.bool, device=dev)
+    length = torch.zeros(N, dtype=torch.int32, device=dev)
+    ticks = 0
+    for _ in range(env.max_step_count + 2):
+        if not bool(counted.any()):
+            break
+        actions = actor.act(env, starts, obs=obs)
+        obs, _, terms, truncs, infos = env.step(actions)
+        ticks += 1
+        done = terms[actor.agents[0]]
+        first = open_ & done
+        winner = torch.where(first, infos["winner"].to(torch.int8), winner)
+        timeout = torch.where(first, truncs[actor.agents[0]], timeout)
+        length = torch.where(first, torch.full_like(length, ticks), length)
+        open_ = open_ & ~done
+        starts = done.clone()
+        if not bool(open_.any()):                       # one host sync per tick, as evaluate_agents
+            break
+    w, t = winner.cpu(), timeout.cpu()
+    out = {"cop_wins": [], "thief_wins": [], "timeouts": [], "episodes": [], "winner": winner, "length": length, "ticks": ticks}
+    for (lo, hi), q in zip(segments, quota):
+        hi = hi if q is None else lo + q
+        out["cop_wins"].append(int((w[lo:hi] == 0).sum()))
+        out["thief_wins"].append(int(((w[lo:hi] == 1) & ~t[lo:hi]).sum()))
+        out["timeouts"].append(int(((w[lo:hi] != 0) & t[lo:hi]).sum()))
+        out["episodes"].append(hi - lo)
+    return out
+
+
+def evaluate_agent_league(eval_env, actor, learned: MAPPOTrainer, archives: Dict[str, Path], tc: TrainingConfig, rng: random.Random, log=print,
+                          learned_roles: Optional[Tuple[str, ...]] = None) -> Dict[str, Dict[str, bool]]:
+    """``evaluate_agent`` for the roles in ``learned_roles`` (default: cops, then thieves) in ONE pass of ``evaluate_league``: every newly
+    trained role against its up to ``tc.num_opponents_to_evaluate`` distinct archived opponents, each match-up on its own segment of
+    ``tc.n_trial_episodes`` slots of ``eval_env``.  ``actor``: a ``LeagueActor`` over ``eval_env`` with at least
+    ``len(agents) * (1 + tc.num_opponents_to_evaluate)`` sets; ``eval_env`` has ``len(learned_roles) * num_opponents_to_evaluate *
+    n_trial_episodes`` slots (segments that no opponent fills play at random and count nothing).  ``archives``: role -> its archive.
+    The opponents are drawn by ``evaluate_agent``'s own sampling loop -- the same strategy, the same ``rng`` consumption per draw -- and one
+    outcome per opponent is booked with ``archive.update_policy_win_rate`` in draw order.  Returns {learned role: {opponent file: opponent won}}.
+
+    The ONE protocol difference to the sequential form: here all opponents of a role are drawn from the win rates as they stood BEFORE this
+    evaluation; ``evaluate_agent`` draws opponent i + 1 after it has booked opponent i, so with PFSP its later draws see the earlier outcomes."""
+    cop, thief = tc.cop_role_prefix, tc.thief_role_prefix
+    learned_roles = (cop, thief) if learned_roles is None else tuple(learned_roles)
+    K, E, agents = tc.num_opponents_to_evaluate, tc.n_trial_episodes, list(actor.agents)
+    assert eval_env.num_envs == actor.N == len(learned_roles) * K * E, (eval_env.num_envs, actor.N, len(learned_roles), K, E)
+    assert actor.sets >= len(agents) * (1 + K), (actor.sets, len(agents), K)
+    role_of = {a: a.split("_")[0] for a in agents}
+    own = {a: g for g, a in enumerate(agents)}                            # sets 0 .. G - 1: the newly trained policies
+    drawn = {}
+    for learned_role in learned_roles:
+        opponent_role = thief if learned_role == cop else cop
+        seen, paths = set(), []
+        for i in range(K):
+            path = _draw_new_opponent(archives[opponent_role], opponent_role, tc, rng, seen)
+            if path is None:
+                log(f"[self-play] no new distinct {opponent_role} opponent for evaluation round {i + 1}/{K}")
+                break
+            seen.add(Path(path).name)
+            paths.append(path)
+        drawn[learned_role] = (opponent_role, paths)
+    results: Dict[str, Dict[str, bool]] = {r: {} for r in learned_roles}
+    if not any(paths for _, paths in drawn.values()):
+        return results
+    for a in agents:
+        actor.load_set(own[a], {a: learned.agent_models(a)}, a)
+    segments, quota, cells, nxt = [], [], [], len(agents)
+    for r, learned_role in enumerate(learned_roles):
+        opponent_role, paths = drawn[learned_role]
+        for i, path in enumerate(paths):
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+            who = {}
+            for a in agents:
+                if role_of[a] == opponent_role:
+                    actor.load_set(nxt, sd, a)
+                    who[a], nxt = nxt, nxt + 1
+                else:
+                    who[a] = own[a]
+            lo = (r * K + i) * E
+            segments.append((lo, lo + E, who))
+            quota.append(E)
+            cells.append((learned_role, Path(path).name))
+        lo, hi = (r * K + len(paths)) * E, (r + 1) * K * E
+        if lo < hi:                                                       # fewer opponents than segments: these slots fill the env
+            segments.append((lo, hi, {a: "random" for a in agents}))
+            quota.append(0)
+            cells.append(None)
+    actor.set_matchups(segments)
+    res = evaluate_league(eval_env, actor, quota)
+    w = res["winner"].cpu()
+    for (lo, hi, _), cell in zip(segments, cells):
+        if cell is None:
+            continue
+        learned_role, name = cell
+        cop_rate, thief_rate = float((w[lo:hi] == 0).sum()) / E, float((w[lo:hi] == 1).sum()) / E
+        opponent_won = (thief_rate > cop_rate) if learned_role == cop else (cop_rate > thief_rate)
+        archive.update_policy_win_rate(archives[drawn[learned_role][0]], name, opponent_won, tc.win_rate_buffer_size)
+        results[learned_role][name] = opponent_won
+        log(f"[self-play]   {learned_role} vs {name}: cop {cop_rate:.2f} thief {thief_rate:.2f} -> opponent {'won' if opponent_won else 'lost'}")
+    return results
+
+
 def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optional[int] = None,
                   training: Optional[TrainingConfig] = None, trainer_cfg: Optional[TrainerConfig] = None,
                   role_cfg: Optional[Dict[str, RoleConfig]] = None, num_rays: int = 64, n_cops: Optional[int] = None,
                   n_thieves: Optional[int] = None, max_step_count: int = 2000, eval_envs: Optional[int] = None,
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
                   query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False,
-                  fused_eval: bool = False) -> Dict[str, object]:
+                  fused_eval: bool = False, league_eval: bool = False) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -294,6 +424,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     same surface).
     ``fused_eval``: the evaluator is a ``PolicyActor`` instead of a second ``MAPPOTrainer``: policy blocks and recurrent state only, and on a
     GPU the act tick of all policies is one launch (``include/cat_act.h``).
+    ``league_eval``: both roles' evaluations of an iteration share ONE pass (``evaluate_agent_league``) through a ``LeagueActor`` on an
+    evaluation env of ``2 x num_opponents_to_evaluate x n_trial_episodes`` slots (``eval_envs``, if given, must be that number); the log
+    lines and ``win_rates.json`` keep their form.  Not with ``tracked_eval``.
     ``tracked_eval``: the evaluation env is built with ``track_episodes=True`` and evaluation goes through
     ``evaluate_agents_tracked``.  ``episode_stats``: the training env is built with ``track_episodes=True``, the trainer reports the
     training episodes (``TrainerConfig.episode_stats``), every iteration's log line carries their win rate and mean length, and rank
@@ -304,6 +437,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     ranks hold identical parameters at all times); rank 0 alone evaluates and writes files, the others wait and read them."""
     import torch.distributed as dist
     from ..sharding import shard_envs
+    if league_eval and tracked_eval:
+        raise ValueError("league_eval plays through evaluate_league (one poll per tick): it cannot be combined with tracked_eval")
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     chief = rank == 0
@@ -332,6 +467,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
             p.mkdir(parents=True, exist_ok=True)
     sync()
     n_eval = eval_envs or tc.n_trial_episodes
+    if league_eval:
+        n_eval = 2 * tc.num_opponents_to_evaluate * tc.n_trial_episodes
+        if eval_envs not in (None, n_eval):
+            raise ValueError(f"league_eval plays on 2 x {tc.num_opponents_to_evaluate} opponents x {tc.n_trial_episodes} episodes = {n_eval} slots, not eval_envs={eval_envs}")
     train_factory = eval_factory = env_factory
     if env_factory is None:
         preset = load_preset(map_name, n_cops, n_thieves)
@@ -359,7 +498,12 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
             raise TypeError(f"{what}=True needs envs with an {attr!r} (VecCopsEnv(track_episodes=True)); the env_factory's have none")
     role_cfg = role_cfg or {"cop": CFG_AGENT, "thief": CFG_AGENT}        # self_play_driver.py passes CFG_AGENT
     trainer = MAPPOTrainer(env, role_cfg, trainer_cfg, seed=seed)
-    if fused_eval:   # policy blocks and recurrent state only; on a GPU the act tick is one launch (include/cat_act.h)
+    if league_eval:  # a bank of policy blocks: the trained agents' and every drawn opponent's (include/cat_act.h, cat_act_league_step)
+        from .actor import LeagueActor
+        evaluator = LeagueActor.from_env(eval_env, len(eval_env.possible_agents) * (1 + tc.num_opponents_to_evaluate), fused="kernel",
+                                         compute_bf16=trainer_cfg.compute_bf16, normalize_inputs=trainer_cfg.normalize_inputs,
+                                         recurrent=trainer_cfg.recurrent, seed=seed + 1, device=trainer.device)
+    elif fused_eval:   # policy blocks and recurrent state only; on a GPU the act tick is one launch (include/cat_act.h)
         from .actor import PolicyActor
         evaluator = PolicyActor.from_checkpoint(None, eval_env, fused="kernel", compute_bf16=trainer_cfg.compute_bf16, normalize_inputs=trainer_cfg.normalize_inputs,
                                                 recurrent=trainer_cfg.recurrent, seed=seed + 1, device=trainer.device)
@@ -392,8 +536,11 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         if chief:
             try:
                 # ---- 3. evaluation against archived opponents (:199-228)
-                ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval),
-                      thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval)}
+                if league_eval:
+                    ev = evaluate_agent_league(eval_env, evaluator, trainer, arch, tc, rng, log)
+                else:
+                    ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval),
+                          thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval)}
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -497,6 +644,8 @@ def main() -> None:
                     "the host polls every 32 ticks instead of every tick")
     ap.add_argument("--fused-eval", action="store_true", help="evaluate through a PolicyActor (policy blocks only; on a GPU one launch per act tick) "
                     "instead of a second trainer")
+    ap.add_argument("--league-eval", action="store_true", help="evaluate both roles against all their drawn opponents in one pass through a LeagueActor "
+                    "(one act launch per tick for every match-up); not with --tracked-eval")
     ap.add_argument("--episode-stats", action="store_true", help="account the training episodes on the device: win rate and mean length in "
                     "every iteration's log line, episode_stats.json in --out (with --gpus N: of rank 0's shard)")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
@@ -521,7 +670,8 @@ def main() -> None:
     res = run_self_play(args.map, args.envs, args.out, iterations=args.iterations, training=tc, trainer_cfg=tcfg, role_cfg=role_cfg,
                         num_rays=args.rays, n_cops=args.cops, n_thieves=args.thieves, max_step_count=args.max_step_count,
                         eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
-                        query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval)
+                        query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval,
+                        league_eval=args.league_eval)
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

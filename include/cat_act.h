@@ -41,6 +41,7 @@ extern "C" {
 #define CAT_ACT_ABI_VERSION 1
 #define CAT_ACT_MAX_AGENTS 8
 #define CAT_ACT_HIDDEN 128
+#define CAT_ACT_MAX_SEGMENTS 32
 
 enum { CAT_ACT_OK = 0, CAT_ACT_ERR_BAD_ARG = -1, CAT_ACT_ERR_HIP = -2 };
 enum { CAT_ACT_SAMPLE = 0, CAT_ACT_GREEDY = 1 };
@@ -81,10 +82,26 @@ typedef struct cat_act_args {
     float *logp_out;                            /* [G][N] or NULL */
 } cat_act_args;
 
+/* The league form: the N rows are cut into S contiguous segments and every segment names, per policy, the parameter set of a
+   BANK that plays there.  base.p addresses the bank: set k of every block at pointer + k * stride.  Policy g in segment s (rows
+   seg_start[s] .. seg_start[s + 1] - 1; seg_start[0] == 0, seg_start[S] == N, strictly increasing) reads set seg_set[g][s] in
+   [0, sets); -1: policy g acts uniformly at random there (the random_mask rule: action min(3, (int)(4 * uniform)), its rows of
+   h / c / logits_out / logp_out untouched).  base.random_mask must be 0; everything else in base keeps its meaning.  A workgroup's
+   rows all lie in one segment, and a row's outputs depend on that row's inputs and its parameter set alone: neither on the tile
+   it falls into nor on the segment table around it. */
+typedef struct cat_act_league_args {
+    cat_act_args base;
+    int32_t S;                                  /* segments, 1 .. CAT_ACT_MAX_SEGMENTS */
+    int32_t sets;                               /* parameter sets in the bank, >= 1 */
+    int32_t seg_start[CAT_ACT_MAX_SEGMENTS + 1];
+    int32_t seg_set[CAT_ACT_MAX_AGENTS][CAT_ACT_MAX_SEGMENTS];
+} cat_act_league_args;
+
 int cat_act_abi_version(void);
 const char *cat_act_last_error(void);
 int cat_act_supported(const cat_act_dims *d);   /* 1: cat_act_step takes these dimensions */
 int cat_act_step(const cat_act_args *a, void *stream);
+int cat_act_league_step(const cat_act_league_args *a, void *stream);
 
 #ifdef __cplusplus
 }
