@@ -74,6 +74,7 @@ DENSE_SYMBOLS = ("cat_dense_abi_version", "cat_dense_last_error", "cat_dense_bia
 PPO_SYMBOLS = ("cat_ppo_abi_version", "cat_ppo_last_error", "cat_ppo_loss_grad", "cat_ppo_adam_step", "cat_ppo_gae_scan")
 RENDER_SYMBOLS = ("cat_render_abi_version", "cat_render_last_error", "cat_render_frames")
 EPISODES_SYMBOLS = ("cat_episodes_abi_version", "cat_episodes_last_error", "cat_episodes_update", "cat_episodes_summary")
+EPISODE_WINDOWS_SYMBOLS = ("cat_episode_windows_update",)     # include/cat_episodes.h: the update for rows of several env ticks
 ACT_SYMBOLS = ("cat_act_abi_version", "cat_act_last_error", "cat_act_supported", "cat_act_step", "cat_act_league_step")
 ACT_MAX_AGENTS = 8              # CAT_ACT_MAX_AGENTS
 ACT_MAX_SEGMENTS = 32           # CAT_ACT_MAX_SEGMENTS
@@ -215,7 +216,7 @@ def lib() -> C.CDLL:
         assert L.cat_render_abi_version() == 1
         L.cat_episodes_abi_version.restype = C.c_int
         L.cat_episodes_last_error.restype = C.c_char_p
-        for n in ("cat_episodes_update", "cat_episodes_summary"):
+        for n in ("cat_episodes_update", "cat_episodes_summary") + EPISODE_WINDOWS_SYMBOLS:
             getattr(L, n).restype = C.c_int
             getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
         assert L.cat_episodes_abi_version() == 1
@@ -717,6 +718,11 @@ class EpisodesUpdate(C.Structure):
                 ("quota", C.c_void_p), ("s", EpisodesState)]
 
 
+class EpisodeWindows(C.Structure):
+    """include/cat_episodes.h cat_episode_windows_args."""
+    _fields_ = [("u", EpisodesUpdate), ("ticks", C.c_void_p)]
+
+
 class EpisodesSummaryBlock(C.Structure):
     _fields_ = [("episodes", C.c_int64), ("cop_wins", C.c_int64), ("thief_wins", C.c_int64), ("timeouts", C.c_int64),
                 ("open_slots", C.c_int64), ("len_sum", C.c_int64), ("len_min", C.c_int32), ("len_max", C.c_int32),
@@ -731,9 +737,10 @@ def _episodes_state(state) -> EpisodesState:
     return EpisodesState(*[state[n].data_ptr() for n in EPISODES_STATE_FIELDS])
 
 
-def episodes_update(state, reward, terminated, truncated, winner, quota, max_step_count: int) -> None:
+def episodes_update(state, reward, terminated, truncated, winner, quota, max_step_count: int, ticks=None) -> None:
     """``state``: the tracker's device tensors by name (``EPISODES_STATE_FIELDS``); reward fp32 [T, N, A], terminated / truncated
-    u8 [T, N], winner i8 [T, N], all contiguous; quota int32 [N] or None.  One launch on the current stream (capturable)."""
+    u8 [T, N], winner i8 [T, N], all contiguous; quota int32 [N] or None.  One launch on the current stream (capturable).
+    ``ticks`` int32 [T, N]: the env ticks each row stands for (``cat_episode_windows_update``); None: one each."""
     import torch
     T, N, A = reward.shape
     assert reward.dtype == torch.float32 and reward.is_contiguous()
@@ -743,7 +750,12 @@ def episodes_update(state, reward, terminated, truncated, winner, quota, max_ste
     assert state["ret_run"].shape == (N, A) and state["len_run"].shape == (N,)
     a = EpisodesUpdate(T, N, A, int(max_step_count), reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), winner.data_ptr(),
                        _ptr(quota), _episodes_state(state))
-    _check(lib().cat_episodes_update(C.byref(a), _stream()), "cat_episodes_update")
+    if ticks is None:
+        _check(lib().cat_episodes_update(C.byref(a), _stream()), "cat_episodes_update")
+        return
+    assert ticks.dtype == torch.int32 and ticks.shape == (T, N) and ticks.is_contiguous() and ticks.device == reward.device
+    w = EpisodeWindows(a, ticks.data_ptr())
+    _check(lib().cat_episode_windows_update(C.byref(w), _stream()), "cat_episodes: cat_episode_windows_update")
 
 
 def episodes_summary(state, quota, block) -> None:

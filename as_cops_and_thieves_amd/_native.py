@@ -27,6 +27,7 @@ OUT_FIELDS = ("obs_distance", "obs_type", "hit_shape", "shared_distance", "share
 STATE_FIELDS = ("pos", "vel", "vbias", "tc", "leaf_bb", "wall_shape", "wall_age", "wall_jn",
                 "pair_age", "pair_jn", "step_count", "reset_count")
 WALL_CACHE = 8
+MAX_ROLLOUT_TICKS = 65536   # CAT_MAX_ROLLOUT_TICKS
 DEVERR_BAD_ACTION, DEVERR_CONTACT_DROPPED, DEVERR_SCHEDULER = 1, 2, 4
 
 GATE_NONE, GATE_INDEX, GATE_TREE = 0, 1, 2   # cat_config.bbtree_gate (CAT_GATE_*)
@@ -105,6 +106,7 @@ def lib() -> C.CDLL:
     L.cat_step.argtypes = [vp, vp, vp, vp]
     L.cat_step_fused.argtypes = [vp, vp, u64, i32, vp, vp]
     L.cat_rollout_fused.argtypes = [vp, i32, vp, u64, i32, vp, vp]
+    L.cat_step_repeat.argtypes = [vp, i32, vp, i32, vp, vp, vp]       # sim, k, actions, auto_reset, out, ticks, stream
     L.cat_get_state.argtypes = [vp, vp, vp]
     L.cat_set_state.argtypes = [vp, vp, vp]
     L.cat_random_actions.argtypes = [vp, u64, vp, vp]
@@ -134,7 +136,7 @@ def lib() -> C.CDLL:
     if hasattr(L, "cat_debug_tree_counts"):      # diagnostic builds only (-DCAT_TREE_COUNTS)
         L.cat_debug_tree_counts.argtypes = [vp, i32]
         L.cat_debug_tree_counts.restype = i32
-    for name in ("cat_create", "cat_destroy", "cat_reset", "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_get_state",
+    for name in ("cat_create", "cat_destroy", "cat_reset", "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_step_repeat", "cat_get_state",
                  "cat_set_state", "cat_random_actions", "cat_set_seed", "cat_device_errors", "cat_arm_kernel_timing", "cat_num_agents", "cat_num_shapes", "cat_selftest_arith", "cat_debug_grid_lookup"):
         getattr(L, name).restype = i32
     _lib = L
@@ -142,7 +144,7 @@ def lib() -> C.CDLL:
 
 
 EXPORTED_SYMBOLS = ("cat_abi_version", "cat_one_tick_kernel", "cat_rollout_kernel", "cat_chunks_per_unit", "cat_last_error", "cat_create", "cat_destroy", "cat_reset",
-                    "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_get_state", "cat_set_state", "cat_random_actions",
+                    "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_step_repeat", "cat_get_state", "cat_set_state", "cat_random_actions",
                     "cat_set_seed", "cat_device_errors", "cat_arm_kernel_timing", "cat_num_agents", "cat_num_shapes", "cat_selftest_arith", "cat_debug_grid_lookup",
                     "cat_grid_build_host", "cat_grid_lookup_host", "cat_grid_bytes_host", "cat_grid_free_host", "cat_map_wall_bb_depth_host",
                     "cat_bbtree_host")

@@ -20,9 +20,10 @@ constexpr int SLEVELS = 22;     // summary: levels of the tree a thread folds in
 constexpr int BINS = CAT_EPISODES_HIST_BINS;
 
 // Lane = slot.  The state of the slot lives in registers for the T ticks; the inputs of UNROLL ticks are loaded ahead of the
-// walk (a wave reads 64 * A contiguous floats and 64 contiguous bytes per stream and tick).
-template <int A>
-__global__ __launch_bounds__(UBLOCK) void episodes_update_kernel(const cat_episodes_update_args a)
+// walk (a wave reads 64 * A contiguous floats and 64 contiguous bytes per stream and tick).  kWindows: a row stands for ticks[row]
+// env ticks (cat_episode_windows_update); without it ``ticks`` is not read and the code is that of one tick per row.
+template <int A, bool kWindows>
+__global__ __launch_bounds__(UBLOCK) void episodes_update_kernel(const cat_episodes_update_args a, const int32_t *__restrict__ ticks)
 {
     __shared__ unsigned int hist[BINS];
     for (int b = threadIdx.x; b < BINS; b += UBLOCK) hist[b] = 0;
@@ -42,6 +43,7 @@ __global__ __launch_bounds__(UBLOCK) void episodes_update_kernel(const cat_episo
             float r[UNROLL][A];
             uint8_t term[UNROLL], trunc[UNROLL];
             int8_t win[UNROLL];
+            int played[UNROLL];
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
                 const bool live = t0 + u < a.T;                    // (the same in every lane)
@@ -49,13 +51,14 @@ __global__ __launch_bounds__(UBLOCK) void episodes_update_kernel(const cat_episo
 #pragma unroll
                 for (int i = 0; i < A; ++i) r[u][i] = a.reward[row * A + i];
                 term[u] = a.terminated[row]; trunc[u] = a.truncated[row]; win[u] = a.winner[row];
+                played[u] = kWindows ? ticks[row] : 1;
             }
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
                 if (t0 + u >= a.T) break;
 #pragma unroll
                 for (int i = 0; i < A; ++i) run[i] += (double)r[u][i];
-                len += 1;
+                len += played[u];
                 if (term[u]) {
                     if (!limited || fin < quota) {
                         fin += 1;
@@ -176,26 +179,41 @@ bool state_complete(const cat_episodes_state &s)
 extern "C" int cat_episodes_abi_version(void) { return CAT_EPISODES_ABI_VERSION; }
 extern "C" const char *cat_episodes_last_error(void) { return g_err; }
 
-extern "C" int cat_episodes_update(const cat_episodes_update_args *a, void *stream)
+// The argument checks and the launch of both update entries; ``ticks`` NULL = one tick per row.
+static int launch_update(const cat_episodes_update_args *a, const int32_t *ticks, void *stream, const char *dims, const char *null)
 {
     if (!a || a->T < 1 || a->T > CAT_EPISODES_MAX_TICKS || a->N <= 0 || a->A <= 0 || a->A > CAT_EPISODES_MAX_AGENTS || a->max_step_count <= 0)
-        return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_update: bad dimensions");
+        return fail(CAT_EPISODES_ERR_BAD_ARG, dims);
     if (!a->reward || !a->terminated || !a->truncated || !a->winner || !state_complete(a->s))
-        return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_update: a required buffer is NULL");
+        return fail(CAT_EPISODES_ERR_BAD_ARG, null);
     const dim3 grid((unsigned)(((long)a->N + UBLOCK - 1) / UBLOCK)), block(UBLOCK);
     hipStream_t st = (hipStream_t)stream;
+#define CAT_EP_LAUNCH(AA)                                                                                          \
+    case AA:                                                                                                       \
+        if (ticks) hipLaunchKernelGGL((episodes_update_kernel<AA, true>), grid, block, 0, st, *a, ticks);          \
+        else hipLaunchKernelGGL((episodes_update_kernel<AA, false>), grid, block, 0, st, *a, ticks);               \
+        break;
     switch (a->A) {
-    case 1: hipLaunchKernelGGL(episodes_update_kernel<1>, grid, block, 0, st, *a); break;
-    case 2: hipLaunchKernelGGL(episodes_update_kernel<2>, grid, block, 0, st, *a); break;
-    case 3: hipLaunchKernelGGL(episodes_update_kernel<3>, grid, block, 0, st, *a); break;
-    case 4: hipLaunchKernelGGL(episodes_update_kernel<4>, grid, block, 0, st, *a); break;
-    case 5: hipLaunchKernelGGL(episodes_update_kernel<5>, grid, block, 0, st, *a); break;
-    case 6: hipLaunchKernelGGL(episodes_update_kernel<6>, grid, block, 0, st, *a); break;
-    case 7: hipLaunchKernelGGL(episodes_update_kernel<7>, grid, block, 0, st, *a); break;
-    default: hipLaunchKernelGGL(episodes_update_kernel<8>, grid, block, 0, st, *a); break;
+    CAT_EP_LAUNCH(1) CAT_EP_LAUNCH(2) CAT_EP_LAUNCH(3) CAT_EP_LAUNCH(4) CAT_EP_LAUNCH(5) CAT_EP_LAUNCH(6) CAT_EP_LAUNCH(7)
+    default:
+        if (ticks) hipLaunchKernelGGL((episodes_update_kernel<8, true>), grid, block, 0, st, *a, ticks);
+        else hipLaunchKernelGGL((episodes_update_kernel<8, false>), grid, block, 0, st, *a, ticks);
+        break;
     }
+#undef CAT_EP_LAUNCH
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? CAT_EPISODES_OK : fail(CAT_EPISODES_ERR_HIP, hipGetErrorString(e));
+}
+
+extern "C" int cat_episodes_update(const cat_episodes_update_args *a, void *stream)
+{
+    return launch_update(a, nullptr, stream, "cat_episodes_update: bad dimensions", "cat_episodes_update: a required buffer is NULL");
+}
+
+extern "C" int cat_episode_windows_update(const cat_episode_windows_args *a, void *stream)
+{
+    return launch_update(a ? &a->u : nullptr, a ? a->ticks : nullptr, stream, "cat_episode_windows_update: bad dimensions",
+                         "cat_episode_windows_update: a required buffer is NULL");
 }
 
 extern "C" int cat_episodes_summary(const cat_episodes_summary_args *a, void *stream)

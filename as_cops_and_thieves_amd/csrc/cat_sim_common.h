@@ -85,6 +85,7 @@ struct Params {
     const double *tree_bb;
     const int *tree_link;
     const int *tree_root;
+    int lds_racc_off;       // cat_step_repeat: byte offset, in a slot's env area, of its [A] f32 reward accumulators (lds_sizes)
 };
 
 // Problem dimensions as seen by the device code: either read from the parameter block (DynDims) or compile-time
@@ -206,6 +207,9 @@ struct LaunchArgs {
     int auto_reset;                 // step / rollout: episodes that end with a tick are reset inside the same launch
     unsigned long long synth_tick;  // step / rollout with actions == NULL: Philox actions of this tick (rollout: of the first tick)
     int T;                          // rollout_kernel: ticks per launch (outputs and actions carry a leading T)
+    int repeat;                     // rollout_kernel, cat_step_repeat: the T ticks of a slot are ONE decision -- actions is one [N, A] row held for every tick, the
+                                    // outputs are [N, ...] (the slot's last played tick; rewards summed in tick order) and a slot stops at the tick that ends its episode
+    int *ticks;                     // repeat: [N] ticks played per slot, or null
 };
 
 // What a kernel's prologue needs of the parameter block (env id, descriptors, state record, map staging, LDS carve), as a THIRD

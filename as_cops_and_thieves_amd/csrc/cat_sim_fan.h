@@ -375,7 +375,7 @@ __device__ __forceinline__ void tree_walls_result(const Lds &L, const Params &p,
 
 // One 64-ray chunk c (agent c / cpa, rays (c % cpa) * 64 ...) of the env whose env area is in L; the scratch
 // union of L is the calling wave's.  Writes the chunk's observations to the env's output staging.
-template <class D>
+template <class D, bool kRowGate = false>
 __device__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int lane,
                           int S, float cmax, int rew_mode, int c, PhaseClock &pc)
 {
@@ -582,7 +582,7 @@ __device__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, c
             const int q = i * R + k;
             L.od[q] = (unsigned short)d16;
             L.ot[q] = (unsigned char)ty;
-            if (la.out.hit_shape) la.out.hit_shape[(size_t)env * A * R + q] = best;  // parity/debug only
+            if (la.out.hit_shape && (!kRowGate || env >= 0)) la.out.hit_shape[(size_t)env * A * R + q] = best;  // parity/debug only
             if (ty == want && d16 < dmin) dmin = d16;  // non-negative f16: bit order = value order
         }
         PHASE(pc, 8);
@@ -607,7 +607,7 @@ __device__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, c
 // packed), and a chunk that alone exceeds the list is handed back to the caller for fan_chunk.
 // Requires (cat_create): one-word rows of id fields (row_id_bits != 0, row_words == 1), shape ids S + A <= 127, at most kSlotPos candidates per ray.
 constexpr int kSlotChunks = 3, kSlotPos = 16;   // (kSlotPos bits per chunk in a 64-bit mask; a chunk's first item in 10 bits of a 32-bit word: item_cap < 1024)
-template <class D>
+template <class D, bool kRowGate = false>
 __device__ __forceinline__ unsigned fan_slot(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int lane,
                                              int S, float cmax, int rew_mode, int c0, int nq, PhaseClock &pc)
 {
@@ -806,7 +806,7 @@ __device__ __forceinline__ unsigned fan_slot(const Lds &L, const Params &p, cons
                 const int o = i * R + k;
                 L.od[o] = (unsigned short)d16;
                 L.ot[o] = (unsigned char)ty;
-                if (la.out.hit_shape) la.out.hit_shape[(size_t)env * A * R + o] = best;  // parity/debug only
+                if (la.out.hit_shape && (!kRowGate || env >= 0)) la.out.hit_shape[(size_t)env * A * R + o] = best;  // parity/debug only
                 const unsigned want = i < n_cops ? CAT_THIEF : CAT_COP;
                 if (ty == want) dmin = d16;  // non-negative f16: bit order = value order
             }
@@ -832,7 +832,7 @@ __device__ __forceinline__ unsigned fan_slot(const Lds &L, const Params &p, cons
 // agents): a ray without a candidate gets its EMPTY observation at once, the others go into a compact list; then rounds of 64
 // ACTIVE rays run the position-major fan of fan_chunk with the origin, the "inside" walls and the roster side per lane.
 // Requires (cat_create): every candidate list fits a four-byte row (fields of wall id + 1), shape ids S + A fit 6 bits, R <= kGroupRays.
-template <class D>
+template <class D, bool kRowGate = false>
 __device__ void fan_group(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int lane,
                           int S, float cmax, int rew_mode, int g, int gsz, PhaseClock &pc)
 {
@@ -887,7 +887,7 @@ __device__ void fan_group(const Lds &L, const Params &p, const LaunchArgs &la, c
                 const int q = i * R + k;
                 L.od[q] = (unsigned short)d_empty;
                 L.ot[q] = (unsigned char)CAT_EMPTY;
-                if (la.out.hit_shape) la.out.hit_shape[(size_t)env * A * R + q] = -1;  // parity/debug only
+                if (la.out.hit_shape && (!kRowGate || env >= 0)) la.out.hit_shape[(size_t)env * A * R + q] = -1;  // parity/debug only
             }
             n_act += __popcll(m);
         }
@@ -1022,7 +1022,7 @@ __device__ void fan_group(const Lds &L, const Params &p, const LaunchArgs &la, c
             const int q = i * R + k;
             L.od[q] = (unsigned short)d16;
             L.ot[q] = (unsigned char)ty;
-            if (la.out.hit_shape) la.out.hit_shape[(size_t)env * A * R + q] = best;  // parity/debug only
+            if (la.out.hit_shape && (!kRowGate || env >= 0)) la.out.hit_shape[(size_t)env * A * R + q] = best;  // parity/debug only
             const unsigned want = i < n_cops ? CAT_THIEF : CAT_COP;
             // min over the agent's rays (other groups / rounds add theirs); non-negative f16: bit order = value order
             if (rew_mode && ty == want) __hip_atomic_fetch_min(&L.dmin[i], d16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

@@ -499,6 +499,7 @@ static const char *select_kernels(int A, int R, int n_cops, int fan, bool pool_r
 // LDS carve sizes (must match carve())
 struct LdsSizes {
     int map, env, uni;
+    int racc;   // offset in an env area of the [A] f32 reward accumulators of cat_step_repeat
     size_t total(int wpb) const { return (size_t)map + (size_t)ctrl_bytes(wpb) + (size_t)wpb * ((size_t)env + (size_t)uni); }
 };
 static LdsSizes lds_sizes(int A, int R, int maxS, int maxP, int maxPP, bool group_fan, int maxc, int grp_rays = 4 * 64)
@@ -516,7 +517,12 @@ static LdsSizes lds_sizes(int A, int R, int maxS, int maxP, int maxPP, bool grou
     const int rec_bytes = 96 * A + 16 + ((A * kK + NPs) * 8 + (2 * A * kK + NPs) * 4 + 15) / 16 * 16;
     int eb = rec_bytes + 8 * A * 8;                                // record, spawn/snapshot
     eb += (3 * A + 2 * A * A + A + A + 4) * 4;                     // acell, anear, dk0, dcnt, adn, dmin, flags
+    // cat_step_repeat's reward accumulators ([A] f32) take the bytes the staging's 16-byte alignment leaves free behind the flags where they fit there
+    // (2v1: 12 of 12, 1v1: 8 of 8), else the end of the area -- which the padding below absorbs for 3v2: the carve of every instantiated shape keeps its size
+    const int gap = up(eb, 16) - eb;
+    z.racc = gap >= 4 * A ? eb : -1;
     eb = up(eb, 16) + up(A * R * 2, 16) + up(A * R, 16) + up(2 * R * 2, 16) + up(2 * R, 16);   // output staging
+    if (z.racc < 0) { z.racc = eb; eb += up(4 * A, 16); }
     z.env = up(eb, 16);
     // The pooled rounds address env areas PER LANE (a round's rays come from several slots: origin, cached circles, "inside" walls, output staging of the
     // lane's slot).  An area of a multiple of 256 bytes -- 2v1 at 64 rays: exactly 2048 -- puts the same field of every slot on the same LDS banks; with
@@ -1112,6 +1118,7 @@ extern "C" int cat_create(const cat_config *cfg, const cat_tables *tab, const vo
         }
         p.maxE = maxS + A;
         p.lds_map_bytes = ls.map; p.lds_env_bytes = ls.env; p.lds_union_bytes = ls.uni; p.wpb = wpb;
+        p.lds_racc_off = ls.racc;
         p.grp_rays = grp_rays;
         p.item_cap = item_cap;
         p.lds_pool_off = pool_cap ? (int)((ls.total(wpb) + 15) / 16 * 16) : 0;
@@ -1287,6 +1294,24 @@ extern "C" int cat_rollout_fused(cat_sim *s, int T, const int32_t *actions, uint
     memset(&la, 0, sizeof la);
     if (out) la.out = *out;
     la.actions = actions; la.synth_tick = synth_tick0; la.T = T;
+    la.auto_reset = auto_reset ? 1 : 0;
+    const int rc = launch_parts(s, la, stream, kFnRollout);
+    if (rc != CAT_OK) return rc;
+    HIP_TRY(s, hipGetLastError());
+    return CAT_OK;
+}
+
+// One decision of k held-action ticks per env slot in ONE resident launch (the sim's rollout kernel with T = k in repeat mode): see include/cat_sim.h.
+extern "C" int cat_step_repeat(cat_sim *s, int k, const int32_t *actions, int auto_reset, const cat_outputs *out, int32_t *ticks, void *stream)
+{
+    if (!s) return CAT_ERR_BAD_ARG;
+    if (k < 1 || k > CAT_MAX_ROLLOUT_TICKS) { snprintf(s->err, sizeof s->err, "cat_step_repeat: k = %d outside 1..%d", k, CAT_MAX_ROLLOUT_TICKS); return CAT_ERR_BAD_ARG; }
+    if (!actions) { snprintf(s->err, sizeof s->err, "cat_step_repeat: actions is NULL (synthetic actions are not offered by this entry)"); return CAT_ERR_BAD_ARG; }
+    HIP_TRY(s, hipSetDevice(s->device));
+    LaunchArgs la;
+    memset(&la, 0, sizeof la);
+    if (out) la.out = *out;
+    la.actions = actions; la.T = k; la.repeat = 1; la.ticks = ticks;
     la.auto_reset = auto_reset ? 1 : 0;
     const int rc = launch_parts(s, la, stream, kFnRollout);
     if (rc != CAT_OK) return rc;

@@ -220,15 +220,27 @@ __device__ __forceinline__ void publish_slot(const Lds &L, int wave, int lane, i
 // Write-back of one finished slot tick: rewards (cop.py / thief.py), the counters of the state record, the record itself
 // (store_rec: the one-tick kernels store it every tick, the resident rollout kernel only after its last tick) and every
 // output.  env_out indexes the output buffers: the env slot, or row t * N + env of buffers with a leading T.
+// fold_t >= 0 (cat_step_repeat: tick fold_t of the slot's held-action window, env_out = the env slot): the tick's rewards are added to the slot's f32
+// accumulators in LDS (a left fold in tick order, plain adds), and only the window's last tick (store_rec) stores outputs: the sums, the tick count
+// and its own observations / flags.  A tick that is not the last leaves HBM alone.
 template <class D>
 __device__ __forceinline__ void slot_writeback(const Lds &Ls, const Params &p, const LaunchArgs &la, int e_s, long long env_out, int lane,
                                                int tick, bool store_rec, int step2, int captured2, int timeout2, int rcount,
-                                               GAS const float *cop_lut, GAS const float *thief_lut, PhaseClock &pc)
+                                               GAS const float *cop_lut, GAS const float *thief_lut, PhaseClock &pc, int fold_t = -1)
 {
     LateOut late;
+    const bool emit = fold_t < 0 || store_rec;
     rewards_and_positions<D>(Ls, p, la, lane, tick, captured2, timeout2, cop_lut, thief_lut, late);
-    stage_shared_observations<D>(Ls, p, lane);
+    if (emit) stage_shared_observations<D>(Ls, p, lane);
     await_reward(late);
+    if (fold_t >= 0) {
+        if (lane < D::A(p) && la.out.reward) {
+            float *const racc = reinterpret_cast<float *>(Ls.rec + p.lds_racc_off);
+            if (fold_t > 0) late.reward = racc[lane] + late.reward;
+            if (!store_rec) racc[lane] = late.reward;
+        }
+        if (store_rec && lane == 0 && la.ticks) la.ticks[env_out] = fold_t + 1;
+    }
     PHASE(pc, 17);
     const unsigned char term = (unsigned char)(captured2 || timeout2);
     if (lane == 0) {   // a slot that went through a reset (rcount >= 0) starts its new episode: base_env.py:350
@@ -237,9 +249,9 @@ __device__ __forceinline__ void slot_writeback(const Lds &Ls, const Params &p, c
     }
     if (store_rec) store_state<D>(Ls, p, e_s, lane);
     PHASE(pc, 18);
-    emit_observations<D>(Ls, p, la, env_out, lane, tick, late);
+    if (emit) emit_observations<D>(Ls, p, la, env_out, lane, tick, late);
     PHASE(pc, 19);
-    if (tick && lane == 0) {
+    if (tick && emit && lane == 0) {
         if (la.out.terminated) la.out.terminated[env_out] = term;       // entity.py:146
         if (la.out.truncated) la.out.truncated[env_out] = (unsigned char)timeout2;  // :397
         if (la.out.winner) la.out.winner[env_out] = (signed char)(captured2 ? 0 : (timeout2 ? 1 : -1));  // :399-406
@@ -541,7 +553,7 @@ __device__ __forceinline__ void rollout_body(const Params *__restrict__ pp0, con
 #ifdef CAT_WAVE_SPREAD
         { int e_ = env, s_ = md0.S; asm volatile("" : "+s"(e_), "+v"(s_)); WSPREAD(7); }   // env id and descriptor have arrived
 #endif
-        // control words of slot `wave`: claim word (above), units done in this epoch, -, env id
+        // control words of slot `wave`: claim word (above), units done in this epoch, the tick of the output row (resident launch; -1: none), env id
         if (lane < 4) ctrl[4 * wave + lane] = lane == 3 ? env : ((lane == 0 && env < 0) ? (int)kRwFinished : 0);
         StateRegs sregs;
         fetch_state<D>(sregs, q, env, lane);
@@ -570,7 +582,7 @@ __device__ __forceinline__ void rollout_body(const Params *__restrict__ pp0, con
             const int e_s = uni(ctrl[4 * slot + 3]);
             const Lds Ls = carve<D>(p, smem, K->md, slot, wave);
             int ap = 0;
-            if (la.actions && lane < D::A(p)) ap = la.actions[((size_t)t * p.N + e_s) * D::A(p) + lane];
+            if (la.actions && lane < D::A(p)) ap = la.actions[((size_t)((!kOneTick && la.repeat) ? 0 : t) * p.N + e_s) * D::A(p) + lane];   // repeat: one row, held
             if (lane == 0) ctrl[4 * slot + 1] = 0;
             const int n_fan = fan_units<D>(p, unit_span<D, kOneTick>(p, K->gd));
 #ifndef CAT_ABL_NOFRONT
@@ -580,6 +592,11 @@ __device__ __forceinline__ void rollout_body(const Params *__restrict__ pp0, con
             if (lane == 0) { Ls.flags[0] = 1; Ls.flags[1] = 0; Ls.flags[2] = 0; Ls.flags[3] = -1; }
             (void)ap;
 #endif
+            if constexpr (!kOneTick) {   // the row of tick t's outputs, for the units (see there)
+                int rt = t;
+                if (la.repeat) rt = (t + 1 >= la.T || uni(Ls.flags[1]) || uni(Ls.flags[2])) ? 0 : -1;
+                if (lane == 0) ctrl[4 * slot + 2] = rt;
+            }
             lds_release();
             // (publishing with unit 0 already claimed for this wave, and re-claiming the slot tick's next unit without a scan, were
             // built: labyrinth T = 64 26.7 us per tick against 20.5 -- waves then stay on their slots and "help the hindmost" is gone)
@@ -634,23 +651,27 @@ __device__ __forceinline__ void rollout_body(const Params *__restrict__ pp0, con
             const BlockDesc *const K = block_desc_lds(smem, p, W);
             const int e_s = uni(ctrl[4 * slot + 3]);
             const Lds Ls = carve<D>(p, smem, K->md, slot, wave);
-            const long long eo = (long long)t * p.N + e_s;   // row of the [T, N, ...] output buffers
+            long long eo = (long long)t * p.N + e_s;   // row of the [T, N, ...] output buffers
+            if constexpr (!kOneTick) {                 // resident: the front left the row's tick in control word 2 (repeat: 0 for the slot's last played tick, else -1 = none;
+                const int rt = uni(ctrl[4 * slot + 2]);   // hit_shape is the one output a unit stores).  Decided there: here it cost the tree-order kernel 20 B of scratch
+                eo = rt < 0 ? -1ll : (long long)rt * p.N + e_s;
+            }
             const int gsz = unit_span<D, kOneTick>(p, K->gd);
             SSPREAD(slot, 2 + 2 * unit);
             if (unit < fan_units<D>(p, gsz)) {
 #ifndef CAT_ABL_NOFAN      // diagnostic builds: a phase compiled out, for instruction counts by difference (tools/ablate_rollout.sh)
-                if constexpr (D::kFan == 1) fan_group<D>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, unit, gsz, pc);
+                if constexpr (D::kFan == 1) fan_group<D, !kOneTick>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, unit, gsz, pc);
                 else {
                     const int nch = D::A(p) * ((D::R(p) + kLanes - 1) / kLanes), c0 = unit * gsz, nq = nch - c0 < gsz ? nch - c0 : gsz;
                     // every chunk of the unit to fan_chunk, one after the other -- unless fan_slot runs, which hands back only what its item list cannot hold.
                     // cat_create gives a map several chunks per unit only where select_kernels chose kernels that carry fan_slot (fixed dimensions): the
                     // generic kernels always get one (a loop over several would cost them 8 VGPRs for nothing)
                     unsigned chunks = D::kFixed ? (1u << nq) - 1u : 1u;
-                    if (D::kFixed && gsz > 1) chunks = fan_slot<D>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, c0, nq, pc);
+                    if (D::kFixed && gsz > 1) chunks = fan_slot<D, !kOneTick>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, c0, nq, pc);
                     while (chunks) {
                         const int q = uni(__builtin_ctz(chunks));
                         chunks &= chunks - 1;
-                        fan_chunk<D>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, c0 + q, pc);
+                        fan_chunk<D, !kOneTick>(Ls, p, la, K->gd, eo, lane, uni(K->md.S), K->md.cmax, 1, c0 + q, pc);
                     }
                 }
 #endif
@@ -680,11 +701,14 @@ __device__ __forceinline__ void rollout_body(const Params *__restrict__ pp0, con
             SSPREAD(slot, 12);
             const int e_s = uni(ctrl[4 * slot + 3]);
             const Lds Ls = carve<D>(p, smem, K->md, slot, wave);
-            const long long eo = (long long)t * p.N + e_s;
+            const bool rep = !kOneTick && la.repeat != 0;
+            const long long eo = rep ? (long long)e_s : (long long)t * p.N + e_s;
             const int step2 = uni(Ls.flags[0]), captured2 = uni(Ls.flags[1]), timeout2 = uni(Ls.flags[2]), rcount = uni(Ls.flags[3]);
-            const bool last = t + 1 >= T;
+            // repeat: the tick that ends the slot's episode is its last one too (the hold rule) -- the record is flushed and the slot leaves the schedule exactly
+            // as after tick T - 1; the other slots of the workgroup go on
+            const bool last = t + 1 >= T || (rep && (captured2 || timeout2));
 #ifndef CAT_ABL_NOWB
-            slot_writeback<D>(Ls, p, la, e_s, eo, lane, 1, last, step2, captured2, timeout2, rcount, lut_c, lut_t, pc);
+            slot_writeback<D>(Ls, p, la, e_s, eo, lane, 1, last, step2, captured2, timeout2, rcount, lut_c, lut_t, pc, rep ? t : -1);
 #else
             (void)eo; (void)step2; (void)captured2; (void)timeout2; (void)rcount; (void)la;
 #endif
@@ -772,7 +796,7 @@ __device__ __forceinline__ int ring_pos(const Params &p, unsigned i)
 
 // The rays of one slot (its front just ran agent_setup): EMPTY observations for the candidate-less ones, ring entries for the others.
 // Returns the number of rays resolved here.  env: the slot's row of the output buffers (hit_shape only).
-template <class D, bool kExact>
+template <class D, bool kExact, bool kRowGate = false>
 __device__ __forceinline__ int pool_sort(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int slot, int lane,
                                          int *pctl, unsigned long long *pool)
 {
@@ -833,7 +857,7 @@ __device__ __forceinline__ int pool_sort(const Lds &L, const Params &p, const La
                     const int o = i * R + k;
                     L.od[o] = (unsigned short)d_empty;
                     L.ot[o] = (unsigned char)CAT_EMPTY;
-                    if (la.out.hit_shape) la.out.hit_shape[(size_t)env * A * R + o] = -1;  // parity/debug only
+                    if (la.out.hit_shape && (!kRowGate || env >= 0)) la.out.hit_shape[(size_t)env * A * R + o] = -1;  // parity/debug only
                 }
                 n_res += __popcll(__ballot(in && (rowv == 0u && dynmask == 0u)));
             }
@@ -844,7 +868,7 @@ __device__ __forceinline__ int pool_sort(const Lds &L, const Params &p, const La
 
 // One round: entries [base, base + n) of the ring, n <= 64, lane = entry.  L0: slot 0's view with the calling wave's scratch union.
 // Returns the mask of the slots whose tick this round completed.
-template <class D, bool kExact>
+template <class D, bool kExact, bool kRowGate = false>
 __device__ __forceinline__ unsigned pool_round(const Lds &L0, const Params &p, const LaunchArgs &la, int S, float cmax, int base, int n, int lane, int *ctrl,
                                unsigned long long *pool, PhaseClock &pc)
 {
@@ -995,8 +1019,13 @@ __device__ __forceinline__ unsigned pool_round(const Lds &L0, const Params &p, c
         slot_ptr(L0.od, s, envb)[o] = (unsigned short)d16;
         slot_ptr(L0.ot, s, envb)[o] = (unsigned char)ty;
         if (la.out.hit_shape) {   // parity/debug only: row (tick, env) of the slot
-            const long long eo = (long long)(rw_epoch((unsigned)ctrl[4 * s]) - 1) * p.N + ctrl[4 * s + 3];
-            la.out.hit_shape[(size_t)eo * A * R + o] = best;
+            const int ep = rw_epoch((unsigned)ctrl[4 * s]);
+            long long eo = (long long)(ep - 1) * p.N + ctrl[4 * s + 3];
+            if (kRowGate && la.repeat) {   // repeat: row = the slot, from its last played tick only
+                const int *const fl = slot_ptr(L0.flags, s, envb);
+                eo = (ep >= la.T || fl[1] || fl[2]) ? (long long)ctrl[4 * s + 3] : -1ll;
+            }
+            if (!kRowGate || eo >= 0) la.out.hit_shape[(size_t)eo * A * R + o] = best;
         }
         const unsigned want = i < n_cops ? CAT_THIEF : CAT_COP;
         // min over the agent's rays (other rounds add theirs); non-negative f16: bit order = value order
@@ -1084,13 +1113,15 @@ __device__ __forceinline__ void rollout_body_pool(const Params *__restrict__ pp0
             const int e_s = uni(ctrl[4 * slot + 3]), t = uni(ctrl[4 * slot + 2]);
             const Lds Ls = carve<D>(p, smem, K->md, slot, wave);
             int ap = 0;
-            if (la.actions && lane < D::A(p)) ap = la.actions[((size_t)t * p.N + e_s) * D::A(p) + lane];
+            if (la.actions && lane < D::A(p)) ap = la.actions[((size_t)((!kOneTick && la.repeat) ? 0 : t) * p.N + e_s) * D::A(p) + lane];   // repeat: one row, held
             if (lane == 0) ctrl[4 * slot + 1] = 0;
             const int n2 = slot_front<D>(Ls, (ParamsK)pp0, la, K->md, K->gd, e_s, lane, ap, la.synth_tick + (unsigned long long)t, 0, pc);   // 1: Space.step to come; 0: it ran inside (reset)
             lds_release();
             if (lane == 0) __hip_atomic_store((unsigned *)&ctrl[4 * slot], rw_make(t + 1, n2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             PHASE(pc, 3);
-            const int n_res = pool_sort<D, kExact>(Ls, p, la, K->gd, (long long)t * p.N + e_s, slot, lane, pool_ctl(smem, p, W), reinterpret_cast<unsigned long long *>(smem + p.lds_pool_off));
+            long long eo = (long long)t * p.N + e_s;
+            if (!kOneTick && la.repeat) eo = (t + 1 >= la.T || uni(Ls.flags[1]) || uni(Ls.flags[2])) ? (long long)e_s : -1ll;   // (as in rollout_body)
+            const int n_res = pool_sort<D, kExact, !kOneTick>(Ls, p, la, K->gd, eo, slot, lane, pool_ctl(smem, p, W), reinterpret_cast<unsigned long long *>(smem + p.lds_pool_off));
             lds_release();
             const int add = n_res + (n2 == 0 ? 1 : 0);
             int old = 0;
@@ -1115,10 +1146,14 @@ __device__ __forceinline__ void rollout_body_pool(const Params *__restrict__ pp0
             SSPREAD(slot, 12);
             const int e_s = uni(ctrl[4 * slot + 3]), t = uni(ctrl[4 * slot + 2]);
             const Lds Ls = carve<D>(p, smem, K->md, slot, wave);
-            const long long eo = (long long)t * p.N + e_s;
+            const bool rep = !kOneTick && la.repeat != 0;
+            const long long eo = rep ? (long long)e_s : (long long)t * p.N + e_s;
             const int step2 = uni(Ls.flags[0]), captured2 = uni(Ls.flags[1]), timeout2 = uni(Ls.flags[2]), rcount = uni(Ls.flags[3]);
-            const bool last = t + 1 >= T;
-            slot_writeback<D>(Ls, p, la, e_s, eo, lane, 1, last, step2, captured2, timeout2, rcount, lut_c, lut_t, pc);
+            // repeat: the hold rule, as in rollout_body.  A slot is written back only once every one of its rays has been counted, i.e. read out of the ring and
+            // cleared by its reader: a slot that leaves at an earlier tick than its neighbours has no entry in the ring and reserves none afterwards, so no writer
+            // waits for a position of its and no reader for an entry of its -- the same state in which a slot leaves after tick T - 1.
+            const bool last = t + 1 >= T || (rep && (captured2 || timeout2));
+            slot_writeback<D>(Ls, p, la, e_s, eo, lane, 1, last, step2, captured2, timeout2, rcount, lut_c, lut_t, pc, rep ? t : -1);
             wave_sync();   // the write-back has read the slot's staging and flags; the next front overwrites them
             SSPREAD(slot, 13);
             if (!last) { if (lane == 0) ctrl[4 * slot + 2] = t + 1; todo |= 1u << slot; }
@@ -1186,7 +1221,7 @@ __device__ __forceinline__ void rollout_body_pool(const Params *__restrict__ pp0
             const BlockDesc *const K = block_desc_lds(smem, p, W);
             if (n > 0) {
                 const Lds L0 = carve<D>(p, smem, K->md, 0, wave);
-                wbm |= pool_round<D, kExact>(L0, p, la, uni(K->md.S), K->md.cmax, base, n, lane, ctrl, reinterpret_cast<unsigned long long *>(smem + p.lds_pool_off), pc);
+                wbm |= pool_round<D, kExact, !kOneTick>(L0, p, la, uni(K->md.S), K->md.cmax, base, n, lane, ctrl, reinterpret_cast<unsigned long long *>(smem + p.lds_pool_off), pc);
             } else {
                 const Lds Ls = carve<D>(p, smem, K->md, slot, wave);
                 SSPREAD(slot, 2);

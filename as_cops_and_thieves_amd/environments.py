@@ -28,6 +28,7 @@ from .constants import DEFAULT_SENSOR, PhysicalParams, load_physical_params
 from .maps import CompiledMap, Map
 from .observation_spaces import (_init_shared_observation_space,
                                  get_nested_agent_observation_spaces as _nested_spaces)
+from ._native import MAX_ROLLOUT_TICKS as _MAX_REPEAT
 from .sim import CatSim
 
 WINNER_NAMES = {-1: None, 0: "cop", 1: "thief"}
@@ -279,6 +280,13 @@ def raw_env(map: Map, render_mode: str = "rgb_array", **kw):
     return parallel_to_aec(BaseEnv(map=map, render_mode=render_mode, **kw))
 
 
+def check_repeat(repeat, what: str = "repeat") -> int:
+    """A frame-skip count: an integer >= 1 (and within one resident launch), else ValueError."""
+    if isinstance(repeat, bool) or not isinstance(repeat, (int, np.integer)) or not 1 <= int(repeat) <= _MAX_REPEAT:
+        raise ValueError(f"{what} must be an integer in 1..{_MAX_REPEAT}, got {repeat!r}")
+    return int(repeat)
+
+
 class VecCopsEnv:
     """Batched env: ``num_envs`` independent envs advanced in lock-step on one GPU.
 
@@ -292,6 +300,15 @@ class VecCopsEnv:
     ``track_episodes=True`` (needs ``auto_reset``): an ``episodes.EpisodeTracker`` on the device adds the ticks of ``step``,
     ``step_raw`` and ``rollout_random`` up into episodes -- returns, lengths, outcomes (``episode_stats()``); an explicit
     ``reset`` abandons the episodes it cuts short.  Off by default: nothing is launched or stored.
+
+    Frame skip (action repeat): ``step(actions, repeat=k)`` / ``step_raw(actions, repeat=k)`` with ``k > 1`` play up to ``k`` env ticks
+    per slot with the actions held, in one resident launch (``CatSim.step_repeat``).  A slot stops at the tick that ends its episode
+    (the new episode is reset but not stepped with the stale action); rewards are the fp32 sums over the ticks played, observations
+    and flags those of the slot's last played tick, and ``infos["ticks"]`` / ``out["ticks"]`` the ticks played.  ``frame_skip=k`` in
+    the constructor sets the default ``repeat``.  ``repeat == 1`` is the one-tick path, unchanged.  With ``track_episodes`` the tracker
+    is given each row's tick count, so lengths, the histogram and the outcomes stay in env ticks; a return is the f64 sum of the fp32
+    window sums (``EpisodeTracker.update``).  ``out["ticks"]`` is written by repeat calls only: after a later one-tick step it still
+    holds the last repeat call's counts.
     """
 
     metadata = BaseEnv.metadata
@@ -301,8 +318,9 @@ class VecCopsEnv:
                  num_rays: int = 64, max_step_count: int = 400, time_step: float = 1 / 60.0,
                  auto_reset: bool = True, device=None, seed: int = 1, env_id_offset: int = 0,
                  physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True, query_order: str = "index",
-                 track_episodes: bool = False):
+                 track_episodes: bool = False, frame_skip: int = 1):
         gate = gate_mode(bbtree_gate, query_order)   # (before anything touches a device)
+        self.frame_skip = check_repeat(frame_skip, "frame_skip")
         if track_episodes and not auto_reset:
             raise ValueError("track_episodes=True needs auto_reset=True: the accounting restarts a slot's episode at its terminal tick")
         self.maps: List[Map] = list(maps) if isinstance(maps, (list, tuple)) else [maps]
@@ -360,9 +378,22 @@ class VecCopsEnv:
             self._tracker.clear()
         return stats
 
-    def _track(self, out) -> None:
+    def _track(self, out, ticks=None) -> None:
         if self._tracker is not None:
-            self._tracker.update(out["reward"], out["terminated"], out["truncated"], out["winner"])
+            self._tracker.update(out["reward"], out["terminated"], out["truncated"], out["winner"], ticks=ticks)
+
+    def _repeat(self, repeat) -> int:
+        """The ``repeat`` argument of ``step`` / ``step_raw``, checked: None is the constructor's ``frame_skip``."""
+        return self.frame_skip if repeat is None else check_repeat(repeat)
+
+    def _step_sim(self, acts, repeat: int):
+        if repeat == 1:
+            out = self._sim.step_fused(acts, auto_reset=self.auto_reset)
+            self._track(out)
+            return out
+        out = self._sim.step_repeat(acts, repeat, auto_reset=self.auto_reset)
+        self._track(out, out["ticks"])      # a row of a repeat call stands for ticks[n] env ticks of slot n
+        return out
 
     # spaces
     def observation_space(self, agent: str):
@@ -395,8 +426,10 @@ class VecCopsEnv:
             self._tracker.abandon(mask)
         return self._obs(), {a: {} for a in self.possible_agents}
 
-    def step(self, actions):
-        """``actions``: int tensor ``[num_envs, A]`` or ``{agent_id: tensor[num_envs]}``."""
+    def step(self, actions, repeat: Optional[int] = None):
+        """``actions``: int tensor ``[num_envs, A]`` or ``{agent_id: tensor[num_envs]}``.  ``repeat``: env ticks per call with the
+        actions held (default: the constructor's ``frame_skip``); above 1, ``infos["ticks"]`` holds the ticks each slot played."""
+        repeat = self._repeat(repeat)
         if isinstance(actions, dict):
             for i, aid in enumerate(self.possible_agents):
                 self._actions[:, i] = actions[aid].reshape(self.num_envs).to(self._actions.dtype)
@@ -405,11 +438,12 @@ class VecCopsEnv:
             acts = actions
         # one launch: finished episodes are reset inside the tick kernel, which leaves the NEW episode's first
         # observations in the buffers of those slots (rewards / flags / winner are the terminal tick's)
-        out = self._sim.step_fused(acts, auto_reset=self.auto_reset)
-        self._track(out)
+        out = self._step_sim(acts, repeat)
         rewards = {aid: out["reward"][:, i] for i, aid in enumerate(self.possible_agents)}
         terminated, truncated = out["terminated"].bool(), out["truncated"].bool()   # fresh tensors
         infos = {"winner": out["winner"].clone(), "terminated": terminated, "truncated": truncated}
+        if repeat > 1:
+            infos["ticks"] = out["ticks"].clone()
         terminations = {aid: terminated for aid in self.possible_agents}
         truncations = {aid: truncated for aid in self.possible_agents}
         return self._obs(), rewards, terminations, truncations, infos
@@ -430,12 +464,11 @@ class VecCopsEnv:
         """The per-agent observation dictionaries over the current output buffers (what ``step`` / ``reset`` return)."""
         return self._obs()
 
-    def step_raw(self, actions: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def step_raw(self, actions: torch.Tensor, repeat: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """``step`` without the per-agent dictionaries: one launch (tick + auto-reset), returns the output buffers
-        themselves (``raw_outputs()``): reward fp32 [N, A], terminated / truncated u8 [N], winner, observations."""
-        out = self._sim.step_fused(actions, auto_reset=self.auto_reset)
-        self._track(out)
-        return out
+        themselves (``raw_outputs()``): reward fp32 [N, A], terminated / truncated u8 [N], winner, observations.
+        ``repeat`` as in ``step``; above 1 the buffers also carry ``ticks`` int32 [N]."""
+        return self._step_sim(actions, self._repeat(repeat))
 
     def raw_outputs(self) -> Dict[str, torch.Tensor]:
         """The env core's output buffers as they lie on the device (``include/cat_sim.h`` ``cat_outputs``: f16 distances,

@@ -70,34 +70,45 @@ class EpisodeTracker:
             ln.lib()     # a missing kernel library is an error here, not at the first update
 
     # ------------------------------------------------------------------ feeding
-    def update(self, reward, terminated, truncated, winner) -> None:
+    def update(self, reward, terminated, truncated, winner, ticks=None) -> None:
         """One tick ``[N, ...]`` or T consecutive ticks ``[T, N, ...]`` of the env's outputs: reward ``[.., N, A]`` fp32,
-        terminated / truncated ``[.., N]`` (uint8 or bool), winner ``[.., N]`` int8."""
+        terminated / truncated ``[.., N]`` (uint8 or bool), winner ``[.., N]`` int8.
+
+        ``ticks`` (int ``[.., N]``, every entry >= 1): the rows are frame-skip windows (``CatSim.step_repeat``) -- row t of slot n
+        stands for ``ticks[t, n]`` env ticks, its reward is the window's fp32 sum and its flags are those of the window's last tick.
+        The slot's length then grows by ``ticks`` instead of by 1, so lengths, the histogram, outcomes and counts equal those of
+        tick-by-tick tracking.  A return is the f64 sum of the fp32 window sums in window order: it differs from the tick-by-tick f64
+        sum in the last bits (the fp32 adds inside a window have already rounded)."""
         if reward.dim() == 2:
             reward, terminated, truncated, winner = reward[None], terminated[None], truncated[None], winner[None]
+            ticks = None if ticks is None else ticks[None]
         T = reward.shape[0]
         if tuple(reward.shape) != (T, self.N, self.A) or any(tuple(t.shape) != (T, self.N) for t in (terminated, truncated, winner)):
             raise ValueError(f"EpisodeTracker.update: expected [T, {self.N}, {self.A}] rewards and [T, {self.N}] flags, got "
                              f"{tuple(reward.shape)}, {tuple(terminated.shape)}, {tuple(truncated.shape)}, {tuple(winner.shape)}")
-        if any(t.device != self.device for t in (reward, terminated, truncated, winner)):
+        if ticks is not None and tuple(ticks.shape) != (T, self.N):
+            raise ValueError(f"EpisodeTracker.update: expected [T, {self.N}] ticks, got {tuple(ticks.shape)}")
+        if any(t.device != self.device for t in (reward, terminated, truncated, winner) + (() if ticks is None else (ticks,))):
             raise ValueError(f"EpisodeTracker.update: the streams must lie on {self.device}")
         as_u8 = lambda t: (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).contiguous()
         reward = reward.to(torch.float32).contiguous()
         terminated, truncated, winner = as_u8(terminated), as_u8(truncated), winner.to(torch.int8).contiguous()
+        ticks = None if ticks is None else ticks.to(torch.int32).contiguous()
         if self._gpu:
             for t0 in range(0, T, ln.EPISODES_MAX_TICKS):
                 sl = slice(t0, min(T, t0 + ln.EPISODES_MAX_TICKS))
-                ln.episodes_update(self.state, reward[sl], terminated[sl], truncated[sl], winner[sl], self._quota, self.max_step_count)
+                ln.episodes_update(self.state, reward[sl], terminated[sl], truncated[sl], winner[sl], self._quota, self.max_step_count,
+                                   ticks=None if ticks is None else ticks[sl])
         else:
-            self._update_host(reward.numpy(), terminated.numpy(), truncated.numpy(), winner.numpy())
+            self._update_host(reward.numpy(), terminated.numpy(), truncated.numpy(), winner.numpy(), None if ticks is None else ticks.numpy())
 
-    def _update_host(self, reward, terminated, truncated, winner) -> None:
+    def _update_host(self, reward, terminated, truncated, winner, ticks=None) -> None:
         """The kernel's arithmetic in NumPy, slots in parallel, ticks in order."""
         s = {k: v.numpy() for k, v in self.state.items()}       # views: updated in place
         quota = self._quota.numpy()
         for t in range(reward.shape[0]):
             s["ret_run"] += reward[t].astype(np.float64)
-            s["len_run"] += 1
+            s["len_run"] += 1 if ticks is None else ticks[t]
             term = terminated[t] != 0
             if not term.any():
                 continue

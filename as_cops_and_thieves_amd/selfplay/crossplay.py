@@ -35,9 +35,11 @@ def policy_files(directory, role: str) -> List[Path]:
 @torch.no_grad()
 def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool = False, greedy: bool = False, num_rays: int = 64,
               n_cops: Optional[int] = None, n_thieves: Optional[int] = None, max_step_count: int = 2000, seed: int = 0, device=None,
-              fused: Union[str, bool] = "kernel", normalize_inputs: bool = False, env_factory=None, log=None) -> Dict[str, object]:
+              fused: Union[str, bool] = "kernel", normalize_inputs: bool = False, env_factory=None, log=None,
+              frame_skip: int = 1) -> Dict[str, object]:
     """``cops`` / ``thieves``: an archive directory or a list of checkpoint files.  ``episodes`` slots per cell; sampled actions, or the
     largest logit with ``greedy``.  ``env_factory(num_envs, seed)``: build the env some other way (``map_name`` etc. are then unused).
+    ``frame_skip``: env ticks per decision (``evaluate_league``); ``mean_length`` stays in env ticks.
     The sampled actions draw from torch's global generator: seed it for a reproducible table.  Returns what the module's docstring lists."""
     cop_files = [Path(f) for f in (cops if isinstance(cops, (list, tuple)) else policy_files(cops, "cop"))]
     thief_files = [Path(f) for f in (thieves if isinstance(thieves, (list, tuple)) else policy_files(thieves, "thief"))]
@@ -90,7 +92,7 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
             quota.append(0)
         loaded.clear()
         actor.set_matchups(segments)
-        res = evaluate_league(env, player, quota)
+        res = evaluate_league(env, player, quota, frame_skip=frame_skip)
         length = res["length"].cpu()
         for s, (i, j) in enumerate(chunk):
             col = columns.index(j)
@@ -120,10 +122,11 @@ def main() -> None:
     ap.add_argument("--max-step-count", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", type=Path, required=True)
+    ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat)")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     res = crossplay(args.cops, args.thieves, args.map, args.episodes, args.random_column, args.greedy, args.rays, args.n_cops, args.n_thieves,
-                    args.max_step_count, args.seed, log=print)
+                    args.max_step_count, args.seed, log=print, frame_skip=args.frame_skip)
     args.out.write_text(json.dumps(res, indent=1))
     print(f"[cross-play] {len(res['cops'])} x {len(res['thieves'])} cells in {res['passes']} pass(es) -> {args.out}")
 

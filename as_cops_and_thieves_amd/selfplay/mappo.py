@@ -104,6 +104,20 @@ class TrainerConfig:
                                            # return of the episodes finished during this ``train()`` call.  The accounting rides inside the
                                            # env's step (captured and replayed with the rollout graph); nothing of the rollout or the update
                                            # changes
+    frame_skip: int = 1                    # env ticks per decision (action repeat): every step of the rollout is ``env.step(actions,
+                                           # repeat=frame_skip)`` / ``step_raw(..., repeat=frame_skip)``, one resident launch that holds
+                                           # the actions for up to that many ticks and stops a slot where its episode ends.  Above 1 a
+                                           # "tick" of ``horizon``, ``bptt``, ``timesteps``, the freeze durations and the role configs'
+                                           # ``random_timesteps`` / ``learning_starts`` is a DECISION, ``discount_factor`` and ``lambda``
+                                           # apply per decision, and the rewards the learner sees are the env's fp32 window sums (the
+                                           # trainer adds nothing up itself).  ``read_stats()["env_ticks"]`` counts the env ticks played.
+                                           # The resident random-phase fast-forward stays as it is: it plays its span in env ticks,
+                                           # one per counted timestep
+
+    def __post_init__(self):
+        k = self.frame_skip
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"TrainerConfig.frame_skip must be an integer >= 1, got {k!r}")
 
 
 def compute_gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: torch.Tensor,
@@ -475,6 +489,8 @@ class MAPPOTrainer:
         self._native_post = self._native_io and hasattr(env, "step_raw")   # cat_rollout_post: rewards and flags of the raw step   # cat_rollout.h: packing and sampling in one launch each
         self._graph = None
         self._eager_rollouts = 0
+        self._env_ticks = torch.zeros((), dtype=torch.int64, device=self.device)   # frame_skip > 1: summed from the env's ``ticks`` on the device
+        self._env_ticks_host = 0                                                    # frame_skip == 1 and the fast-forward: N per tick, known here
         self.stats: Dict[str, float] = {}
         self.use_graphs = on_gpu
 
@@ -508,8 +524,11 @@ class MAPPOTrainer:
     def _rollout_ticks(self, random_actions) -> None:
         """T ticks: networks -> actions -> env.step into the preallocated buffers.  In-place updates of persistent
         tensors only and no host synchronisation: the whole loop is captured in one HIP graph and replayed.
-        ``random_actions``: True / False for every learner, or the set of learner keys still in their ``random_timesteps``."""
+        ``random_actions``: True / False for every learner, or the set of learner keys still in their ``random_timesteps``.
+        With ``TrainerConfig.frame_skip`` k > 1 each of the T steps is a decision: the env plays up to k ticks with the actions held and
+        returns the summed rewards, which go into the buffers as they come; the ticks played are added to a device counter."""
         N, T = self.N, self.tcfg.horizon
+        skip = {} if self.tcfg.frame_skip == 1 else {"repeat": self.tcfg.frame_skip}     # 1: the call is today's, argument for argument
         random_of = {key: (random_actions is True or (not isinstance(random_actions, bool) and key in random_actions))
                      for key in self.roles}
         any_random = any(random_of.values())
@@ -556,13 +575,17 @@ class MAPPOTrainer:
                 b["val"][:, t].copy_(val[:, 0, :, 0].float())
                 self._actions.index_copy_(1, rl.index_t, act.t().to(torch.int32))    # device index: capturable
             if all_fused:   # one launch for the tick, one for rewards + episode-end flags (cat_rollout_post)
-                raw = self.env.step_raw(self._actions)
+                raw = self.env.step_raw(self._actions, **skip)
+                if skip:
+                    self._env_ticks.add_(raw["ticks"].sum())
                 for i, rl in enumerate(self.roles.values()):
                     flags = (self._done_buf[t], self._starts, self._keep32) if i == 0 else (None, None, None)
                     _learn_native.rollout_post(raw, rl.indices, rl.buf["rew"][:, t], *flags)
                 self._obs = self.env.observations()
                 continue
-            self._obs, rewards, terms, truncs, infos = self.env.step(self._actions)
+            self._obs, rewards, terms, truncs, infos = self.env.step(self._actions, **skip)
+            if skip:
+                self._env_ticks.add_(infos["ticks"].sum())
             done = terms[self.agents[0]]
             for rl in self.roles.values():
                 rl.buf["rew"][:, t].copy_(torch.stack([rewards[a].float() for a in rl.agents]))
@@ -596,6 +619,7 @@ class MAPPOTrainer:
                     self._rollout_ticks(False)      # (sampling included) has then run once before it is captured
                     self._eager_rollouts += 1
                     self.timestep += self.tcfg.horizon
+                    self._count_env_ticks(self.tcfg.horizon)
                     return
                 torch.cuda.synchronize(self.device)
                 self._graph = torch.cuda.CUDAGraph()
@@ -603,6 +627,12 @@ class MAPPOTrainer:
                     self._rollout_ticks(False)
             self._graph.replay()
         self.timestep += self.tcfg.horizon
+        self._count_env_ticks(self.tcfg.horizon)
+
+    def _count_env_ticks(self, ticks: int) -> None:
+        """``ticks`` one-tick steps of all N slots went by (with ``frame_skip`` > 1 the rollout counts on the device instead)."""
+        if self.tcfg.frame_skip == 1:
+            self._env_ticks_host += self.N * ticks
 
     # ------------------------------------------------------------------ update
     def update(self, only: Optional[Sequence[str]] = None) -> Dict[str, float]:
@@ -630,7 +660,9 @@ class MAPPOTrainer:
         return {}
 
     def read_stats(self) -> Dict[str, float]:
-        """Host copy of the last minibatch's losses (one synchronisation; call it when you want to look)."""
+        """Host copy of the last minibatch's losses (one synchronisation; call it when you want to look), and ``env_ticks``: the env
+        ticks (slot-ticks, summed over the batch) played by ``collect`` and the random-phase fast-forward since the trainer was built --
+        with ``frame_skip`` > 1 the device sum of the env's per-slot ``ticks``, read here and nowhere else."""
         out = {}
         for rl in self.roles.values():
             s = rl.stat.cpu()
@@ -642,6 +674,7 @@ class MAPPOTrainer:
             out["episodes"], out["cop_win_rate"], out["mean_episode_length"] = e["episodes"], e["cop_win_rate"], e["mean_length"]
             for a in self.agents:
                 out[f"mean_return/{a}"] = e[f"mean_return/{a}"]
+        out["env_ticks"] = self._env_ticks_host + int(self._env_ticks)
         self.stats = out
         return out
 
@@ -723,6 +756,7 @@ class MAPPOTrainer:
             for st in rl.p_state + rl.v_state:
                 st.zero_()
         self.timestep += ticks
+        self._env_ticks_host += self.N * ticks      # one-tick steps whatever frame_skip is: nothing decides during this phase
 
     # ------------------------------------------------------------------ checkpoints
     def agent_models(self, agent: str) -> Dict[str, Dict[str, torch.Tensor]]:

@@ -67,17 +67,27 @@ class TrainingConfig:
     num_opponents_to_evaluate: int = 5        # evaluate_agent(num_additional_opponents_to_evaluate=5)
 
 
+def _skip_kw(frame_skip: int) -> dict:
+    """The keyword that makes ``env.step`` a frame-skip step; empty for 1, so that envs without the keyword keep working."""
+    if isinstance(frame_skip, bool) or not isinstance(frame_skip, int) or frame_skip < 1:
+        raise ValueError(f"frame_skip must be an integer >= 1, got {frame_skip!r}")
+    return {} if frame_skip == 1 else {"repeat": frame_skip}
+
+
 @torch.no_grad()
-def evaluate_agents(env, runner: Optional[MAPPOTrainer], n_episodes: int, random_roles: Tuple[str, ...] = (), actor=None) -> Tuple[float, float]:
+def evaluate_agents(env, runner: Optional[MAPPOTrainer], n_episodes: int, random_roles: Tuple[str, ...] = (), actor=None,
+                    frame_skip: int = 1) -> Tuple[float, float]:
     """``src/utils/eval_pfsp_agents.py:7-59``: ``n_episodes`` episodes with every model frozen, actions sampled from
     the policies (skrl ``policy.act``), an episode ends at its first termination and is a win of ``infos["winner"]``.
     Returns (cop wins / n, thief wins / n).  The batched form plays the episodes in parallel, one per env slot
     (``env.num_envs >= n_episodes``; the first episode of the first ``n_episodes`` slots counts).  ``random_roles``:
     these roles act uniformly at random instead (a fixed yardstick opponent; not part of the reference protocol).
-    ``actor`` (``actor.PolicyActor``): the policies act through it instead of through ``runner`` (which may then be None)."""
+    ``actor`` (``actor.PolicyActor``): the policies act through it instead of through ``runner`` (which may then be None).
+    ``frame_skip`` k > 1: the policies decide once per ``env.step(actions, repeat=k)``, i.e. every k env ticks of an episode."""
     N = env.num_envs
     who = actor if actor is not None else runner          # sizes, device and agent names: the actor's or the trainer's
     assert N >= n_episodes and N == who.N
+    skip = _skip_kw(frame_skip)
     obs, _ = env.reset()
     starts = torch.ones(N, dtype=torch.bool, device=who.device)
     state = _initial_states(runner, actor, N)
@@ -90,7 +100,7 @@ def evaluate_agents(env, runner: Optional[MAPPOTrainer], n_episodes: int, random
             actions = actor.act(env, starts, random_roles=random_roles, obs=obs)
         else:
             _trainer_actions(runner, obs, state, starts, actions, random_roles)
-        obs, _, terms, _, infos = env.step(actions)
+        obs, _, terms, _, infos = env.step(actions, **skip)
         done = terms[who.agents[0]]
         first = open_ & done
         winner = torch.where(first, infos["winner"].to(torch.int8), winner)
@@ -156,7 +166,7 @@ class _Rewind:
 
 @torch.no_grad()
 def evaluate_agents_tracked(env, runner: Optional[MAPPOTrainer], n_episodes: int, random_roles: Tuple[str, ...] = (),
-                            poll_every: int = 32, actor=None) -> Tuple[float, float]:
+                            poll_every: int = 32, actor=None, frame_skip: int = 1) -> Tuple[float, float]:
     """``evaluate_agents`` with the book-keeping done on the device by the env's ``episode_tracker`` (``episodes.EpisodeTracker``,
     which the env feeds on every ``step``): the same tick loop, but the host looks at the number of slots still owing an episode only
     every ``poll_every`` ticks instead of every tick, and a slot plays several episodes in a row, so any ``n_episodes`` is allowed.
@@ -168,10 +178,14 @@ def evaluate_agents_tracked(env, runner: Optional[MAPPOTrainer], n_episodes: int
     ``evaluate_agents`` uses, the env must offer ``episode_tracker`` and ``get_env_state(out=None)`` / ``set_env_state(**state)``.
     Cost of ``poll_every``: the window holds that many full copies of the env state on the device (a few hundred bytes per slot
     each), and every tick makes one state-copy launch and two host reads of generator state (a new 5 KB CPU snapshot each).
-    ``actor``: as in ``evaluate_agents``; its recurrent state is kept and put back with the env's."""
+    ``actor``: as in ``evaluate_agents``; its recurrent state is kept and put back with the env's.
+    ``frame_skip`` k > 1: one decision per ``env.step(actions, repeat=k)``; ``poll_every`` and the rewind then count decisions, the tracker
+    still counts lengths in env ticks (the env hands it every row's tick count), and the decision that closed the last counted episode
+    is kept on the device, since the slots' tick counts no longer tell it."""
     N = env.num_envs
     who = actor if actor is not None else runner          # sizes, device and agent names: the actor's or the trainer's
     assert N == who.N and n_episodes >= 1 and poll_every >= 1
+    skip = _skip_kw(frame_skip)
     tracker = env.episode_tracker
     obs, _ = env.reset()
     quota = torch.full((N,), n_episodes // N, dtype=torch.int32)
@@ -185,15 +199,23 @@ def evaluate_agents_tracked(env, runner: Optional[MAPPOTrainer], n_episodes: int
     limit = int(quota.max()) * env.max_step_count + 2
     rewind = _Rewind(env, who.device, poll_every, actor)
     stats, tick = None, 0
+    if skip:    # the decision after which the last slot filled its quota, found without a synchronisation
+        slots = tracker.per_slot()
+        owing = slots["finished"] < slots["quota"]
+        last_close = torch.zeros((), dtype=torch.int64, device=who.device)
     while tick < limit:
         if actor is not None:
             actions = actor.act(env, starts, random_roles=random_roles, obs=obs)
         else:
             _trainer_actions(runner, obs, state, starts, actions, random_roles)
-        obs, _, terms, _, _ = env.step(actions)
+        obs, _, terms, _, _ = env.step(actions, **skip)
         starts = terms[who.agents[0]].clone()
         tick += 1
         rewind.keep(tick)
+        if skip:
+            still = slots["finished"] < slots["quota"]
+            last_close = torch.where((owing & ~still).any(), torch.full_like(last_close, tick), last_close)
+            owing = still
         if tick % poll_every == 0 or tick == limit:
             stats = tracker.summary()                   # the one host synchronisation of these poll_every ticks
             if stats["open_slots"] == 0:
@@ -201,7 +223,7 @@ def evaluate_agents_tracked(env, runner: Optional[MAPPOTrainer], n_episodes: int
     assert stats is not None and stats["open_slots"] == 0 and stats["episodes"] == n_episodes, stats
     # a slot's counted episodes are its first ones after the reset, back to back: the last of them ended at tick max(len_sum), which
     # lies after the poll before this one (slots were still open then), i.e. within the poll_every ticks kept
-    rewind.restore(int(tracker.per_slot()["len_sum"].max()))
+    rewind.restore(int(last_close) if skip else int(tracker.per_slot()["len_sum"].max()))
     return float(stats["cop_wins"]) / n_episodes, float(stats["thief_wins"]) / n_episodes
 
 
@@ -250,11 +272,12 @@ def _draw_new_opponent(opponent_archive: Path, opponent_role: str, tc: TrainingC
 
 def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, learned_role: str, opponent_role: str,
                    opponent_archive: Path, tc: TrainingConfig, rng: random.Random, log=print, tracked: bool = False,
-                   fused_eval: bool = False) -> Dict[str, bool]:
+                   fused_eval: bool = False, frame_skip: int = 1) -> Dict[str, bool]:
     """``agent_learning_utils.py:233-380``: the newly trained ``learned_role`` against up to
     ``tc.num_opponents_to_evaluate`` distinct archived ``opponent_role`` policies.  Returns {opponent file: opponent won}.
     ``tracked``: play the episodes through ``evaluate_agents_tracked`` (``eval_env`` must feed an ``episode_tracker``).
-    ``fused_eval``: ``evaluator`` is a ``PolicyActor`` (``from_checkpoint(None, eval_env, ...)``) and the episodes are played through it."""
+    ``fused_eval``: ``evaluator`` is a ``PolicyActor`` (``from_checkpoint(None, eval_env, ...)``) and the episodes are played through it.
+    ``frame_skip``: env ticks per decision of the episodes played (``evaluate_agents``)."""
     results: Dict[str, bool] = {}
     if fused_eval:
         evaluator.load({a: learned.agent_models(a) for a in learned.agents}, roles=[learned_role])
@@ -274,8 +297,8 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
             evaluator.load_state_dict(torch.load(path, map_location=evaluator.device, weights_only=True), roles=[opponent_role],
                                       optimizer=False)                   # copy_role_models: policy + value weights
         play = evaluate_agents_tracked if tracked else evaluate_agents
-        cop_rate, thief_rate = (play(eval_env, None, tc.n_trial_episodes, actor=evaluator) if fused_eval
-                                else play(eval_env, evaluator, tc.n_trial_episodes))
+        cop_rate, thief_rate = (play(eval_env, None, tc.n_trial_episodes, actor=evaluator, frame_skip=frame_skip) if fused_eval
+                                else play(eval_env, evaluator, tc.n_trial_episodes, frame_skip=frame_skip))
         opponent_won = (thief_rate > cop_rate) if learned_role == tc.cop_role_prefix else (cop_rate > thief_rate)
         archive.update_policy_win_rate(opponent_archive, name, opponent_won, tc.win_rate_buffer_size)
         results[name] = opponent_won
@@ -284,15 +307,17 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
 
 
 @torch.no_grad()
-def evaluate_league(env, actor, episodes_per_segment=None) -> Dict[str, object]:
+def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1) -> Dict[str, object]:
     """``evaluate_agents``' loop -- the first episode of every slot, one poll per tick -- under the match-ups of a ``LeagueActor``: all its
     segments play at once.  ``episodes_per_segment``: an int or one int per segment -- only the first that many slots of a segment count
     (None: all of them; 0 for a segment that merely fills the env).  Returns per segment (lists in segment order) ``cop_wins`` (winner 0),
     ``thief_wins`` (winner 1 before the step limit), ``timeouts`` (the step limit ran out; not the cops' win) -- the three add up to the
     segment's counted slots -- and ``episodes``; per slot ``winner`` (int8, -1 where nothing counted) and ``length`` (ticks of the counted
-    episode, int32); and ``ticks``, the ticks played."""
+    episode, int32); and ``ticks``, the steps of the loop played.  ``frame_skip`` k > 1: one decision per ``env.step(actions, repeat=k)``;
+    ``length`` stays in env ticks (the sum of the slot's ``infos["ticks"]``), ``ticks`` counts decisions."""
     N = env.num_envs
     assert N == actor.N and actor.table is not None
+    skip = _skip_kw(frame_skip)
     segments = actor.segments
     quota = episodes_per_segment
     if quota is None or isinstance(quota, int):
@@ -311,18 +336,21 @@ def evaluate_league(env, actor, episodes_per_segment=None) -> Dict[str, object]:
     winner = torch.full((N,), -1, dtype=torch.int8, device=dev)
     timeout = torch.zeros(N, dtype=torch.bool, device=dev)
     length = torch.zeros(N, dtype=torch.int32, device=dev)
+    played = torch.zeros(N, dtype=torch.int32, device=dev)      # frame_skip > 1: env ticks of the slot so far
     ticks = 0
     for _ in range(env.max_step_count + 2):
         if not bool(counted.any()):
             break
         actions = actor.act(env, starts, obs=obs)
-        obs, _, terms, truncs, infos = env.step(actions)
+        obs, _, terms, truncs, infos = env.step(actions, **skip)
         ticks += 1
         done = terms[actor.agents[0]]
         first = open_ & done
         winner = torch.where(first, infos["winner"].to(torch.int8), winner)
         timeout = torch.where(first, truncs[actor.agents[0]], timeout)
-        length = torch.where(first, torch.full_like(length, ticks), length)
+        if skip:
+            played = played + infos["ticks"]
+        length = torch.where(first, played if skip else torch.full_like(length, ticks), length)
         open_ = open_ & ~done
         starts = done.clone()
         if not bool(open_.any()):                       # one host sync per tick, as evaluate_agents
@@ -339,7 +367,7 @@ def evaluate_league(env, actor, episodes_per_segment=None) -> Dict[str, object]:
 
 
 def evaluate_agent_league(eval_env, actor, learned: MAPPOTrainer, archives: Dict[str, Path], tc: TrainingConfig, rng: random.Random, log=print,
-                          learned_roles: Optional[Tuple[str, ...]] = None) -> Dict[str, Dict[str, bool]]:
+                          learned_roles: Optional[Tuple[str, ...]] = None, frame_skip: int = 1) -> Dict[str, Dict[str, bool]]:
     """``evaluate_agent`` for the roles in ``learned_roles`` (default: cops, then thieves) in ONE pass of ``evaluate_league``: every newly
     trained role against its up to ``tc.num_opponents_to_evaluate`` distinct archived opponents, each match-up on its own segment of
     ``tc.n_trial_episodes`` slots of ``eval_env``.  ``actor``: a ``LeagueActor`` over ``eval_env`` with at least
@@ -396,7 +424,7 @@ def evaluate_agent_league(eval_env, actor, learned: MAPPOTrainer, archives: Dict
             quota.append(0)
             cells.append(None)
     actor.set_matchups(segments)
-    res = evaluate_league(eval_env, actor, quota)
+    res = evaluate_league(eval_env, actor, quota, frame_skip=frame_skip)
     w = res["winner"].cpu()
     for (lo, hi, _), cell in zip(segments, cells):
         if cell is None:
@@ -537,10 +565,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
             try:
                 # ---- 3. evaluation against archived opponents (:199-228)
                 if league_eval:
-                    ev = evaluate_agent_league(eval_env, evaluator, trainer, arch, tc, rng, log)
+                    ev = evaluate_agent_league(eval_env, evaluator, trainer, arch, tc, rng, log, frame_skip=trainer_cfg.frame_skip)
                 else:
-                    ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval),
-                          thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval)}
+                    ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval, frame_skip=trainer_cfg.frame_skip),
+                          thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval, frame_skip=trainer_cfg.frame_skip)}
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -649,6 +677,8 @@ def main() -> None:
     ap.add_argument("--episode-stats", action="store_true", help="account the training episodes on the device: win rate and mean length in "
                     "every iteration's log line, episode_stats.json in --out (with --gpus N: of rank 0's shard)")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
+    ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat) in training and in the evaluations; above 1 "
+                    "--timesteps, --horizon and the schedule options count decisions")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))          # plain command: start the ranks ourselves
@@ -657,6 +687,8 @@ def main() -> None:
         backend = init_ranks(args.gpus)
     tc = TrainingConfig(policy_sample_strategy=args.strategy, training_timesteps_per_role_training=args.timesteps)
     over = {"horizon": args.horizon} if args.horizon else {}
+    if args.frame_skip != 1:
+        over["frame_skip"] = args.frame_skip
     if args.non_recurrent:
         over["recurrent"] = False
     if args.freeze_duration is not None:

@@ -24,7 +24,7 @@ from ..environments import WINNER_NAMES, VecCopsEnv
 from ..maps import load_preset
 from ..render import write_png
 from .mappo import CFG_AGENT, MAPPOTrainer, TrainerConfig
-from .self_play import _initial_states, _trainer_actions
+from .self_play import _initial_states, _skip_kw, _trainer_actions
 
 
 def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None,
@@ -37,10 +37,13 @@ def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_st
 @torch.no_grad()
 def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, ticks: int = 2000, rays: bool = False, seed: int = 0,
           num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None, n_thieves: Optional[int] = None, device=None,
-          log=print, fused_act: bool = False, greedy: bool = False) -> Dict[str, object]:
-    """``fused_act``: no trainer is built -- a ``PolicyActor`` reads the checkpoint's policy blocks and acts (on a GPU: one launch per tick,
+          log=print, fused_act: bool = False, greedy: bool = False, frame_skip: int = 1) -> Dict[str, object]:
+    """``frame_skip`` k > 1: the policies decide once per ``env.step(actions, repeat=k)`` and one frame is drawn per decision; ``ticks`` is then
+    the most decisions played, a slot's ``length`` stays in env ticks (the sum of its ``infos["ticks"]``).
+    ``fused_act``: no trainer is built -- a ``PolicyActor`` reads the checkpoint's policy blocks and acts (on a GPU: one launch per tick,
     ``include/cat_act.h``).  ``greedy`` (with ``fused_act``): the most probable action instead of a draw."""
     out_dir = Path(out_dir)
+    skip = _skip_kw(frame_skip)
     torch.manual_seed(seed)
     env = make_env(map_name, envs, seed, num_rays, max_step_count, n_cops, n_thieves, device)
     if greedy and not fused_act:
@@ -73,27 +76,33 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
     actions = torch.zeros(N, len(who.agents), dtype=torch.int32, device=who.device)
     open_host = [True] * N
     winner, length, ended = [None] * N, [ticks] * N, [False] * N
+    played = [0] * N                                                      # frame_skip > 1: env ticks of the slot's episode so far
     save(0, open_host)
     for t in range(1, ticks + 1):
         if actor is not None:
             actions = actor.act(env, starts, greedy=greedy, obs=obs)
         else:
             _trainer_actions(runner, obs, state, starts, actions, ())     # self_play.evaluate_agents' action selection
-        obs, _, terms, _, infos = env.step(actions)
+        obs, _, terms, _, infos = env.step(actions, **skip)
         starts = torch.zeros_like(starts)
         save(t, open_host)
         done = terms[who.agents[0]].cpu().tolist()
         win = infos["winner"].cpu().tolist()
+        if skip:
+            for k, n in enumerate(infos["ticks"].cpu().tolist()):
+                if open_host[k]:
+                    played[k] += n
+                    length[k] = played[k]
         for k in slots:
             if open_host[k] and done[k]:
-                open_host[k], ended[k], length[k], winner[k] = False, True, t, WINNER_NAMES[int(win[k])]
+                open_host[k], ended[k], length[k], winner[k] = False, True, played[k] if skip else t, WINNER_NAMES[int(win[k])]
         if not any(open_host):
             break
     env.check_errors()
+    frames_of = [(length[k] + 1) if ended[k] and not skip else (t + 1) for k in slots]
     result = {"map": map_name, "envs": N, "ticks": ticks, "checkpoint": checkpoint, "seed": seed, "rays": bool(rays),
-              **({"fused_act": True, "greedy": bool(greedy)} if fused_act else {}),
-              "slots": [{"env": k, "winner": winner[k], "length": length[k], "terminated": ended[k],
-                         "frames": (length[k] + 1) if ended[k] else (t + 1)} for k in slots]}
+              **({"fused_act": True, "greedy": bool(greedy)} if fused_act else {}), **({"frame_skip": frame_skip} if skip else {}),
+              "slots": [{"env": k, "winner": winner[k], "length": length[k], "terminated": ended[k], "frames": frames_of[k]} for k in slots]}
     (out_dir / "episode.json").write_text(json.dumps(result, indent=1))
     for s in result["slots"]:
         log(f"[watch] env {s['env']}: {'winner ' + str(s['winner']) if s['terminated'] else 'no termination'} after {s['length']} ticks")
@@ -115,13 +124,14 @@ def main(argv=None) -> int:
     ap.add_argument("--fused-act", action="store_true", help="act through a PolicyActor built straight from the checkpoint (no trainer; on a "
                     "GPU one launch per tick)")
     ap.add_argument("--greedy", action="store_true", help="with --fused-act: the most probable action instead of a draw")
+    ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat); one frame per decision, --ticks counts decisions")
     args = ap.parse_args(argv)
-    if args.envs < 1 or args.ticks < 1:
-        ap.error("--envs and --ticks must be >= 1")
+    if args.envs < 1 or args.ticks < 1 or args.frame_skip < 1:
+        ap.error("--envs, --ticks and --frame-skip must be >= 1")
     if args.greedy and not args.fused_act:
         ap.error("--greedy needs --fused-act")
     watch(args.map, args.envs, args.out, args.checkpoint, args.ticks, args.rays, args.seed, args.num_rays, args.max_steps,
-          fused_act=args.fused_act, greedy=args.greedy)
+          fused_act=args.fused_act, greedy=args.greedy, frame_skip=args.frame_skip)
     return 0
 
 

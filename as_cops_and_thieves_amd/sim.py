@@ -153,6 +153,24 @@ class CatSim:
                                            self._stream()), "cat_step_fused")
         return self.out
 
+    def step_repeat(self, actions: torch.Tensor, k: int, auto_reset: bool = True):
+        """Frame skip: ONE resident launch (cat_step_repeat) in which every env slot plays up to ``k`` ticks with its row of ``actions``
+        held, and stops at the tick that ends its episode (after that tick's auto-reset: the new episode is not stepped).  Returns
+        ``self.out``: observations and flags of each slot's last played tick, ``reward`` the fp32 sum of the played ticks' rewards in
+        tick order, and ``out["ticks"]`` (a persistent int32 ``[N]`` tensor, created by the first call) the ticks played, 1 .. k.
+        ``k == 1`` equals ``step_fused(actions, auto_reset=auto_reset)`` bit for bit."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"step_repeat: k must be an integer, got {k!r}")
+        if actions.dtype != torch.int32 or not actions.is_contiguous() or actions.device != self.device:
+            actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        if actions.shape != (self.N, self.A):
+            raise ValueError(f"actions must have shape {(self.N, self.A)}, got {tuple(actions.shape)}")
+        if "ticks" not in self.out:
+            self.out["ticks"] = torch.zeros((self.N,), dtype=torch.int32, device=self.device)
+        self._check(self._L.cat_step_repeat(self._h, int(k), actions.data_ptr(), int(auto_reset), C.byref(self._out_struct),
+                                            self.out["ticks"].data_ptr(), self._stream()), "cat_step_repeat")
+        return self.out
+
     def rollout_buffers(self, T: int) -> Dict[str, torch.Tensor]:
         """Caller-owned output buffers with a leading T for ``rollout_fused`` (cached per T)."""
         cache = self.__dict__.setdefault("_rollout_bufs", {})

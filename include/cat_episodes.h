@@ -16,6 +16,13 @@
  *    of two P with zeros, then x[i] += x[i + h] for h = P/2, P/4, ..., 1.  The order of the additions is the contract: the block
  *    is bit-reproducible and does not depend on the launch shape or on how the ticks were chunked into update calls.
  *
+ *  - cat_episode_windows_update: cat_episodes_update for rows that stand for SEVERAL env ticks each, as cat_step_repeat (cat_sim.h)
+ *    writes them: row t of slot n is a window of ticks[t][n] >= 1 played ticks whose reward is the window's fp32 sum and whose flags
+ *    are those of the window's last tick (the only one that can carry them).  Per row: ret_run += (double)reward, len_run +=
+ *    ticks[t][n]; everything else as above.  Lengths, the histogram, the outcome counters and the counts therefore equal those of
+ *    feeding the same ticks one by one; a return is the f64 sum of the fp32 window sums in window order, which differs from the
+ *    tick-by-tick f64 sum in the last bits.  ticks == NULL means one tick per row: cat_episodes_update itself.
+ *
  * No floating-point atomics anywhere.  Conventions as in cat_rollout.h: int status, argument checks before any device call,
  * explicit stream, caller-owned device buffers, arguments by value, no allocation and no synchronisation inside.
  */
@@ -60,6 +67,12 @@ typedef struct cat_episodes_update_args {
     cat_episodes_state s;
 } cat_episodes_update_args;
 
+/* cat_episode_windows_update: the update arguments plus the ticks each row stands for. */
+typedef struct cat_episode_windows_args {
+    cat_episodes_update_args u;
+    const int32_t *ticks;                       /* [T][N] ticks played in the row's window (>= 1), or NULL = 1 each */
+} cat_episode_windows_args;
+
 typedef struct cat_episodes_summary_block {
     int64_t episodes, cop_wins, thief_wins, timeouts;
     int64_t open_slots;                         /* slots with finished < quota; 0 without a quota */
@@ -80,6 +93,7 @@ int cat_episodes_abi_version(void);
 const char *cat_episodes_last_error(void);
 int cat_episodes_update(const cat_episodes_update_args *a, void *stream);
 int cat_episodes_summary(const cat_episodes_summary_args *a, void *stream);
+int cat_episode_windows_update(const cat_episode_windows_args *a, void *stream);   /* errors: cat_episodes_last_error */
 
 #ifdef __cplusplus
 }

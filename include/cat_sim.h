@@ -185,6 +185,27 @@ int cat_step_fused(cat_sim *sim, const int32_t *actions, uint64_t synth_tick, in
 int cat_rollout_fused(cat_sim *sim, int T, const int32_t *actions, uint64_t synth_tick0, int auto_reset,
                       const cat_outputs *out, void *stream);
 
+/* FRAME SKIP (action repeat): ONE decision of up to k ticks per env slot in ONE resident launch (the sim's rollout kernel, T = k).
+   For every env slot independently, 1 <= k <= CAT_MAX_ROLLOUT_TICKS:
+   1. The slot plays ticks j = 0, 1, ... with the SAME row of actions (DEVICE [N,A] int32, not NULL: synthetic actions are not offered
+      here).  Each tick is exactly a cat_step_fused(actions, ., auto_reset) tick of that slot; an action outside 0..3 raises
+      CAT_DEVERR_BAD_ACTION as it does there.
+   2. Hold rule: the slot stops after the first tick j* at which `terminated` is set, or after tick k - 1 if none is; the rule is checked
+      after every tick, the first included.  With auto_reset the auto-reset of tick j* happens inside that tick as in cat_step_fused and
+      the slot then does not advance: the new episode has its first observation and step_count 0, and is never stepped with the stale
+      action.  Without auto_reset the slot is left as cat_step_fused(..., 0) leaves it after j*.
+   3. Outputs: `out` addresses [N,...] buffers, the one-tick layout.  Observations, shared observations, team positions and hit_shape are
+      those of the slot's LAST played tick, and so are terminated / truncated / winner (the only tick that can carry them).  reward[n][a] is
+      the fp32 left fold ((r_0 + r_1) + r_2) + ... over the played ticks in tick order: plain fp32 adds, no fused multiply-add, no
+      discounting.  ticks (DEVICE [N] int32, or NULL): the number of ticks played, 1 .. k.  Ticks before the last store nothing.
+   4. The state afterwards is, in every field of cat_state, bit-identical to playing those ticks one launch at a time.
+   5. k == 1 is bit-identical to cat_step_fused in every output and in the state.
+   6. Asynchronous; no allocation and no synchronisation (capturable in a HIP graph); k out of range and actions == NULL are rejected with
+      CAT_ERR_BAD_ARG and a message (cat_last_error) before any device call.
+   No reference counterpart (the reference steps one tick per call). */
+int cat_step_repeat(cat_sim *sim, int k, const int32_t *actions, int auto_reset,
+                    const cat_outputs *out, int32_t *ticks, void *stream);
+
 /* Env-state access (the reference cannot checkpoint env state). D2D copies. */
 int cat_get_state(cat_sim *sim, const cat_state *dst, void *stream);
 int cat_set_state(cat_sim *sim, const cat_state *src, void *stream);
