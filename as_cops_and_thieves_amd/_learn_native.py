@@ -1,7 +1,7 @@
-"""ctypes binding of libcat_learn.so (include/cat_lstm.h, include/cat_trunk.h, ...): the LSTM recurrence and the
-convolutional trunk of the self-play learner's networks, one launch per direction each, the learner's other kernels, and the batched
-frame renderer (include/cat_render.h).  No CPU fallback inside: callers
-on a CUDA/HIP device in bf16 get these kernels or an exception."""
+"""ctypes binding of libcat_learn.so, one module per header under include/: the learner's LSTM recurrence (cat_lstm.h), convolutional trunk
+(cat_trunk.h), PPO loss / optimiser step / GAE scan (cat_ppo.h) and dense layers (cat_dense.h), the rollout tick's glue (cat_rollout.h), the
+batched frame renderer (cat_render.h), on-device episode accounting (cat_episodes.h) and the fused act tick (cat_act.h).  ``MODULES`` is the
+one table of their entries.  No CPU fallback inside: callers on a CUDA/HIP device in bf16 get these kernels or an exception."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,12 +16,41 @@ if os.environ.get("CAT_LEARN_LIB"):         # diagnostic builds (A/B of kernel v
     LIB_PATH = Path(os.environ["CAT_LEARN_LIB"]).resolve()
 SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes", "act"))
 HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes", "act"))
+INTERNAL_HEADERS = (PKG / "csrc" / "cat_learn_common.h",)   # what the sources share; not part of the C ABI, but an input of the build
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared"]
 HIDDEN = 128
-EXPORTED_SYMBOLS = ("cat_lstm_abi_version", "cat_lstm_last_error", "cat_lstm_blocks", "cat_lstm_saved_acts_bytes", "cat_lstm_saved_cell_bytes",
-                    "cat_lstm_seq_forward", "cat_lstm_seq_backward")
-TRUNK_SYMBOLS = ("cat_trunk_abi_version", "cat_trunk_last_error", "cat_trunk_out_positions", "cat_trunk_supported",
-                 "cat_trunk_backward_blocks", "cat_trunk_forward", "cat_trunk_backward", "cat_trunk_grad_finish")
+
+_ENTRY = (C.c_int, [C.c_void_p, C.c_void_p])   # int entry(const args *, void *stream): most of the library
+_QUERY = (C.c_int, [C.c_void_p])               # int query(const dims *)
+# module -> (expected ABI version, {symbol: (restype, argtypes)} in the header's order); every module also has <module>_abi_version
+# and <module>_last_error.  ``lib`` declares the library from this table and ``_check`` finds a symbol's error string through it.
+MODULES = {
+    "cat_lstm": (1, {"cat_lstm_blocks": _QUERY, "cat_lstm_saved_acts_bytes": (C.c_size_t, [C.c_void_p]),
+                     "cat_lstm_saved_cell_bytes": (C.c_size_t, [C.c_void_p]), "cat_lstm_seq_forward": _ENTRY, "cat_lstm_seq_backward": _ENTRY}),
+    "cat_trunk": (2, {"cat_trunk_out_positions": _QUERY, "cat_trunk_supported": _QUERY, "cat_trunk_backward_blocks": _QUERY,
+                      "cat_trunk_forward": _ENTRY, "cat_trunk_backward": _ENTRY, "cat_trunk_grad_finish": _ENTRY}),
+    "cat_ppo": (2, {"cat_ppo_loss_grad": _ENTRY, "cat_ppo_adam_step": _ENTRY, "cat_ppo_gae_scan": _ENTRY}),
+    "cat_dense": (2, {"cat_dense_bias_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+                      "cat_dense_act_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+                      "cat_dense_sum_chunks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                         C.c_int32, C.c_void_p]),
+                      "cat_dense_wgrad_splits": (C.c_int, [C.c_int32] * 4), "cat_dense_wgrad": _ENTRY, "cat_dense_forward": _ENTRY,
+                      "cat_dense_dgrad": _ENTRY, "cat_dense_sum_chunks2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])}),
+    "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY}),
+    "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])}),
+    "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
+                         "cat_episodes_segment_summary": _ENTRY}),
+    "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_league_step": _ENTRY}),
+}
+_MODULE_OF = {sym: mod for mod, (_, entries) in MODULES.items() for sym in entries}
+
+
+def _symbols(module: str) -> tuple:
+    return (f"{module}_abi_version", f"{module}_last_error", *MODULES[module][1])
+
+
+EXPORTED_SYMBOLS = _symbols("cat_lstm")
+TRUNK_SYMBOLS = _symbols("cat_trunk")
 
 
 class Dims(C.Structure):
@@ -68,15 +97,14 @@ class TrunkBwd(C.Structure):
                 ("part_dw1", C.c_void_p), ("part_db1", C.c_void_p), ("part_dw2", C.c_void_p), ("part_db2", C.c_void_p)]
 
 
-ROLLOUT_SYMBOLS = ("cat_rollout_abi_version", "cat_rollout_last_error", "cat_rollout_pack", "cat_rollout_sample", "cat_rollout_post")
-DENSE_SYMBOLS = ("cat_dense_abi_version", "cat_dense_last_error", "cat_dense_bias_act", "cat_dense_act_grad", "cat_dense_sum_chunks",
-                 "cat_dense_wgrad_splits", "cat_dense_wgrad", "cat_dense_forward", "cat_dense_dgrad", "cat_dense_sum_chunks2")
-PPO_SYMBOLS = ("cat_ppo_abi_version", "cat_ppo_last_error", "cat_ppo_loss_grad", "cat_ppo_adam_step", "cat_ppo_gae_scan")
-RENDER_SYMBOLS = ("cat_render_abi_version", "cat_render_last_error", "cat_render_frames")
-EPISODES_SYMBOLS = ("cat_episodes_abi_version", "cat_episodes_last_error", "cat_episodes_update", "cat_episodes_summary")
+ROLLOUT_SYMBOLS = _symbols("cat_rollout")
+DENSE_SYMBOLS = _symbols("cat_dense")
+PPO_SYMBOLS = _symbols("cat_ppo")
+RENDER_SYMBOLS = _symbols("cat_render")
+EPISODES_SYMBOLS = _symbols("cat_episodes")[:4]
 EPISODE_WINDOWS_SYMBOLS = ("cat_episode_windows_update",)     # include/cat_episodes.h: the update for rows of several env ticks
 EPISODE_SEGMENTS_SYMBOLS = ("cat_episodes_segment_summary",)  # include/cat_episodes.h: one summary block per contiguous segment of the slots
-ACT_SYMBOLS = ("cat_act_abi_version", "cat_act_last_error", "cat_act_supported", "cat_act_step", "cat_act_league_step")
+ACT_SYMBOLS = _symbols("cat_act")
 ACT_MAX_AGENTS = 8              # CAT_ACT_MAX_AGENTS
 ACT_MAX_SEGMENTS = 32           # CAT_ACT_MAX_SEGMENTS
 ACT_SAMPLE, ACT_GREEDY = 0, 1   # cat_act_args.mode
@@ -134,7 +162,7 @@ class NativeLibraryMissing(RuntimeError):
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile the kernels in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    newest = max(f.stat().st_mtime for f in SOURCES + HEADERS)
+    newest = max(f.stat().st_mtime for f in SOURCES + HEADERS + INTERNAL_HEADERS)
     stale = not LIB_PATH.exists() or LIB_PATH.stat().st_mtime < newest
     if force or stale:
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -160,90 +188,20 @@ def lib() -> C.CDLL:
                 "The bf16 learner on a GPU has no other LSTM path.")
         import torch  # noqa: F401  (torch's HIP runtime first, as in _native.lib)
         L = C.CDLL(str(LIB_PATH))
-        L.cat_lstm_abi_version.restype = C.c_int
-        L.cat_lstm_last_error.restype = C.c_char_p
-        L.cat_lstm_blocks.restype = C.c_int
-        L.cat_lstm_blocks.argtypes = [C.c_void_p]
-        for n in ("cat_lstm_saved_acts_bytes", "cat_lstm_saved_cell_bytes"):
-            getattr(L, n).restype = C.c_size_t
-            getattr(L, n).argtypes = [C.c_void_p]
-        for n in ("cat_lstm_seq_forward", "cat_lstm_seq_backward"):
-            getattr(L, n).restype = C.c_int
-            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
-        assert L.cat_lstm_abi_version() == 1
-        L.cat_trunk_abi_version.restype = C.c_int
-        L.cat_trunk_last_error.restype = C.c_char_p
-        for n in ("cat_trunk_out_positions", "cat_trunk_supported", "cat_trunk_backward_blocks"):
-            getattr(L, n).restype = C.c_int
-            getattr(L, n).argtypes = [C.c_void_p]
-        for n in ("cat_trunk_forward", "cat_trunk_backward", "cat_trunk_grad_finish"):
-            getattr(L, n).restype = C.c_int
-            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
-        assert L.cat_trunk_abi_version() == 2
-        L.cat_ppo_abi_version.restype = C.c_int
-        L.cat_ppo_last_error.restype = C.c_char_p
-        for n in ("cat_ppo_loss_grad", "cat_ppo_adam_step", "cat_ppo_gae_scan"):
-            getattr(L, n).restype = C.c_int
-            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
-        assert L.cat_ppo_abi_version() == 2
-        L.cat_dense_abi_version.restype = C.c_int
-        L.cat_dense_last_error.restype = C.c_char_p
-        L.cat_dense_bias_act.restype = C.c_int
-        L.cat_dense_bias_act.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        L.cat_dense_act_grad.restype = C.c_int
-        L.cat_dense_act_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-        L.cat_dense_sum_chunks.restype = C.c_int
-        L.cat_dense_sum_chunks.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                           C.c_int32, C.c_void_p]
-        L.cat_dense_wgrad_splits.restype = C.c_int
-        L.cat_dense_wgrad_splits.argtypes = [C.c_int32] * 4
-        L.cat_dense_wgrad.restype = C.c_int
-        L.cat_dense_wgrad.argtypes = [C.c_void_p, C.c_void_p]
-        L.cat_dense_sum_chunks2.restype = C.c_int
-        L.cat_dense_sum_chunks2.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-        for n in ("cat_dense_forward", "cat_dense_dgrad"):
-            getattr(L, n).restype = C.c_int
-            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
-        assert L.cat_dense_abi_version() == 2
-        L.cat_rollout_abi_version.restype = C.c_int
-        L.cat_rollout_last_error.restype = C.c_char_p
-        for n in ("cat_rollout_pack", "cat_rollout_sample", "cat_rollout_post"):
-            getattr(L, n).restype = C.c_int
-            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
-        assert L.cat_rollout_abi_version() == 1
-        L.cat_render_abi_version.restype = C.c_int
-        L.cat_render_last_error.restype = C.c_char_p
-        L.cat_render_frames.restype = C.c_int
-        L.cat_render_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        assert L.cat_render_abi_version() == 1
-        L.cat_episodes_abi_version.restype = C.c_int
-        L.cat_episodes_last_error.restype = C.c_char_p
-        for n in ("cat_episodes_update", "cat_episodes_summary") + EPISODE_WINDOWS_SYMBOLS + EPISODE_SEGMENTS_SYMBOLS:
-            getattr(L, n).restype = C.c_int
-            getattr(L, n).argtypes = [C.c_void_p, C.c_void_p]
-        assert L.cat_episodes_abi_version() == 1
-        L.cat_act_abi_version.restype = C.c_int
-        L.cat_act_last_error.restype = C.c_char_p
-        L.cat_act_supported.restype = C.c_int
-        L.cat_act_supported.argtypes = [C.c_void_p]
-        L.cat_act_step.restype = C.c_int
-        L.cat_act_step.argtypes = [C.c_void_p, C.c_void_p]
-        L.cat_act_league_step.restype = C.c_int
-        L.cat_act_league_step.argtypes = [C.c_void_p, C.c_void_p]
-        assert L.cat_act_abi_version() == 1
+        for module, (abi, entries) in MODULES.items():
+            getattr(L, f"{module}_last_error").restype = C.c_char_p
+            for sym, (restype, argtypes) in entries.items():
+                getattr(L, sym).restype, getattr(L, sym).argtypes = restype, argtypes
+            assert getattr(L, f"{module}_abi_version")() == abi, module
         _lib = L
     return _lib
 
 
-def _check(rc: int, what: str) -> None:
+def _check(rc: int, symbol: str) -> None:
+    """Raise on a non-zero return of entry ``symbol`` with its module's error string."""
     if rc != 0:
-        err = (lib().cat_trunk_last_error() if "trunk" in what else lib().cat_ppo_last_error() if "ppo" in what
-               else lib().cat_dense_last_error() if "dense" in what else lib().cat_rollout_last_error() if "rollout" in what
-               else lib().cat_render_last_error() if "render" in what
-               else lib().cat_episodes_last_error() if "episodes" in what
-               else lib().cat_act_last_error() if "cat_act" in what
-               else lib().cat_lstm_last_error())
-        raise RuntimeError(f"{what} failed ({rc}): {err.decode()}")
+        err = getattr(lib(), f"{_MODULE_OF[symbol]}_last_error")()
+        raise RuntimeError(f"{symbol} failed ({rc}): {err.decode()}")
 
 
 def _ptr(t) -> int:
@@ -757,7 +715,7 @@ def episodes_update(state, reward, terminated, truncated, winner, quota, max_ste
         return
     assert ticks.dtype == torch.int32 and ticks.shape == (T, N) and ticks.is_contiguous() and ticks.device == reward.device
     w = EpisodeWindows(a, ticks.data_ptr())
-    _check(lib().cat_episode_windows_update(C.byref(w), _stream()), "cat_episodes: cat_episode_windows_update")
+    _check(lib().cat_episode_windows_update(C.byref(w), _stream()), "cat_episode_windows_update")
 
 
 def episodes_summary(state, quota, block) -> None:
@@ -776,6 +734,17 @@ class EpisodesSegmentSummary(C.Structure):
                 ("quota", C.c_void_p), ("s", EpisodesState), ("out", C.c_void_p)]
 
 
+def _check_bounds(N: int, start, max_segments: int) -> None:
+    """The rules of the C entries' ``seg_start`` for S + 1 ints: 1 <= S <= max_segments, 0 first, N last, strictly increasing."""
+    S = len(start) - 1
+    if not 1 <= S <= max_segments:
+        raise ValueError(f"{S} segments: 1..{max_segments} are allowed")
+    if start[0] != 0 or start[-1] != N:
+        raise ValueError(f"the segments must begin at row 0 and end at row {N}: {start}")
+    if any(b <= a for a, b in zip(start, start[1:])):
+        raise ValueError(f"the segment bounds must be strictly increasing: {start}")
+
+
 def segment_bounds(N: int, bounds):
     """``bounds``: S + 1 row bounds of S contiguous segments of N slots, checked by the rules of ``cat_act_league_args`` (0 first, N last,
     strictly increasing, 1 <= S <= EPISODES_MAX_SEGMENTS) -> a list of ints.  Raises ValueError."""
@@ -786,13 +755,7 @@ def segment_bounds(N: int, bounds):
         raise ValueError(f"segment bounds must be a sequence of integers: {bounds!r}") from exc
     if not exact:
         raise ValueError(f"segment bounds must be integers: {list(bounds)}")
-    S = len(start) - 1
-    if not 1 <= S <= EPISODES_MAX_SEGMENTS:
-        raise ValueError(f"{S} segments: 1..{EPISODES_MAX_SEGMENTS} are allowed")
-    if start[0] != 0 or start[-1] != N:
-        raise ValueError(f"the segments must begin at row 0 and end at row {N}: {start}")
-    if any(b <= a for a, b in zip(start, start[1:])):
-        raise ValueError(f"the segment bounds must be strictly increasing: {start}")
+    _check_bounds(N, start, EPISODES_MAX_SEGMENTS)
     return start
 
 
@@ -905,15 +868,10 @@ def league_table(N: int, G: int, sets: int, seg_start, seg_set) -> LeagueTable:
     """The segment table of ``cat_act_league_args`` checked by the C entry's rules: ``seg_start`` S + 1 row bounds (0 first, N last, strictly
     increasing, 1 <= S <= ACT_MAX_SEGMENTS), ``seg_set`` [G][S] set indices in [-1, sets) (-1: uniformly random).  Raises ValueError."""
     start = [int(v) for v in seg_start]
+    _check_bounds(N, start, ACT_MAX_SEGMENTS)
     S = len(start) - 1
-    if not 1 <= S <= ACT_MAX_SEGMENTS:
-        raise ValueError(f"{S} segments: 1..{ACT_MAX_SEGMENTS} are allowed")
     if sets < 1:
         raise ValueError("the bank needs at least one parameter set")
-    if start[0] != 0 or start[-1] != N:
-        raise ValueError(f"the segments must begin at row 0 and end at row {N}: {start}")
-    if any(b <= a for a, b in zip(start, start[1:])):
-        raise ValueError(f"the segment bounds must be strictly increasing: {start}")
     table = [[int(v) for v in row] for row in seg_set]
     if len(table) != G or any(len(row) != S for row in table):
         raise ValueError(f"seg_set must be [{G}][{S}]")

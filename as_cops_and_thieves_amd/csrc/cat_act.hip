@@ -1,4 +1,4 @@
-// cat_act.hip -- libcat_learn.so, part 8: the act tick of the stacked recurrent policies in one launch (include/cat_act.h).
+// cat_act.hip -- libcat_learn.so, part 8 of 8: the act tick of the stacked recurrent policies in one launch (include/cat_act.h).
 //
 // A workgroup of four waves owns TM = 32 or 64 rows (envs) of ONE network and carries them from the env core's observation
 // buffers to the action.  Every layer is Y^T = W X^T on mfma_f32_16x16x32_bf16 with the WEIGHTS as the A operand: a lane's
@@ -19,19 +19,13 @@
 //
 // LDS: two regions that the stages reuse -- A: observation rows + conv1 image, later [f | h], later head layer 1;
 // B: conv2 output, later h' and head layer 2.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <stdint.h>
-#include <stdio.h>
-
+#include "cat_learn_common.h"
 #include "cat_act.h"
 
 namespace {
 
+CAT_LEARN_CODES(CAT_ACT);
 constexpr int BLOCK = 256, HID = CAT_ACT_HIDDEN;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 enum { A_NONE = 0, A_RELU = 1, A_TANH = 2 };
 
@@ -43,8 +37,6 @@ template <int R> struct Geo {
     static constexpr size_t lds_bytes(int tm) { return (size_t)tm * (A_LD + B_LD) * 2; }
 };
 
-__device__ __forceinline__ float sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 template <int ACT> __device__ __forceinline__ float act_fwd(float x)
 {
     if (ACT == A_RELU) return fmaxf(x, 0.0f);
@@ -120,20 +112,20 @@ __device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, con
     const __bf16 *hw1 = (const __bf16 *)a.p.head1_w + po, *hb1 = (const __bf16 *)a.p.head1_b + po;
     const __bf16 *hw2 = (const __bf16 *)a.p.head2_w + po, *hb2 = (const __bf16 *)a.p.head2_b + po;
 
-    // ---- the observation rows: [distance (R) | type (R)], scaled, bf16 (cat_rollout_pack's policy row); rows >= rend are zero
+    // ---- the observation rows: [distance (R) | type (R)] of obs_scaled elements, as cat_rollout_pack's policy row; rows >= rend are zero
     {
         const __half *od = (const __half *)a.obs_distance;
         const uint8_t *ot = (const uint8_t *)a.obs_type;
         for (int i = tid; i < TM * R; i += BLOCK) {
             const int m = i / R, rr = i - m * R, n = row0 + m;
-            float dv = 0.0f, tv = 0.0f;
+            __bf16 dv = (__bf16)0.0f, tv = (__bf16)0.0f;
             if (n < rend) {
                 const size_t o = ((size_t)n * A + ai) * R + rr;
-                dv = __half2float(od[o]) * a.distance_scale;
-                tv = (float)ot[o] * a.type_scale;
+                dv = obs_scaled(od[o], a.distance_scale);
+                tv = obs_scaled(ot[o], a.type_scale);
             }
-            xin[m * G::XIN_LD + rr] = (__bf16)dv;
-            xin[m * G::XIN_LD + R + rr] = (__bf16)tv;
+            xin[m * G::XIN_LD + rr] = dv;
+            xin[m * G::XIN_LD + R + rr] = tv;
         }
     }
     // ---- the convolutions' weights of this wave, in registers for the whole trunk
@@ -287,11 +279,7 @@ __device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, con
         const bf16x4 zb = __builtin_convertvector(zf, bf16x4);
         const f32x4 z = __builtin_convertvector(zb, f32x4);
         const size_t sidx = (size_t)g * N + n;
-        // cat_rollout_sample's rule on the bf16 logits
-        const float zmax = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-        const float e0 = __expf(z[0] - zmax), e1 = __expf(z[1] - zmax), e2 = __expf(z[2] - zmax), e3 = __expf(z[3] - zmax);
-        float sum = 0.f;
-        sum += e0; sum += e1; sum += e2; sum += e3;
+        const Cat4 cm = cat4_masses(z);                 // on the bf16 logits, as cat_rollout_sample
         int act;
         if (a.mode == CAT_ACT_GREEDY) {
             act = 0;
@@ -300,13 +288,12 @@ __device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, con
             if (z[2] > best) { best = z[2]; act = 2; }
             if (z[3] > best) { best = z[3]; act = 3; }
         } else {
-            const float u = uni[n] * sum;             // inverse CDF on the unnormalised masses
-            act = (u >= e0) + (u >= e0 + e1) + (u >= e0 + e1 + e2);
+            act = cat4_draw(cm, uni[n]);
         }
         const float zact = act == 0 ? z[0] : act == 1 ? z[1] : act == 2 ? z[2] : z[3];
         a.actions[(size_t)n * A + ai] = act;
         if (a.logits_out) *(bf16x4 *)((__bf16 *)a.logits_out + 4 * sidx) = zb;
-        if (a.logp_out) a.logp_out[sidx] = zact - zmax - __logf(sum);
+        if (a.logp_out) a.logp_out[sidx] = cat4_sampled_logp(cm, zact);
     }
 }
 
@@ -335,13 +322,6 @@ __global__ __launch_bounds__(BLOCK) void act_league_kernel(const cat_act_league_
     act_rows<R, MT>(a.base, g, row0, row0 + TM < send ? row0 + TM : send, (size_t)(set < 0 ? 0 : set) * a.base.p.stride, set < 0);
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char *who, const char *msg)
-{
-    snprintf(g_err, sizeof g_err, "%s: %s", who, msg);
-    return code;
-}
-
 bool dims_ok(const cat_act_dims &d)
 {
     return d.G >= 1 && d.G <= CAT_ACT_MAX_AGENTS && d.N >= 1 && d.A >= 1 && d.A <= CAT_ACT_MAX_AGENTS && (d.R == 64 || d.R == 90);
@@ -351,8 +331,7 @@ bool dims_ok(const cat_act_dims &d)
 int check_args(const cat_act_args *a, const char *who, bool need_params)
 {
     if (!a || !dims_ok(a->d)) return fail(CAT_ACT_ERR_BAD_ARG, who, "bad dimensions (G 1..8, A 1..8, N >= 1, R 64 or 90)");
-    for (int g = 0; g < a->d.G; ++g)
-        if (a->agent[g] < 0 || a->agent[g] >= a->d.A) return fail(CAT_ACT_ERR_BAD_ARG, who, "agent index out of range");
+    if (!agents_ok(a->agent, a->d.G, a->d.A)) return fail(CAT_ACT_ERR_BAD_ARG, who, "agent index out of range");
     if ((a->mode != CAT_ACT_SAMPLE && a->mode != CAT_ACT_GREEDY) || (a->random_mask >> a->d.G) != 0 ||
         (a->row_tile != 0 && a->row_tile != 32 && a->row_tile != 64))
         return fail(CAT_ACT_ERR_BAD_ARG, who, "bad mode, random_mask or row_tile");
@@ -376,8 +355,7 @@ template <int R, int MT, typename Args> int launch(void (*kernel)(const Args), c
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return fail(CAT_ACT_ERR_HIP, who, "hipFuncSetAttribute failed");
     hipLaunchKernelGGL(kernel, dim3(tiles, G), dim3(BLOCK), lds, stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_ACT_OK : fail(CAT_ACT_ERR_HIP, who, hipGetErrorString(e));
+    return launched(who);
 }
 
 }   // namespace

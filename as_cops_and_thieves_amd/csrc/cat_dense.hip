@@ -1,23 +1,20 @@
-// cat_dense.hip -- libcat_learn.so, part 4: bias + activation in place, and activation derivative + bias gradient
-// (include/cat_dense.h).  Bandwidth-bound passes over [G][M][out] bf16: 8-byte accesses, consecutive threads on
+// cat_dense.hip -- libcat_learn.so, part 4 of 8: the dense layers (include/cat_dense.h) -- bias + activation in place, activation
+// derivative + bias gradient, the chunk sums, and further down the weight-gradient, forward and input-gradient GEMMs.  The first are
+// bandwidth-bound passes over [G][M][out] bf16: 8-byte accesses, consecutive threads on
 // consecutive column groups; the column sums are two-stage (per-chunk partial sums in registers, LDS across the row
 // lanes of a block, chunks added up by the caller).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
+#include "cat_learn_common.h"
 #include "cat_dense.h"
 
 namespace {
 
+CAT_LEARN_CODES(CAT_DENSE);
 constexpr int BLOCK = 256;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 __device__ __forceinline__ float act_fwd(float x, int act)
 {
     if (act == CAT_ACT_RELU) return fmaxf(x, 0.0f);
-    if (act == CAT_ACT_TANH) return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x));
+    if (act == CAT_ACT_TANH) return tanh_fast(x);
     return x;
 }
 __device__ __forceinline__ float act_der(float y, int act)   // from the activation's output
@@ -150,8 +147,6 @@ __global__ __launch_bounds__(BLOCK) void sum_chunks_kernel(SumJob j0, SumJob j1)
 // {16+4q..16+4q+3} of the 32-row step (the same permutation for A and B, so the product is unchanged): with a row
 // stride of 288 B the two groups of a 32-lane half then sit in disjoint banks.
 constexpr int WG_BM = 128, WG_BN = 128, WG_BK = 32, WG_LD = 144;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using s16x4 = __attribute__((ext_vector_type(4))) short;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 __device__ __forceinline__ bf16x8 tr_frag(const __bf16 *tile, int row0, int col0)
@@ -407,12 +402,6 @@ __global__ __launch_bounds__(BLOCK) void dense_dgrad_kernel(const cat_dense_gemm
     }
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char *msg)
-{
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return code;
-}
 bool dims_ok(const cat_dense_dims *d)
 {
     return d && d->G > 0 && d->G <= 65535 && d->M > 0 && (d->out == 1 || (d->out % 4 == 0 && d->out > 0 && d->out <= CAT_DENSE_MAX_OUT)) &&
@@ -432,8 +421,7 @@ extern "C" int cat_dense_bias_act(const cat_dense_dims *d, void *y, const void *
     size_t blocks = (work + BLOCK - 1) / BLOCK;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(bias_act_kernel, dim3((unsigned)blocks, d->G), dim3(BLOCK), 0, (hipStream_t)stream, *d, (__bf16 *)y, (const __bf16 *)bias, sb_g);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_DENSE_OK : fail(CAT_DENSE_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_dense_act_grad(const cat_dense_dims *d, const void *d_y, const void *y, void *g_out, float *partial, int32_t chunks,
@@ -447,8 +435,7 @@ extern "C" int cat_dense_act_grad(const cat_dense_dims *d, const void *d_y, cons
     const int gy = (groups + BLOCK - 1) / BLOCK;
     hipLaunchKernelGGL(act_grad_kernel, dim3(chunks, gy, d->G), dim3(BLOCK), 0, (hipStream_t)stream, *d, (const __bf16 *)d_y,
                        (const __bf16 *)y, (__bf16 *)g_out, partial);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_DENSE_OK : fail(CAT_DENSE_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_dense_sum_chunks(const float *partial, int32_t G, int32_t chunks, int32_t n, void *dst0, int64_t sd0_g, void *dst1,
@@ -468,8 +455,7 @@ extern "C" int cat_dense_sum_chunks2(const cat_dense_sum_job *a, const cat_dense
     j1.blocks = 0;
     if (b) j1 = SumJob{b->partial, b->chunks, b->n, (__bf16 *)b->dst0, (__bf16 *)b->dst1, b->sd0_g, b->sd1_g, b->accumulate, (b->n + 31) / 32};
     hipLaunchKernelGGL(sum_chunks_kernel, dim3(j0.blocks + (b ? j1.blocks : 0), G), dim3(BLOCK), 0, (hipStream_t)stream, j0, j1);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_DENSE_OK : fail(CAT_DENSE_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_dense_wgrad_splits(int32_t G, int32_t K, int32_t M, int32_t N)
@@ -493,8 +479,7 @@ extern "C" int cat_dense_wgrad(const cat_dense_wgrad_args *a, void *stream)
         return fail(CAT_DENSE_ERR_BAD_ARG, "cat_dense_wgrad: the second input needs N1 > 0, its slabs and an aligned buffer");
     const int tiles = ((a->M + WG_BM - 1) / WG_BM) * ((a->N + WG_BN - 1) / WG_BN + (a->b1 ? (a->N1 + WG_BN - 1) / WG_BN : 0));
     hipLaunchKernelGGL(wgrad_kernel, dim3(tiles, a->splits, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_DENSE_OK : fail(CAT_DENSE_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 static int gemm_args_ok(const cat_dense_gemm_args *a)
@@ -509,8 +494,7 @@ extern "C" int cat_dense_forward(const cat_dense_gemm_args *a, void *stream)
         return fail(CAT_DENSE_ERR_BAD_ARG, "cat_dense_forward: bad dimensions (K % 8), NULL or misaligned buffer");
     const int tiles = ((a->M + WG_BM - 1) / WG_BM) * ((a->N + WG_BN - 1) / WG_BN);
     hipLaunchKernelGGL(dense_fwd_kernel, dim3(tiles, 1, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_DENSE_OK : fail(CAT_DENSE_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_dense_dgrad(const cat_dense_gemm_args *a, void *stream)
@@ -519,6 +503,5 @@ extern "C" int cat_dense_dgrad(const cat_dense_gemm_args *a, void *stream)
         return fail(CAT_DENSE_ERR_BAD_ARG, "cat_dense_dgrad: bad dimensions (K % 8), NULL or misaligned buffer");
     const int tiles = ((a->M + WG_BM - 1) / WG_BM) * ((a->K + 127) / 128);
     hipLaunchKernelGGL(dense_dgrad_kernel, dim3(tiles, 1, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_DENSE_OK : fail(CAT_DENSE_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }

@@ -1,11 +1,9 @@
-// cat_episodes.hip -- libcat_learn.so, part 7: episode accounting on the device (include/cat_episodes.h).
+// cat_episodes.hip -- libcat_learn.so, part 7 of 8: episode accounting on the device (include/cat_episodes.h).
 // A few bytes per env-tick and a few hundred bytes of state per slot: what matters is that the f64 sums are formed in a fixed
 // order (tick order inside a slot, a halving tree across the slots) and that each entry is ONE capturable launch.
-#include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdint.h>
-#include <stdio.h>
 
+#include "cat_learn_common.h"
 #include "cat_episodes.h"
 
 // ret_sq += r * r is a multiply and an add, as NumPy does it (no fused multiply-add): this file only, as in cat_render.hip
@@ -13,6 +11,7 @@
 
 namespace {
 
+CAT_LEARN_CODES(CAT_EPISODES);
 constexpr int UBLOCK = 64;      // update: one wave per workgroup, so that a few thousand slots spread over as many CUs as they can
 constexpr int UNROLL = 8;       // update: ticks whose loads are issued together before the serial walk over them
 constexpr int SBLOCK = 1024;    // summary: ONE workgroup (per segment); the last ten levels of the halving tree run through its LDS
@@ -179,12 +178,6 @@ __global__ __launch_bounds__(SBLOCK) void episodes_segment_summary_kernel(const 
     summarise_slots(s, a.quota ? a.quota + lo : nullptr, n, a.A, a.out + blockIdx.x);
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char *msg)
-{
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return code;
-}
 
 bool state_complete(const cat_episodes_state &s)
 {
@@ -219,8 +212,7 @@ static int launch_update(const cat_episodes_update_args *a, const int32_t *ticks
         break;
     }
 #undef CAT_EP_LAUNCH
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_EPISODES_OK : fail(CAT_EPISODES_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_episodes_update(const cat_episodes_update_args *a, void *stream)
@@ -240,8 +232,7 @@ extern "C" int cat_episodes_summary(const cat_episodes_summary_args *a, void *st
         return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_summary: bad dimensions");
     if (!a->out || !state_complete(a->s)) return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_summary: a required buffer is NULL");
     hipLaunchKernelGGL(episodes_summary_kernel, dim3(1), dim3(SBLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_EPISODES_OK : fail(CAT_EPISODES_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_episodes_segment_summary(const cat_episodes_segment_summary_args *a, void *stream)
@@ -257,6 +248,5 @@ extern "C" int cat_episodes_segment_summary(const cat_episodes_segment_summary_a
             return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_segment_summary: bad segments: seg_start must be strictly increasing");
     if (!a->out || !state_complete(a->s)) return fail(CAT_EPISODES_ERR_BAD_ARG, "cat_episodes_segment_summary: a required buffer is NULL");
     hipLaunchKernelGGL(episodes_segment_summary_kernel, dim3((unsigned)a->S), dim3(SBLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_EPISODES_OK : fail(CAT_EPISODES_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }

@@ -1,4 +1,4 @@
-// cat_lstm.hip -- libcat_learn.so: the LSTM recurrence of the role-stacked self-play learner on MI355X (gfx950).
+// cat_lstm.hip -- libcat_learn.so, part 1 of 8: the LSTM recurrence of the role-stacked self-play learner on MI355X (gfx950).
 //
 // What it replaces (include/cat_lstm.h): per BPTT step a batched GEMM + the fused gate kernel + the episode-start
 // masks forward, the gate gradient + a batched GEMM + masks backward -- about forty ~5 us launches per step and
@@ -18,14 +18,12 @@
 //     lane order -- fully coalesced, read back by the same lanes.
 //
 // Backward: d h_{t-1}^T [H x 16] = W_hh^T [H x 4H] * d gates^T; the A operand is W_hh^T gathered once per launch.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
+#include "cat_learn_common.h"
 #include "cat_lstm.h"
 
 namespace {
 
+CAT_LEARN_CODES(CAT_LSTM);
 #ifndef CAT_LSTM_WAVES
 #define CAT_LSTM_WAVES 8
 #endif
@@ -34,16 +32,10 @@ constexpr int HH = H / (16 * NW);                    // 16-unit groups of hidden
 static_assert(HH * 16 * NW == H && HH >= 1, "the waves of a workgroup split the hidden units in groups of 16");
 constexpr int HPAD = H + 8, GPAD = H4 + 8;          // LDS row strides (bf16): 272 B / 1040 B -> 16 rows hit 64 distinct banks
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 __device__ __forceinline__ f32x4 widen(bf16x4 v) { return __builtin_convertvector(v, f32x4); }
 __device__ __forceinline__ bf16x4 narrow(f32x4 v) { return __builtin_convertvector(v, bf16x4); }
 __device__ __forceinline__ bf16x4 zero4() { return narrow(f32x4{0.f, 0.f, 0.f, 0.f}); }
-
-__device__ __forceinline__ float sigmoidf(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
 // index (in bf16 elements) of a lane's 4-vector inside the saved buffers
 __device__ __forceinline__ size_t acts_index(int t, int g, int G, int nblk, int blk, int w, int tile, int lane)
@@ -353,13 +345,6 @@ __global__ __launch_bounds__(NW *LANES) void lstm_seq_bwd_kernel(const cat_lstm_
     }
 }
 
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *msg)
-{
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return code;
-}
 
 bool dims_ok(const cat_lstm_dims &d) { return d.G > 0 && d.G <= 65535 && d.T > 0 && d.T <= CAT_LSTM_MAX_T && d.B > 0; }
 bool aligned(const void *p, size_t a) { return ((uintptr_t)p % a) == 0; }
@@ -403,8 +388,7 @@ extern "C" int cat_lstm_seq_forward(const cat_lstm_fwd *a, void *stream)
         const int rounds = (nb * a->d.G + 511) / 512;      // two 4-wave workgroups per CU are resident
         hipLaunchKernelGGL((lstm_seq_fwd_kernel<false, 4>), dim3((nb + rounds - 1) / rounds, a->d.G), dim3(4 * LANES), 0, (hipStream_t)stream, *a);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_LSTM_OK : fail(CAT_LSTM_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_lstm_seq_backward(const cat_lstm_bwd *a, void *stream)
@@ -417,6 +401,5 @@ extern "C" int cat_lstm_seq_backward(const cat_lstm_bwd *a, void *stream)
         !aligned(a->d_h0, 8) || !aligned(a->d_c0, 8) || !aligned(a->saved_acts, 8) || !aligned(a->saved_cell, 8) || !aligned(a->part_dbias, 16))
         return fail(CAT_LSTM_ERR_BAD_ARG, "cat_lstm_seq_backward: misaligned buffer or stride");
     hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3(blocks_of(a->d), a->d.G), dim3(NW * LANES), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_LSTM_OK : fail(CAT_LSTM_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }

@@ -1,22 +1,18 @@
-// cat_ppo.hip -- libcat_learn.so, part 3: PPO loss + gradient and the optimiser step (include/cat_ppo.h).
+// cat_ppo.hip -- libcat_learn.so, part 3 of 8: PPO loss + gradient, the optimiser step and the GAE scan (include/cat_ppo.h).
 //
-// Both are a few flops per element over at most a few million elements: as library elementwise kernels they are
+// The first two are a few flops per element over at most a few million elements: as library elementwise kernels they are
 // ~110 launches of ~5 us per minibatch step inside the replayed HIP graph (each a dependent graph node), about a tenth
 // of the step.  Here: one launch for the loss, its four per-agent statistics and the gradient w.r.t. logits and
 // values (the derivative is written out analytically, no autograd graph for this part), and two launches for the
 // gradient-norm clip + masked Adam + bf16 refresh.  Reductions are two-stage (per-block partial sums, added up by the
 // consumer), never a semaphore-style single-pass reduction.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
+#include "cat_learn_common.h"
 #include "cat_ppo.h"
 
 namespace {
 
+CAT_LEARN_CODES(CAT_PPO);
 constexpr int BLOCK = 256;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // sum of v over the block; valid in thread 0
 template <int N>
@@ -46,11 +42,9 @@ __global__ __launch_bounds__(BLOCK) void ppo_loss_kernel(const cat_ppo_loss a)
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < M; i += gridDim.x * BLOCK) {
         const size_t s = base + i;
         const f32x4 z = __builtin_convertvector(*(const bf16x4 *)((const __bf16 *)a.logits + 4 * s), f32x4);
-        const float zmax = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-        float e[4], lp[4], p[4], sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { e[j] = __expf(z[j] - zmax); sum += e[j]; }
-        const float lse = zmax + __logf(sum), rs = 1.0f / sum;
+        const Cat4 m = cat4_masses(z);
+        const float e[4] = {m.e0, m.e1, m.e2, m.e3}, lse = cat4_loss_lse(m), rs = 1.0f / m.sum;
+        float lp[4], p[4];
         float ent = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { lp[j] = z[j] - lse; p[j] = e[j] * rs; ent -= p[j] * lp[j]; }
@@ -150,12 +144,6 @@ __global__ __launch_bounds__(BLOCK) void gae_kernel(const cat_ppo_gae a)
     }
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char *msg)
-{
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return code;
-}
 
 }   // namespace
 
@@ -171,8 +159,7 @@ extern "C" int cat_ppo_loss_grad(const cat_ppo_loss *a, void *stream)
     if (((uintptr_t)a->logits % 8) || ((uintptr_t)a->d_logits % 8))
         return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_loss_grad: logits must be 8-byte aligned");
     hipLaunchKernelGGL(ppo_loss_kernel, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_PPO_OK : fail(CAT_PPO_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_ppo_gae_scan(const cat_ppo_gae *a, void *stream)
@@ -181,8 +168,7 @@ extern "C" int cat_ppo_gae_scan(const cat_ppo_gae *a, void *stream)
     if (!a->rewards || !a->values || !a->dones || !a->last_values || !a->adv || !a->ret)
         return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_gae_scan: a required buffer is NULL");
     hipLaunchKernelGGL(gae_kernel, dim3((a->N + BLOCK - 1) / BLOCK, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_PPO_OK : fail(CAT_PPO_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_ppo_adam_step(const cat_ppo_adam *a, void *stream)
@@ -193,6 +179,5 @@ extern "C" int cat_ppo_adam_step(const cat_ppo_adam *a, void *stream)
         return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_adam_step: a required buffer is NULL");
     hipLaunchKernelGGL(grad_norm_kernel, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
     hipLaunchKernelGGL(adam_kernel, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_PPO_OK : fail(CAT_PPO_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }

@@ -1,4 +1,4 @@
-// cat_render.hip -- libcat_learn.so, part 6: batched rgb_array frames on MI355X (gfx950).  include/cat_render.h has the interface and
+// cat_render.hip -- libcat_learn.so, part 6 of 8: batched rgb_array frames on MI355X (gfx950).  include/cat_render.h has the interface and
 // the pixel contract; as_cops_and_thieves_amd/render.py (render_frame_reference) is its NumPy statement, byte for byte.
 //
 // One workgroup draws one TX x TY tile of one frame.  The frame is x-major, [width][height][3], so a column x is a contiguous run of
@@ -12,15 +12,14 @@
 // hip-clang does by default: the pragma below turns it off for this file (and only here: the library's other kernels keep their flags).
 #pragma clang fp contract(off)
 
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
-#include <stdio.h>
 
+#include "cat_learn_common.h"
 #include "cat_render.h"
 
 namespace {
 
+CAT_LEARN_CODES(CAT_RENDER);
 constexpr int BLOCK = 256, WAVES = BLOCK / 64;
 constexpr int LANES_Y = 16, PIX = 4, ROWS = 2;            // 16 lanes x 4 pixels along y; each thread draws 2 columns
 constexpr int TY = LANES_Y * PIX;                         // 64 pixels along y per tile
@@ -263,12 +262,7 @@ __global__ __launch_bounds__(BLOCK) void render_tiles_kernel(const cat_render_sc
     }
 }
 
-thread_local char g_err[256] = "";
-int fail(const char *msg)
-{
-    snprintf(g_err, sizeof g_err, "cat_render_frames: %s", msg);
-    return CAT_RENDER_ERR_BAD_ARG;
-}
+int fail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_frames", msg); }
 
 }   // namespace
 
@@ -308,10 +302,5 @@ extern "C" int cat_render_frames(const cat_render_scene *sc, const cat_render_ar
     const long long blocks = tiles_x * tiles_y * a->F;
     if (blocks > INT32_MAX) return fail("too many frames for one launch");
     hipLaunchKernelGGL(render_tiles_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, *sc, *a, (int)tiles_x, (int)tiles_y);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "cat_render_frames: %s", hipGetErrorString(e));
-        return CAT_RENDER_ERR_HIP;
-    }
-    return CAT_RENDER_OK;
+    return launched("cat_render_frames");
 }

@@ -1,4 +1,4 @@
-// cat_trunk.hip -- libcat_learn.so, part 2: Conv1d(C,64,5,s2) -> ReLU -> Conv1d(64,32,5,s3) -> ReLU of the learner's
+// cat_trunk.hip -- libcat_learn.so, part 2 of 8: Conv1d(C,64,5,s2) -> ReLU -> Conv1d(64,32,5,s3) -> ReLU of the learner's
 // role-stacked networks, forward and backward, on MI355X (gfx950).  include/cat_trunk.h has the interface.
 //
 // Why a kernel: as library GEMMs the two convolutions are either im2col copies of hundreds of MB or dense GEMMs on the
@@ -16,22 +16,16 @@
 //     forms the weight gradients as products whose inner index is (sample, position): the operands it needs sample-
 //     contiguous are written to LDS in [column][sample] order by the passes that produce them.  Weight and bias
 //     gradients accumulate in registers over all tiles of the workgroup and leave as one fp32 slab per workgroup.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-
+#include "cat_learn_common.h"
 #include "cat_trunk.h"
 
 namespace {
 
+CAT_LEARN_CODES(CAT_TRUNK);
 constexpr int C1 = CAT_TRUNK_C1, C2 = CAT_TRUNK_C2, KW = 5, TS = CAT_TRUNK_TILE, NW = 4, LANES = 64;
 constexpr int WIN2 = KW * C1;                 // 320: the second convolution's window in the (position, channel) row
 constexpr int LDS_LIMIT = 160 * 1024;
 
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using s16x4 = __attribute__((ext_vector_type(4))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 __device__ __forceinline__ bf16x4 narrow(f32x4 v) { return __builtin_convertvector(v, bf16x4); }
 __device__ __forceinline__ f32x4 relu4(f32x4 v)
@@ -443,12 +437,6 @@ __global__ __launch_bounds__(256) void trunk_finish_kernel(const cat_trunk_finis
     *dst = (__bf16)(a.accumulate ? s + (float)*dst : s);
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char *msg)
-{
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return code;
-}
 
 int g_cus = 0;
 int compute_units()
@@ -514,8 +502,7 @@ extern "C" int cat_trunk_forward(const cat_trunk_fwd *a, void *stream)
         lds_set = lds;
     }
     hipLaunchKernelGGL(trunk_fwd_kernel, dim3(fwd_blocks(a->d), a->d.G), dim3(NW * LANES), lds, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_TRUNK_OK : fail(CAT_TRUNK_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_trunk_backward(const cat_trunk_bwd *a, void *stream)
@@ -537,8 +524,7 @@ extern "C" int cat_trunk_backward(const cat_trunk_bwd *a, void *stream)
         lds_set = lds;
     }
     hipLaunchKernelGGL(trunk_bwd_kernel, dim3(bwd_blocks(a->d), a->d.G), dim3(NWB * LANES), lds, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_TRUNK_OK : fail(CAT_TRUNK_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
 
 extern "C" int cat_trunk_grad_finish(const cat_trunk_finish_args *a, void *stream)
@@ -548,6 +534,5 @@ extern "C" int cat_trunk_grad_finish(const cat_trunk_finish_args *a, void *strea
         return fail(CAT_TRUNK_ERR_BAD_ARG, "cat_trunk_grad_finish: a required buffer is NULL");
     const int n = C1 * KW * a->d.C + C1 + C2 * WIN2 + C2;
     hipLaunchKernelGGL(trunk_finish_kernel, dim3((n + 255) / 256, a->d.G), dim3(256), 0, (hipStream_t)stream, *a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CAT_TRUNK_OK : fail(CAT_TRUNK_ERR_HIP, hipGetErrorString(e));
+    return launched();
 }
