@@ -40,7 +40,7 @@ MODULES = {
     "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])}),
     "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
                          "cat_episodes_segment_summary": _ENTRY}),
-    "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_league_step": _ENTRY}),
+    "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_collect_step": _ENTRY, "cat_act_league_step": _ENTRY}),
 }
 _MODULE_OF = {sym: mod for mod, (_, entries) in MODULES.items() for sym in entries}
 
@@ -801,6 +801,13 @@ class ActArgs(C.Structure):
                 ("keep", C.c_void_p), ("uniform", C.c_void_p), ("actions", C.c_void_p), ("logits_out", C.c_void_p), ("logp_out", C.c_void_p)]
 
 
+class ActCollectArgs(C.Structure):
+    """include/cat_act.h cat_act_collect_args."""
+    _fields_ = [("base", ActArgs), ("n_cops", C.c_int32), ("first_agent_state", C.c_int32), ("shared_distance", C.c_void_p), ("shared_type", C.c_void_p),
+                ("policy_in", C.c_void_p), ("sp_g", C.c_int64), ("sp_n", C.c_int64), ("value_in", C.c_void_p), ("sv_g", C.c_int64), ("sv_n", C.c_int64),
+                ("act_out", C.c_void_p), ("sa_g", C.c_int64), ("logp_out", C.c_void_p), ("sl_g", C.c_int64), ("h0_out", C.c_void_p), ("c0_out", C.c_void_p)]
+
+
 class ActLeagueArgs(C.Structure):
     """include/cat_act.h cat_act_league_args."""
     _fields_ = [("base", ActArgs), ("S", C.c_int32), ("sets", C.c_int32), ("seg_start", C.c_int32 * (ACT_MAX_SEGMENTS + 1)),
@@ -853,6 +860,34 @@ def _act_args(raw, agent_indices, params, h, c, keep, uniform, actions, distance
     return ActArgs(ActDims(G, N, A, R), (C.c_int32 * ACT_MAX_AGENTS)(*agent_indices), ACT_GREEDY if greedy else ACT_SAMPLE, int(random_mask), int(row_tile),
                    distance_scale, type_scale, 0, od.data_ptr(), ot.data_ptr(), p, h.data_ptr(), c.data_ptr(), _ptr(keep), uniform.data_ptr(),
                    actions.data_ptr(), _ptr(logits_out), _ptr(logp_out))
+
+
+def act_collect_step(raw, agent_indices, params, h, c, keep, uniform, actions, n_cops: int, first_agent_state: bool, policy_in, value_in, act_out,
+                     logp_out, h0_out=None, c0_out=None, distance_scale: float = 1.0, type_scale: float = 1.0, logits_out=None, base_logp_out=None,
+                     row_tile: int = 0) -> None:
+    """``act_step`` (sampled, no random agents) that also writes what a rollout keeps of the tick, in one launch (include/cat_act.h,
+    ``cat_act_collect_step``).  raw additionally holds shared_distance f16 / shared_type u8 [N, 2, R]; policy_in bf16 [G, N, 2R] and value_in bf16
+    [G, N, 4R]: views with contiguous rows whose outer strides are multiples of 4 elements (``rollout_pack``'s rows); act_out int64 / logp_out fp32
+    [G, N] row-strided views (``rollout_sample``'s); h0_out, c0_out bf16 [G, N, 128] contiguous, both or neither: h and c as they stood before the
+    tick.  ``logits_out`` / ``base_logp_out``: ``act_step``'s optional contiguous outputs."""
+    import torch
+    sd, st = raw["shared_distance"], raw["shared_type"]
+    a = ActCollectArgs()
+    a.base = _act_args(raw, agent_indices, params, h, c, keep, uniform, actions, distance_scale, type_scale, False, 0, logits_out, base_logp_out, row_tile)
+    G, N, R = a.base.d.G, a.base.d.N, a.base.d.R
+    assert sd.dtype == torch.float16 and st.dtype == torch.uint8 and sd.shape == st.shape == (N, 2, R) and sd.is_contiguous() and st.is_contiguous()
+    for t, w in ((policy_in, 2 * R), (value_in, 4 * R)):
+        assert t.dtype == torch.bfloat16 and t.shape == (G, N, w) and t.stride(2) == 1
+    assert act_out.dtype == torch.int64 and act_out.shape == (G, N) and act_out.stride(1) == 1
+    assert logp_out.dtype == torch.float32 and logp_out.shape == (G, N) and logp_out.stride(1) == 1
+    for t in (h0_out, c0_out):
+        assert t is None or (t.dtype == torch.bfloat16 and t.shape == (G, N, HIDDEN) and t.is_contiguous())
+    a.n_cops, a.first_agent_state, a.shared_distance, a.shared_type = int(n_cops), 1 if first_agent_state else 0, sd.data_ptr(), st.data_ptr()
+    a.policy_in, a.sp_g, a.sp_n = policy_in.data_ptr(), policy_in.stride(0), policy_in.stride(1)
+    a.value_in, a.sv_g, a.sv_n = value_in.data_ptr(), value_in.stride(0), value_in.stride(1)
+    a.act_out, a.sa_g, a.logp_out, a.sl_g = act_out.data_ptr(), act_out.stride(0), logp_out.data_ptr(), logp_out.stride(0)
+    a.h0_out, a.c0_out = _ptr(h0_out) or None, _ptr(c0_out) or None
+    _check(lib().cat_act_collect_step(C.byref(a), _stream()), "cat_act_collect_step")
 
 
 class LeagueTable:

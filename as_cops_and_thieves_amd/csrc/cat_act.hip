@@ -25,6 +25,7 @@
 namespace {
 
 CAT_LEARN_CODES(CAT_ACT);
+static_assert(sizeof(cat_act_args) == 280 && sizeof(cat_act_collect_args) == 400, "the layouts the ctypes mirror pins");
 constexpr int BLOCK = 256, HID = CAT_ACT_HIDDEN;
 
 enum { A_NONE = 0, A_RELU = 1, A_TANH = 2 };
@@ -78,8 +79,11 @@ __device__ __forceinline__ void layer(const __bf16 *W, const __bf16 *bias, int n
 // The chain for the rows row0 .. rend - 1 (at most TM of them) of policy g: the parameters at element offset po of every block, or no
 // network at all where ``random``.  Rows at and beyond rend are neither read nor written (their LDS images are zero): in the league
 // form they belong to another segment, whose workgroup updates them in place.
-template <int R, int MT>
-__device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, const int row0, const int rend, const size_t po, const bool random)
+// COLLECT (cat_act_collect_step): ``x`` names the rollout's buffers and the same pass also stores the packed input rows, the state as it
+// stood before the tick and the action / log-probability where the rollout keeps them; nothing else of the chain changes.
+template <int R, int MT, bool COLLECT = false>
+__device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, const int row0, const int rend, const size_t po, const bool random,
+                                         const cat_act_collect_args *x = nullptr)
 {
     using G = Geo<R>;
     constexpr int TM = 16 * MT;
@@ -127,6 +131,27 @@ __device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, con
             xin[m * G::XIN_LD + rr] = dv;
             xin[m * G::XIN_LD + R + rr] = tv;
         }
+        if constexpr (COLLECT) {
+            // the critic's rows, cat_rollout_pack's: [shared distance | shared type | distance | type] of agent si and its team, four
+            // consecutive elements (8 bytes) per store; with R = 90 the four may come from two quarters of the row
+            const int si = x->first_agent_state ? 0 : ai, team = si < x->n_cops ? 0 : 1;
+            const __half *sd = (const __half *)x->shared_distance;
+            const uint8_t *st = (const uint8_t *)x->shared_type;
+            __bf16 *vg = (__bf16 *)x->value_in + (size_t)g * x->sv_g;
+            for (int i = tid; i < TM * R; i += BLOCK) {
+                const int m = i / R, k = i - m * R, n = row0 + m;
+                if (n >= rend) continue;
+                bf16x4 v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int e = 4 * k + j, seg = e / R, rr = e - seg * R;
+                    const size_t sh = ((size_t)n * 2 + team) * R + rr, own = ((size_t)n * A + si) * R + rr;
+                    v[j] = seg == 0 ? obs_scaled(sd[sh], a.distance_scale) : seg == 1 ? obs_scaled(st[sh], a.type_scale)
+                         : seg == 2 ? obs_scaled(od[own], a.distance_scale) : obs_scaled(ot[own], a.type_scale);
+                }
+                *(bf16x4 *)(vg + (size_t)n * x->sv_n + 4 * k) = v;
+            }
+        }
     }
     // ---- the convolutions' weights of this wave, in registers for the whole trunk
     const int nt2 = w & 1;                            // conv2: this wave's 16 output channels
@@ -145,6 +170,13 @@ __device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, con
     }
     const f32x4 b1v = ld4(b1 + 16 * w + 4 * q), b2v = ld4(b2 + 16 * nt2 + 4 * q);
     __syncthreads();
+    if constexpr (COLLECT) {                          // the policy's rows: the xin image as it stands, before region A becomes [f | h]
+        __bf16 *pg = (__bf16 *)x->policy_in + (size_t)g * x->sp_g;
+        for (int i = tid; i < TM * (R / 2); i += BLOCK) {
+            const int m = i / (R / 2), k = i - m * (R / 2), n = row0 + m;
+            if (n < rend) *(bf16x4 *)(pg + (size_t)n * x->sp_n + 4 * k) = *(const bf16x4 *)(xin + m * G::XIN_LD + 4 * k);
+        }
+    }
 
     for (int p = 0; p < G::L2; ++p) {
         // conv1 at positions 3 p .. 3 p + 4 -> c1[m][tap * 64 + channel]
@@ -192,7 +224,19 @@ __device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, con
     for (int i = tid; i < TM * (HID / 8); i += BLOCK) {
         const int m = i / (HID / 8), ch = i % (HID / 8), n = row0 + m;
         bf16x8 v = {};
-        if (n < rend && (!a.keep || a.keep[n] != 0.0f)) v = *(const bf16x8 *)(hg + (size_t)n * HID + 8 * ch);
+        if constexpr (COLLECT) {                      // h and c as they stand in memory go out first: keep is not applied to them
+            if (n < rend) {
+                v = *(const bf16x8 *)(hg + (size_t)n * HID + 8 * ch);
+                if (x->h0_out) {
+                    const size_t o = ((size_t)g * N + n) * HID + 8 * ch;
+                    *(bf16x8 *)((__bf16 *)x->h0_out + o) = v;
+                    *(bf16x8 *)((__bf16 *)x->c0_out + o) = *(const bf16x8 *)(cg + (size_t)n * HID + 8 * ch);
+                }
+                if (a.keep && a.keep[n] == 0.0f) v = bf16x8{};
+            }
+        } else {
+            if (n < rend && (!a.keep || a.keep[n] != 0.0f)) v = *(const bf16x8 *)(hg + (size_t)n * HID + 8 * ch);
+        }
         *(bf16x8 *)(fh + m * G::FH_LD + 256 + 8 * ch) = v;
     }
     layer<G::KFC, MT, A_TANH>(wfc, bfc, 256, x2, G::X2_LD, fh, G::FH_LD, w, q, r);
@@ -293,7 +337,14 @@ __device__ __forceinline__ void act_rows(const cat_act_args &a, const int g, con
         const float zact = act == 0 ? z[0] : act == 1 ? z[1] : act == 2 ? z[2] : z[3];
         a.actions[(size_t)n * A + ai] = act;
         if (a.logits_out) *(bf16x4 *)((__bf16 *)a.logits_out + 4 * sidx) = zb;
-        if (a.logp_out) a.logp_out[sidx] = cat4_sampled_logp(cm, zact);
+        if constexpr (COLLECT) {
+            const float lp = cat4_sampled_logp(cm, zact);
+            if (a.logp_out) a.logp_out[sidx] = lp;
+            x->act_out[(size_t)g * x->sa_g + n] = act;
+            x->logp_out[(size_t)g * x->sl_g + n] = lp;
+        } else {
+            if (a.logp_out) a.logp_out[sidx] = cat4_sampled_logp(cm, zact);
+        }
     }
 }
 
@@ -302,6 +353,13 @@ __global__ __launch_bounds__(BLOCK) void act_kernel(const cat_act_args a)
 {
     const int g = blockIdx.y;
     act_rows<R, MT>(a, g, blockIdx.x * (16 * MT), a.d.N, (size_t)g * a.p.stride, (a.random_mask >> g) & 1u);
+}
+
+template <int R, int MT>
+__global__ __launch_bounds__(BLOCK) void act_collect_kernel(const cat_act_collect_args a)
+{
+    const int g = blockIdx.y;
+    act_rows<R, MT, true>(a.base, g, blockIdx.x * (16 * MT), a.base.d.N, (size_t)g * a.base.p.stride, false, &a);
 }
 
 // The league form: workgroup blockIdx.x is tile t of segment s, found by a uniform scan of the (at most 32) segment lengths -- the
@@ -373,6 +431,29 @@ extern "C" int cat_act_step(const cat_act_args *a, void *stream)
     hipStream_t s = (hipStream_t)stream;
     if (a->d.R == 64) return TM == 32 ? launch<64, 2>(act_kernel<64, 2>, *a, tiles, G, who, s) : launch<64, 4>(act_kernel<64, 4>, *a, tiles, G, who, s);
     return TM == 32 ? launch<90, 2>(act_kernel<90, 2>, *a, tiles, G, who, s) : launch<90, 4>(act_kernel<90, 4>, *a, tiles, G, who, s);
+}
+
+extern "C" int cat_act_collect_step(const cat_act_collect_args *a, void *stream)
+{
+    const char *who = "cat_act_collect_step";
+    if (!a || !dims_ok(a->base.d)) return fail(CAT_ACT_ERR_BAD_ARG, who, "bad dimensions (G 1..8, A 1..8, N >= 1, R 64 or 90)");
+    if (a->base.random_mask != 0) return fail(CAT_ACT_ERR_BAD_ARG, who, "random_mask must be 0 (a learner's rollout rows come from its network)");
+    if (const int rc = check_args(&a->base, who, true)) return rc;
+    const int R = a->base.d.R;
+    if (!a->shared_distance || !a->shared_type || !a->policy_in || !a->value_in || !a->act_out || !a->logp_out)
+        return fail(CAT_ACT_ERR_BAD_ARG, who, "a required collect buffer is NULL");
+    if (!a->h0_out != !a->c0_out) return fail(CAT_ACT_ERR_BAD_ARG, who, "h0_out and c0_out must be given together (or both NULL)");
+    if (a->n_cops < 0 || a->n_cops > a->base.d.A) return fail(CAT_ACT_ERR_BAD_ARG, who, "n_cops outside 0..A");
+    if (((uintptr_t)a->policy_in % 8) || ((uintptr_t)a->value_in % 8) || ((uintptr_t)a->act_out % 8) || ((uintptr_t)a->logp_out % 4) ||
+        ((uintptr_t)a->h0_out % 16) || ((uintptr_t)a->c0_out % 16))
+        return fail(CAT_ACT_ERR_BAD_ARG, who, "a collect pointer is misaligned (policy_in, value_in, act_out 8 bytes; h0_out, c0_out 16; logp_out 4)");
+    if ((a->sp_g % 4) || (a->sp_n % 4) || (a->sv_g % 4) || (a->sv_n % 4) || a->sp_n < 2 * R || a->sv_n < 4 * R)
+        return fail(CAT_ACT_ERR_BAD_ARG, who, "a row stride is misaligned or short (sp_g, sp_n, sv_g, sv_n multiples of 4 elements; sp_n >= 2R, sv_n >= 4R)");
+    const int TM = a->base.row_tile ? a->base.row_tile : 32, tiles = (a->base.d.N + TM - 1) / TM, G = a->base.d.G;
+    hipStream_t s = (hipStream_t)stream;
+    if (R == 64)
+        return TM == 32 ? launch<64, 2>(act_collect_kernel<64, 2>, *a, tiles, G, who, s) : launch<64, 4>(act_collect_kernel<64, 4>, *a, tiles, G, who, s);
+    return TM == 32 ? launch<90, 2>(act_collect_kernel<90, 2>, *a, tiles, G, who, s) : launch<90, 4>(act_collect_kernel<90, 4>, *a, tiles, G, who, s);
 }
 
 extern "C" int cat_act_league_step(const cat_act_league_args *a, void *stream)

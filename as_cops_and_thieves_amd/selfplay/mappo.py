@@ -113,6 +113,15 @@ class TrainerConfig:
                                            # trainer adds nothing up itself).  ``read_stats()["env_ticks"]`` counts the env ticks played.
                                            # The resident random-phase fast-forward stays as it is: it plays its span in env ticks,
                                            # one per counted timestep
+    fused_collect: bool = False            # True: a policy-driven tick of a learner is ONE launch of ``cat_act_collect_step`` (include/cat_act.h) --
+                                           # observation packing, the whole policy chain, the draw, and the stores of the packed rows, the
+                                           # action, its log-probability and the window-start state into the rollout buffers -- instead of
+                                           # cat_rollout_pack + the per-layer chain + cat_rollout_sample.  Needs a GPU, bf16 compute, the
+                                           # recurrent pair, 64 or 90 rays, an env with ``raw_outputs`` / ``step_raw``, ``deferred_values`` and no
+                                           # ``random_action_roles``: the trainer raises ValueError otherwise.  Random-phase ticks and roles
+                                           # played by ``set_opponent`` actors stay on their own paths.  The kernel rounds where the chain does
+                                           # but accumulates the LSTM gates unrounded (include/cat_act.h), so actions differ from the chain's in
+                                           # the last bits of the logits: same distribution, not the same trajectory
 
     def __post_init__(self):
         k = self.frame_skip
@@ -497,6 +506,44 @@ class MAPPOTrainer:
         self._env_ticks_host = 0                                                    # frame_skip == 1 and the fast-forward: N per tick, known here
         self.stats: Dict[str, float] = {}
         self.use_graphs = on_gpu
+        self._collect_params: Dict[str, object] = {}    # fused_collect: learner key -> the kernel's parameter block (pointers into fp.lp)
+        if self.tcfg.fused_collect:
+            self._check_fused_collect(on_gpu)
+
+    def _check_fused_collect(self, on_gpu: bool) -> None:
+        """``TrainerConfig.fused_collect`` where the one-launch tick can never apply is an error, not a silent per-layer rollout."""
+        tc, A = self.tcfg, len(self.agents)
+        missing = []
+        if not on_gpu:
+            missing.append("a GPU (the device is %s)" % self.device)
+        if not tc.compute_bf16:
+            missing.append("bf16 compute (compute_bf16=False gives fp32)")
+        if not tc.recurrent:
+            missing.append("the recurrent policies (recurrent=False)")
+        if not tc.deferred_values:
+            missing.append("deferred_values=True")
+        if tc.random_action_roles:
+            missing.append(f"no random_action_roles (got {tuple(tc.random_action_roles)})")
+        if not (hasattr(self.env, "raw_outputs") and hasattr(self.env, "step_raw")):
+            missing.append("an env with raw_outputs() and step_raw()")
+        if not (self.R in (64, 90) and all(_learn_native.act_supported(rl.G, self.N, A, self.R) for rl in self.roles.values())):
+            missing.append(f"64 or 90 rays and at most {_learn_native.ACT_MAX_AGENTS} agents (the env has {self.R} rays, {A} agents): cat_act_supported")
+        if missing:
+            raise ValueError("TrainerConfig.fused_collect=True needs " + "; ".join(missing))
+
+    def _collect_tick(self, key: str, rl: RoleLearner, t: int) -> None:
+        """One policy-driven tick of learner ``rl`` in one launch: its rows of the rollout buffers at tick ``t``, its columns of the action matrix,
+        its recurrent state in place and, at a window start, that state as it stood before the tick."""
+        if key not in self._collect_params:          # the bf16 compute copy itself: every optimiser step is seen, also by a captured rollout
+            self._collect_params[key] = _learn_native.act_params({n: rl.policy.w(n) for n in _learn_native.ACT_PARAM_NAMES})
+        d, ts = (1.0 / 400.0, 0.25) if self.tcfg.normalize_inputs else (1.0, 1.0)
+        b, (h, c) = rl.buf, rl.p_state
+        k, first = divmod(t, rl.bptt)
+        h0, c0 = (rl.p0w[0][k][0], rl.p0w[1][k][0]) if first == 0 else (None, None)
+        u = torch.rand(rl.G, self.N, device=self.device)
+        _learn_native.act_collect_step(self.env.raw_outputs(), rl.indices, self._collect_params[key], h[0], c[0], self._keep32, u, self._actions,
+                                       sum(a.startswith("cop") for a in self.agents), self.tcfg.reference_q11, b["pin"][:, t], b["vin"][:, t],
+                                       b["act"][:, t], b["logp"][:, t], h0, c0, d, ts)
 
     # ------------------------------------------------------------------ model inputs (packing.py layouts)
     def _pack_native(self, rl: RoleLearner, pin: torch.Tensor, vin: torch.Tensor) -> None:
@@ -539,6 +586,7 @@ class MAPPOTrainer:
         any_random = any(random_of.values())
         all_fused = self._native_post and not any_random and all(rl.native and rl.random_rows is None for rl in learners.values())
         defer = all_fused and self._native_io and self.tcfg.deferred_values
+        collect = self.tcfg.fused_collect and defer        # (defer implies all_fused: every learner is native and none acts at random)
         for t in range(T):
             state = self.env.state()
             keep = self._keep32 if all_fused else (~self._starts).view(1, N)
@@ -547,6 +595,9 @@ class MAPPOTrainer:
                 if key in self._opponents:       # played by an actor: no network of the trainer runs, no rollout row is kept; the actor
                     # carries the role's recurrent state (zeroed where ``starts`` is set) and writes its columns of the action matrix
                     self._opponents[key].act(self.env, starts=self._starts, obs=self._obs, actions=self._actions)
+                    continue
+                if collect:
+                    self._collect_tick(key, rl, t)
                     continue
                 random_actions = random_of[key]
                 if t % rl.bptt == 0:                # the recurrent state at the start of a BPTT window is kept

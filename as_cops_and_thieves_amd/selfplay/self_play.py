@@ -611,7 +611,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   n_thieves: Optional[int] = None, max_step_count: int = 2000, eval_envs: Optional[int] = None,
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
                   query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False,
-                  fused_eval: bool = False, league_eval: bool = False, role_training: bool = False) -> Dict[str, object]:
+                  fused_eval: bool = False, league_eval: bool = False, role_training: bool = False,
+                  fused_collect: bool = False) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -637,6 +638,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     data-parallel job (ValueError on every rank before any collective).  ``resume`` continues after the lowest iteration that BOTH roles'
     archives hold and skips a phase whose role has that iteration archived, so a run stopped between the cop and the thief phase of an
     iteration plays the missing thief phase first.
+
+    ``fused_collect``: the training rollouts go through the one-launch collect tick (``TrainerConfig.fused_collect``; ValueError from the
+    trainer where it cannot apply).  The evaluator is not affected.
 
     With an initialised ``torch.distributed`` group of W > 1 ranks this is ONE data-parallel job: ``num_envs`` is the TOTAL,
     rank r simulates ``shard_envs(num_envs, r, W)``; the trainer all-reduces its gradient | KL buffer every optimiser step (all
@@ -670,6 +674,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     trainer_cfg = trainer_cfg or TrainerConfig(timesteps=tc.training_timesteps_per_role_training)
     if episode_stats:
         trainer_cfg = dataclasses.replace(trainer_cfg, episode_stats=True)
+    if fused_collect:
+        trainer_cfg = dataclasses.replace(trainer_cfg, fused_collect=True)
     out_dir = Path(out_dir)
     arch = {tc.cop_role_prefix: out_dir / "cops", tc.thief_role_prefix: out_dir / "thieves"}
     if chief:
@@ -727,7 +733,7 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         evaluator = PolicyActor.from_checkpoint(None, eval_env, fused="kernel", compute_bf16=trainer_cfg.compute_bf16, normalize_inputs=trainer_cfg.normalize_inputs,
                                                 recurrent=trainer_cfg.recurrent, seed=seed + 1, device=trainer.device)
     else:
-        evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False),
+        evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False, fused_collect=False),
                                  seed=seed + 1)
     rng = random.Random(seed)
     start = 0
@@ -884,6 +890,8 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
     ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat) in training and in the evaluations; above 1 "
                     "--timesteps, --horizon and the schedule options count decisions")
+    ap.add_argument("--fused-collect", action="store_true", help="collect the training rollouts through the one-launch fused act kernel "
+                    "(TrainerConfig.fused_collect: a GPU, bf16, the recurrent pair, 64 or 90 rays)")
     args = ap.parse_args()
     if args.role_training and args.gpus > 1:
         sys.exit("--role-training is a single-process mode: it cannot be combined with --gpus > 1")
@@ -911,7 +919,8 @@ def main() -> None:
                         num_rays=args.rays, n_cops=args.cops, n_thieves=args.thieves, max_step_count=args.max_step_count,
                         eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
                         query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval,
-                        league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}))
+                        league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}),
+                        **({"fused_collect": True} if args.fused_collect else {}))
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

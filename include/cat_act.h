@@ -82,6 +82,38 @@ typedef struct cat_act_args {
     float *logp_out;                            /* [G][N] or NULL */
 } cat_act_args;
 
+/* The collect form: cat_act_step for a policy the trainer LEARNS.  Next to everything cat_act_step does with ``base`` (base.actions,
+   base.h / base.c in place, base.logits_out / base.logp_out where non-NULL: bit for bit what cat_act_step produces from the same
+   inputs), the one launch writes what a rollout keeps of the tick, in the rollout's own strided buffers:
+    - policy_in[g][n] (bf16 [2R]) and value_in[g][n] (bf16 [4R]): the rows cat_rollout_pack writes for the same agents, scales, n_cops
+      and first_agent_state (n_cops, first_agent_state, shared_distance, shared_type: the meanings of cat_rollout_pack_args).  The policy
+      row is the observation image the networks read; the workgroup that owns rows of network g writes g's value rows;
+    - act_out[g * sa_g + n]: the action as int64; logp_out[g * sl_g + n]: the fp32 log-probability cat_act_step writes to base.logp_out;
+    - h0_out / c0_out (bf16 [G][N][128] contiguous, both or neither): h and c as they stood in memory BEFORE the tick -- keep is not
+      applied to them -- what a learner keeps as the state at the start of a BPTT window.  They must not overlap base.h / base.c.
+   Row (g, n) of policy_in lies at element g * sp_g + n * sp_n, of value_in at g * sv_g + n * sv_n.  Alignment: rows are stored 8 bytes
+   at a time ([G, T, N, 2R] with R = 90 aligns its rows to 8 bytes and no more), so policy_in and value_in are 8-byte aligned and sp_g, sp_n,
+   sv_g, sv_n are multiples of 4 elements with sp_n >= 2R, sv_n >= 4R; h0_out / c0_out are 16-byte aligned; act_out and logp_out have
+   their types' alignment.  base.random_mask must be 0.  Rows n >= N are never read or written, bytes outside the addressed rows of a
+   strided buffer are untouched, there are no atomics, equal inputs give bit-equal outputs, and the launch is graph-capturable (no
+   allocation, no synchronisation).  The entry uses the LDS of cat_act_step and reads the weights once, as cat_act_step. */
+typedef struct cat_act_collect_args {
+    cat_act_args base;
+    int32_t n_cops;                             /* agents [0, n_cops) are team 0 */
+    int32_t first_agent_state;                  /* 1: every critic row is built from env agent 0 */
+    const void *shared_distance;                /* f16 [N][2][R] */
+    const void *shared_type;                    /* u8  [N][2][R] */
+    void *policy_in;                            /* bf16 rows [2R] */
+    int64_t sp_g, sp_n;
+    void *value_in;                             /* bf16 rows [4R] */
+    int64_t sv_g, sv_n;
+    int64_t *act_out;                           /* [G][N], row stride sa_g */
+    int64_t sa_g;
+    float *logp_out;                            /* [G][N], row stride sl_g */
+    int64_t sl_g;
+    void *h0_out, *c0_out;                      /* bf16 [G][N][128], or both NULL */
+} cat_act_collect_args;
+
 /* The league form: the N rows are cut into S contiguous segments and every segment names, per policy, the parameter set of a
    BANK that plays there.  base.p addresses the bank: set k of every block at pointer + k * stride.  Policy g in segment s (rows
    seg_start[s] .. seg_start[s + 1] - 1; seg_start[0] == 0, seg_start[S] == N, strictly increasing) reads set seg_set[g][s] in
@@ -101,6 +133,7 @@ int cat_act_abi_version(void);
 const char *cat_act_last_error(void);
 int cat_act_supported(const cat_act_dims *d);   /* 1: cat_act_step takes these dimensions */
 int cat_act_step(const cat_act_args *a, void *stream);
+int cat_act_collect_step(const cat_act_collect_args *a, void *stream);
 int cat_act_league_step(const cat_act_league_args *a, void *stream);
 
 #ifdef __cplusplus
