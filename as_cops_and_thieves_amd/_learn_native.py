@@ -29,7 +29,8 @@ MODULES = {
                      "cat_lstm_saved_cell_bytes": (C.c_size_t, [C.c_void_p]), "cat_lstm_seq_forward": _ENTRY, "cat_lstm_seq_backward": _ENTRY}),
     "cat_trunk": (2, {"cat_trunk_out_positions": _QUERY, "cat_trunk_supported": _QUERY, "cat_trunk_backward_blocks": _QUERY,
                       "cat_trunk_forward": _ENTRY, "cat_trunk_backward": _ENTRY, "cat_trunk_grad_finish": _ENTRY}),
-    "cat_ppo": (2, {"cat_ppo_loss_grad": _ENTRY, "cat_ppo_adam_step": _ENTRY, "cat_ppo_gae_scan": _ENTRY}),
+    "cat_ppo": (2, {"cat_ppo_loss_grad": _ENTRY, "cat_ppo_adam_step": _ENTRY, "cat_ppo_gae_scan": _ENTRY, "cat_ppo_gae_scan_scaled": _ENTRY,
+                    "cat_ppo_moment_chunks": (C.c_int, [C.c_int32]), "cat_ppo_moments": _ENTRY}),
     "cat_dense": (2, {"cat_dense_bias_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
                       "cat_dense_act_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
                       "cat_dense_sum_chunks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -422,6 +423,61 @@ def ppo_gae(rewards, values, dones, last_values, gamma: float, lam: float, adv_o
     a = PpoGae(G, T, N, 0, rewards.data_ptr(), values.data_ptr(), d8.data_ptr(), last_values.data_ptr(), gamma, lam,
                adv_out.data_ptr(), ret_out.data_ptr())
     _check(lib().cat_ppo_gae_scan(C.byref(a), _stream()), "cat_ppo_gae_scan")
+
+
+class PpoGaeScaled(C.Structure):
+    _fields_ = PpoGae._fields_ + [("scale", C.c_void_p)]
+
+
+def ppo_gae_scaled(rewards, values, dones, last_values, scale, gamma: float, lam: float, adv_out, ret_out) -> None:
+    """``ppo_gae`` over a critic trained on normalised returns: ``scale`` fp32 [G, 2] = (mu, sigma) on the device; values and last_values
+    are denormalised (v * sigma, then + mu) as they are read, ret_out is the raw return (include/cat_ppo.h)."""
+    import torch
+    G, T, N = rewards.shape
+    for t in (rewards, values, adv_out, ret_out):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (G, T, N)
+    last_values = last_values.contiguous()
+    assert last_values.dtype == torch.float32 and last_values.shape == (G, N)
+    assert scale.dtype == torch.float32 and scale.shape == (G, 2) and scale.is_contiguous() and scale.device == rewards.device
+    d8 = dones.contiguous().view(torch.uint8) if dones.dtype == torch.bool else dones.contiguous()
+    assert d8.dtype == torch.uint8 and d8.shape == (T, N)
+    a = PpoGaeScaled(G, T, N, 0, rewards.data_ptr(), values.data_ptr(), d8.data_ptr(), last_values.data_ptr(), gamma, lam,
+                     adv_out.data_ptr(), ret_out.data_ptr(), scale.data_ptr())
+    _check(lib().cat_ppo_gae_scan_scaled(C.byref(a), _stream()), "cat_ppo_gae_scan_scaled")
+
+
+PPO_MOMENT_CHUNK = 4096         # CAT_PPO_MOMENT_CHUNK
+
+
+class PpoMoments(C.Structure):
+    _fields_ = [("G", C.c_int32), ("M", C.c_int32), ("x", C.c_void_p), ("partial", C.c_void_p), ("batch_out", C.c_void_p),
+                ("state", C.c_void_p), ("scale_out", C.c_void_p)]
+
+
+def ppo_moment_chunks(M: int) -> int:
+    """Rows of the scratch buffer ``ppo_moments`` needs per agent for M samples: ceil(M / 4096)."""
+    return lib().cat_ppo_moment_chunks(M)
+
+
+def ppo_moments(x, state=None, scale_out=None, batch_out=None, partial=None):
+    """x fp32 [G, M] contiguous: the f64 moments (n, mean, M2) of every row in the fixed order of include/cat_ppo.h.  ``batch_out`` f64
+    [G, 3] receives them; ``state`` f64 [G, 3] is merged with them in place; ``scale_out`` fp32 [G, 2] receives (mu, sigma) of the merged
+    state (needs ``state``).  ``partial``: f64 [G, chunks, 3] scratch (allocated when None; pass one for a captured call).  Two
+    launches on the current stream.  Returns ``partial``."""
+    import torch
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()
+    G, M = x.shape
+    if scale_out is not None and state is None:
+        raise ValueError("ppo_moments: scale_out needs state")
+    chunks = ppo_moment_chunks(M)
+    if partial is None:
+        partial = torch.empty(G, chunks, 3, dtype=torch.float64, device=x.device)
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.shape == (G, chunks, 3) and partial.device == x.device
+    for t, dt, shape in ((state, torch.float64, (G, 3)), (batch_out, torch.float64, (G, 3)), (scale_out, torch.float32, (G, 2))):
+        assert t is None or (t.dtype == dt and t.shape == shape and t.is_contiguous() and t.device == x.device)
+    a = PpoMoments(G, M, x.data_ptr(), partial.data_ptr(), _ptr(batch_out), _ptr(state), _ptr(scale_out))
+    _check(lib().cat_ppo_moments(C.byref(a), _stream()), "cat_ppo_moments")
+    return partial
 
 
 # ---------------------------------------------------------------------------------------------- dense-layer epilogues

@@ -1,4 +1,5 @@
-// cat_ppo.hip -- libcat_learn.so, part 3 of 8: PPO loss + gradient, the optimiser step and the GAE scan (include/cat_ppo.h).
+// cat_ppo.hip -- libcat_learn.so, part 3 of 8: PPO loss + gradient, the optimiser step, the GAE scan (plain and over a normalised
+// critic) and the running f64 moments of the returns (include/cat_ppo.h).
 //
 // The first two are a few flops per element over at most a few million elements: as library elementwise kernels they are
 // ~110 launches of ~5 us per minibatch step inside the replayed HIP graph (each a dependent graph node), about a tenth
@@ -8,6 +9,7 @@
 // consumer), never a semaphore-style single-pass reduction.
 #include "cat_learn_common.h"
 #include "cat_ppo.h"
+#include <type_traits>
 
 namespace {
 
@@ -125,22 +127,137 @@ __global__ __launch_bounds__(BLOCK) void adam_kernel(const cat_ppo_adam a)
     }
 }
 
-// one thread per (agent, env): the reverse scan of the rollout's T ticks; lanes = envs, so every access is coalesced
-__global__ __launch_bounds__(BLOCK) void gae_kernel(const cat_ppo_gae a)
+// a normalised critic output back in the returns' units: the product rounded, then the sum rounded (include/cat_ppo.h)
+__device__ __forceinline__ float denormalised(float v, float mu, float sigma)
 {
+#pragma clang fp contract(off)
+    const float p = v * sigma;
+    return p + mu;
+}
+
+// one thread per (agent, env): the reverse scan of the rollout's T ticks; lanes = envs, so every access is coalesced.
+// Args = cat_ppo_gae_scaled: every value read goes through denormalised() first, nothing else differs.
+template <class Args>
+__global__ __launch_bounds__(BLOCK) void gae_kernel(const Args a)
+{
+    constexpr bool SCALED = std::is_same<Args, cat_ppo_gae_scaled>::value;
     const int n = blockIdx.x * BLOCK + threadIdx.x, g = blockIdx.y;
     if (n >= a.N) return;
+    float mu = 0.0f, sigma = 1.0f;
+    if constexpr (SCALED) { mu = a.scale[2 * g]; sigma = a.scale[2 * g + 1]; }
+    const auto value = [&](float v) { if constexpr (SCALED) return denormalised(v, mu, sigma); else return v; };
     const size_t col = (size_t)g * a.T * a.N + n;
-    float last = 0.0f, nxt = a.last_values[(size_t)g * a.N + n];
+    float last = 0.0f, nxt = value(a.last_values[(size_t)g * a.N + n]);
     const float gl = a.gamma * a.lambda;
     for (int t = a.T - 1; t >= 0; --t) {
         const size_t o = col + (size_t)t * a.N;
-        const float nd = a.dones[(size_t)t * a.N + n] ? 0.0f : 1.0f, v = a.values[o];
+        const float nd = a.dones[(size_t)t * a.N + n] ? 0.0f : 1.0f, v = value(a.values[o]);
         const float delta = a.rewards[o] + a.gamma * nxt * nd - v;
         last = delta + gl * nd * last;
         a.adv[o] = last;
         a.ret[o] = last + v;
         nxt = v;
+    }
+}
+
+// ---- running moments (include/cat_ppo.h has the order; every operation below is one rounded f64 operation)
+constexpr int MOMENT_PER_THREAD = CAT_PPO_MOMENT_CHUNK / BLOCK;
+static_assert(MOMENT_PER_THREAD * BLOCK == CAT_PPO_MOMENT_CHUNK && BLOCK == 256, "16 elements per thread, a 256-wide tree");
+
+struct Moments {
+    double n, mean, m2;
+};
+
+__device__ __forceinline__ Moments moments_merge(const Moments a, const Moments b)
+{
+#pragma clang fp contract(off)
+    if (b.n == 0.0) return a;
+    if (a.n == 0.0) return b;
+    Moments r;
+    r.n = a.n + b.n;
+    const double delta = b.mean - a.mean, w = b.n / r.n;
+    const double shift = delta * w;
+    r.mean = a.mean + shift;
+    const double sq = delta * delta, cross = a.n * w;
+    const double corr = sq * cross;
+    r.m2 = (a.m2 + b.m2) + corr;
+    return r;
+}
+
+// s[0] = the halving-tree sum of the 256 threads' v; every thread returns it
+__device__ __forceinline__ double tree_sum(double v, double *s)
+{
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int stride = BLOCK / 2; stride > 0; stride >>= 1) {
+        if ((int)threadIdx.x < stride) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + stride];
+        __syncthreads();
+    }
+    const double total = s[0];
+    __syncthreads();
+    return total;
+}
+
+__global__ __launch_bounds__(BLOCK) void moments_chunk_kernel(const cat_ppo_moments_args a, const int chunks)
+{
+#pragma clang fp contract(off)
+    __shared__ double s[BLOCK];
+    const int c = blockIdx.x, g = blockIdx.y;
+    const float *x = a.x + (size_t)g * a.M;
+    const int first = c * CAT_PPO_MOMENT_CHUNK;                 // c < 65536 (checked by the entry): below 2^28
+    const int count = min(CAT_PPO_MOMENT_CHUNK, a.M - first);
+    float e[MOMENT_PER_THREAD];
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < MOMENT_PER_THREAD; ++j) {
+        const int k = (int)threadIdx.x + BLOCK * j;
+        e[j] = k < count ? x[(size_t)first + k] : 0.0f;
+        if (k < count) acc = acc + (double)e[j];
+    }
+    const double n = (double)count, mean = tree_sum(acc, s) / n;
+    acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < MOMENT_PER_THREAD; ++j) {
+        const int k = (int)threadIdx.x + BLOCK * j;
+        if (k < count) {
+            const double d = (double)e[j] - mean;
+            const double dd = d * d;
+            acc = acc + dd;
+        }
+    }
+    const double m2 = tree_sum(acc, s);
+    if (threadIdx.x == 0) {
+        double *out = a.partial + ((size_t)g * chunks + c) * 3;
+        out[0] = n; out[1] = mean; out[2] = m2;
+    }
+}
+
+// one workgroup per agent: the halving tree over its chunk triples, in place in partial[g] (a pad triple is (0, 0, 0), which merge()
+// passes over: t[i + stride] beyond the chunks leaves t[i] as it is); then the running state and the scale
+__global__ __launch_bounds__(BLOCK) void moments_merge_kernel(const cat_ppo_moments_args a, const int chunks, const int P)
+{
+#pragma clang fp contract(off)
+    const int g = blockIdx.x;
+    double *t = a.partial + (size_t)g * chunks * 3;
+    for (int stride = P / 2; stride > 0; stride >>= 1) {
+        for (int i = threadIdx.x; i < stride && i + stride < chunks; i += BLOCK) {
+            const double *pa = t + 3 * (size_t)i, *pb = t + 3 * (size_t)(i + stride);
+            const Moments r = moments_merge(Moments{pa[0], pa[1], pa[2]}, Moments{pb[0], pb[1], pb[2]});
+            t[3 * (size_t)i] = r.n; t[3 * (size_t)i + 1] = r.mean; t[3 * (size_t)i + 2] = r.m2;
+        }
+        __syncthreads();        // workgroup-scope release / acquire: the next level reads what this one stored
+    }
+    if (threadIdx.x != 0) return;
+    const Moments batch{t[0], t[1], t[2]};
+    if (a.batch_out) { double *o = a.batch_out + 3 * (size_t)g; o[0] = batch.n; o[1] = batch.mean; o[2] = batch.m2; }
+    if (!a.state) return;
+    double *st = a.state + 3 * (size_t)g;
+    const Moments now = moments_merge(Moments{st[0], st[1], st[2]}, batch);
+    st[0] = now.n; st[1] = now.mean; st[2] = now.m2;
+    if (a.scale_out) {
+        const bool empty = now.n == 0.0;
+        a.scale_out[2 * g] = empty ? 0.0f : (float)now.mean;
+        a.scale_out[2 * g + 1] = empty ? 1.0f : (float)sqrt(now.m2 / now.n);
     }
 }
 
@@ -167,7 +284,35 @@ extern "C" int cat_ppo_gae_scan(const cat_ppo_gae *a, void *stream)
     if (!a || a->G <= 0 || a->G > 65535 || a->T <= 0 || a->N <= 0) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_gae_scan: bad dimensions");
     if (!a->rewards || !a->values || !a->dones || !a->last_values || !a->adv || !a->ret)
         return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_gae_scan: a required buffer is NULL");
-    hipLaunchKernelGGL(gae_kernel, dim3((a->N + BLOCK - 1) / BLOCK, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(gae_kernel<cat_ppo_gae>, dim3((a->N + BLOCK - 1) / BLOCK, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    return launched();
+}
+
+extern "C" int cat_ppo_gae_scan_scaled(const cat_ppo_gae_scaled *a, void *stream)
+{
+    if (!a || a->G <= 0 || a->G > 65535 || a->T <= 0 || a->N <= 0) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_gae_scan_scaled: bad dimensions");
+    if (!a->rewards || !a->values || !a->dones || !a->last_values || !a->adv || !a->ret || !a->scale)
+        return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_gae_scan_scaled: a required buffer is NULL");
+    hipLaunchKernelGGL(gae_kernel<cat_ppo_gae_scaled>, dim3((a->N + BLOCK - 1) / BLOCK, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    return launched();
+}
+
+extern "C" int cat_ppo_moment_chunks(int32_t M)
+{
+    return M <= 0 ? 0 : (int)(((int64_t)M + CAT_PPO_MOMENT_CHUNK - 1) / CAT_PPO_MOMENT_CHUNK);
+}
+
+extern "C" int cat_ppo_moments(const cat_ppo_moments_args *a, void *stream)
+{
+    if (!a || a->G <= 0 || a->G > 65535 || a->M <= 0) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_moments: bad dimensions");
+    const int chunks = cat_ppo_moment_chunks(a->M);
+    if (chunks > 65536) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_moments: M is above 65536 chunks of 4096 samples");
+    if (!a->x || !a->partial) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_moments: a required buffer is NULL");
+    if (a->scale_out && !a->state) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_moments: scale_out needs state");
+    int P = 1;
+    while (P < chunks) P <<= 1;
+    hipLaunchKernelGGL(moments_chunk_kernel, dim3(chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a, chunks);
+    hipLaunchKernelGGL(moments_merge_kernel, dim3(a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a, chunks, P);
     return launched();
 }
 

@@ -122,6 +122,13 @@ class TrainerConfig:
                                            # played by ``set_opponent`` actors stay on their own paths.  The kernel rounds where the chain does
                                            # but accumulates the LSTM gates unrounded (include/cat_act.h), so actions differ from the chain's in
                                            # the last bits of the logits: same distribution, not the same trajectory
+    value_norm: bool = False               # True: running value normalisation (the MAPPO paper's first implementation recommendation; skrl's
+                                           # ``value_preprocessor``, which the reference leaves off).  Every learner keeps per-agent running moments
+                                           # (n, mean, M2) of the raw returns in f64 (``RoleLearner.vn_state``) and the scale (mu, sigma) they give
+                                           # (``vn_scale``, (0, 1) at first).  The critic is trained on (return - mu) / (sigma + 1e-8) and its outputs
+                                           # are normalised values: the GAE scan denormalises them as it reads them (``cat_ppo_gae_scan_scaled``),
+                                           # the moments take in every update's raw returns (``cat_ppo_moments``: fixed order, bit-reproducible,
+                                           # include/cat_ppo.h), then the targets are normalised with the new scale.  False: nothing is added
 
     def __post_init__(self):
         k = self.frame_skip
@@ -218,6 +225,68 @@ def advantage_moments(adv: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return mean64.float().view(-1, 1, 1), (dev2 / (n - 1)).sqrt().float().view(-1, 1, 1)
 
 
+# ---------------------------------------------------------------------------------------------- running value normalisation
+# ``cat_ppo_moments`` restated from include/cat_ppo.h in torch f64 on the CPU: every line is one IEEE operation on whole arrays, in the
+# header's order, so the results are the kernel's bit for bit.  The learner's CPU path and the merge of the ranks' triples use them.
+MOMENT_CHUNK = _learn_native.PPO_MOMENT_CHUNK       # CAT_PPO_MOMENT_CHUNK, the binding's one copy of it
+
+
+def merge_moments(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """merge(a, b) of two f64 [..., 3] stacks of (n, mean, M2) triples (Chan et al., the header's order of operations)."""
+    an, am, a2 = a.unbind(-1)
+    bn, bm, b2 = b.unbind(-1)
+    n = an + bn
+    delta = bm - am
+    w = bn / torch.where(n == 0, torch.ones_like(n), n)          # (n == 0 only where both are empty: a is returned there)
+    mean = am + delta * w
+    m2 = (a2 + b2) + (delta * delta) * (an * w)
+    out = torch.stack([n, mean, m2], -1)
+    out = torch.where((an == 0).unsqueeze(-1), b, out)
+    return torch.where((bn == 0).unsqueeze(-1), a, out)
+
+
+def running_moments(x: torch.Tensor) -> torch.Tensor:
+    """x fp32 [G, M] -> f64 [G, 3] on the CPU: (n, mean, M2) of every row in ``cat_ppo_moments``'s order -- chunks of 4096, in a chunk
+    256 "threads" that add their 16 strided elements left to right, a halving tree over the 256, the mean, the same again over the
+    squared deviations; then a halving tree of ``merge_moments`` over the chunks, padded with empty triples to a power of two."""
+    x = x.detach().to("cpu", torch.float64)
+    G, M = x.shape
+    chunks = -(-M // MOMENT_CHUNK)
+    pad = chunks * MOMENT_CHUNK - M
+    inside = torch.nn.functional.pad(torch.ones(M, dtype=torch.bool), (0, pad)).view(chunks, 16, 256)
+    v = torch.nn.functional.pad(x, (0, pad)).view(G, chunks, 16, 256)         # [g][c][j][i] = x[g][c * 4096 + i + 256 j]
+
+    def chunk_sum(e):           # elements out of range are +0.0: adding one leaves a sum that started at +0.0 as it is
+        s = torch.zeros(G, chunks, 256, dtype=torch.float64)
+        for j in range(16):
+            s = s + e[:, :, j]
+        stride = 128
+        while stride:
+            s = s[..., :stride] + s[..., stride:2 * stride]
+            stride //= 2
+        return s[..., 0]
+    n = inside.sum(dim=(1, 2)).to(torch.float64).expand(G, chunks)
+    mean = chunk_sum(v) / n
+    d = torch.where(inside, v - mean.view(G, chunks, 1, 1), torch.zeros((), dtype=torch.float64))
+    t = torch.stack([n, mean, chunk_sum(d * d)], -1)                           # [G, chunks, 3]
+    P = 1
+    while P < chunks:
+        P *= 2
+    t = torch.cat([t, torch.zeros(G, P - chunks, 3, dtype=torch.float64)], 1)
+    while P > 1:
+        P //= 2
+        t = merge_moments(t[:, :P], t[:, P:2 * P])
+    return t[:, 0]
+
+
+def moments_scale(state: torch.Tensor) -> torch.Tensor:
+    """f64 [G, 3] -> fp32 [G, 2] = (mu, sigma) = (mean, sqrt(M2 / n)), and (0, 1) while n == 0."""
+    n, mean, m2 = state.unbind(-1)
+    empty = n == 0
+    sigma = torch.sqrt(m2 / torch.where(empty, torch.ones_like(n), n))
+    return torch.stack([torch.where(empty, torch.zeros_like(mean), mean).float(), torch.where(empty, torch.ones_like(sigma), sigma).float()], -1)
+
+
 class RoleLearner:
     """G agents that share one ``RoleConfig`` -- the agents of a role, or of both roles when the roles are configured
     alike (the reference's driver: ``CFG_AGENT`` for everyone) -- as stacked policy + value networks over one flat
@@ -228,7 +297,7 @@ class RoleLearner:
 
     def __init__(self, role: str, agents: List[str], indices: List[int], R: int, N: int, T: int, cfg: RoleConfig,
                  device: torch.device, compute_dtype: torch.dtype, seeds: List[int], bptt: Optional[int] = None,
-                 arch: str = "lstm", vwidth: Optional[int] = None):
+                 arch: str = "lstm", vwidth: Optional[int] = None, value_norm: bool = False):
         self.role, self.agents, self.indices, self.cfg = role, agents, indices, cfg
         self.agent_roles = [a.split("_")[0] for a in agents]
         self.G, self.R, self.N, self.T, self.device = len(agents), R, N, T, device
@@ -280,6 +349,14 @@ class RoleLearner:
             self.v0 = tuple(torch.zeros(s.shape[1], G, S, s.shape[4], dtype=s.dtype, device=device) for s in self.v0w)
             self.start = torch.zeros(self.bptt, S, dtype=torch.bool, device=device)
         self._graphs = None
+        self.value_norm = value_norm
+        if value_norm:      # TrainerConfig.value_norm: running moments of the raw returns and the scale the critic's targets are normalised with
+            self.vn_state = torch.zeros(G, 3, dtype=torch.float64, device=device)              # (n, mean, M2) per agent
+            self.vn_scale = torch.tensor([[0.0, 1.0]] * G, **f32)                              # (mu, sigma) per agent
+            if self.native:
+                self._vn_partial = torch.empty(G, _learn_native.ppo_moment_chunks(T * N), 3, dtype=torch.float64, device=device)
+                self._vn_batch = torch.zeros(G, 3, dtype=torch.float64, device=device)
+            self._vn_frozen = torch.zeros(G, 1, dtype=torch.bool, device=device)               # agents whose value network is frozen
 
     # ------------------------------------------------------------------ freezing (skrl Model.freeze_parameters)
     def set_frozen(self, role: Optional[str] = None, policy: Optional[bool] = None, value: Optional[bool] = None) -> None:
@@ -292,6 +369,8 @@ class RoleLearner:
         rows = [self.col_policy * (0.0 if self.frozen[r][0] else 1.0) + self.col_value * (0.0 if self.frozen[r][1] else 1.0)
                 for r in self.agent_roles]
         self.col_train.copy_(torch.stack(rows))
+        if self.value_norm:     # a frozen critic keeps the scale it was trained under (``_moments_step``)
+            self._vn_frozen.copy_(torch.tensor([[self.frozen[r][1]] for r in self.agent_roles]))
 
     def rows(self, role: str) -> List[int]:
         return [g for g, r in enumerate(self.agent_roles) if r == role]
@@ -410,12 +489,79 @@ class RoleLearner:
             restore()
             return ()
 
+    # ------------------------------------------------------------------ running value normalisation
+    def set_value_moments(self, g: int, triple: Optional[torch.Tensor]) -> None:
+        """Agent g's running moments <- ``triple`` f64 [3] (None: a fresh scaler), and the scale they give."""
+        self.vn_state[g] = 0.0 if triple is None else triple.to(self.device, torch.float64)
+        self.vn_scale.copy_(moments_scale(self.vn_state.cpu()))
+
+    @torch.no_grad()
+    def _moments_step(self, raw: torch.Tensor) -> None:
+        """The running moments take in this update's raw returns ``raw`` fp32 [G, M] (``_moments_merge``) -- but not those of an agent
+        whose value network is frozen (``set_frozen(value=True)``): its critic is not trained meanwhile, so its outputs stay in the units
+        of the scale it was trained under, and its ``vn_state`` / ``vn_scale`` rows stay as they are until it is released."""
+        if not any(self.frozen[r][1] for r in self.agent_roles):
+            return self._moments_merge(raw)
+        state, scale = self.vn_state.clone(), self.vn_scale.clone()
+        self._moments_merge(raw)
+        self.vn_state.copy_(torch.where(self._vn_frozen, state, self.vn_state))
+        self.vn_scale.copy_(torch.where(self._vn_frozen, scale, self.vn_scale))
+
+    @torch.no_grad()
+    def _moments_merge(self, raw: torch.Tensor) -> None:
+        """``vn_state`` takes in the raw returns ``raw`` fp32 [G, M] of this update and ``vn_scale`` follows.  One rank on the kernel path:
+        two launches of ``cat_ppo_moments``, no host involvement.  Several ranks: each takes the moments of its shard, the [G, 3] triples are
+        all-gathered and every rank merges them into its state in rank order on the host -- the same operations on the same numbers, so all
+        ranks keep bit-equal state (gloo takes CPU tensors, as in ``advantage_moments``)."""
+        import torch.distributed as dist
+        multi = _dist_ready() and dist.get_world_size() > 1
+        if self.native and not multi:
+            _learn_native.ppo_moments(raw, state=self.vn_state, scale_out=self.vn_scale, partial=self._vn_partial)
+            return
+        if self.native:
+            _learn_native.ppo_moments(raw, batch_out=self._vn_batch, partial=self._vn_partial)
+            batch = self._vn_batch
+        else:
+            batch = running_moments(raw)
+        shards = [batch.cpu()]
+        if multi:
+            if dist.get_backend() == "gloo" or not batch.is_cuda:
+                shards = [torch.empty_like(shards[0]) for _ in range(dist.get_world_size())]
+                dist.all_gather(shards, batch.cpu())
+            else:   # RCCL: device tensors.  (No test reaches this branch: the suite has gloo ranks on the CPU and one GPU.)
+                shards = [torch.empty_like(batch) for _ in range(dist.get_world_size())]
+                dist.all_gather(shards, batch.contiguous())
+                shards = [t.cpu() for t in shards]
+        state = self.vn_state.cpu()
+        for t in shards:
+            state = merge_moments(state, t)
+        self.vn_state.copy_(state)
+        self.vn_scale.copy_(moments_scale(state))
+
+    def _scan_normalised(self, dones: torch.Tensor, last_values: torch.Tensor) -> torch.Tensor:
+        """The update's first steps with ``value_norm``: the scan over the denormalised critic outputs (advantages and RAW returns), the
+        running moments take the raw returns in, and ``buf["ret"]`` receives the returns normalised with the NEW scale.  Returns adv."""
+        cfg, b, G = self.cfg, self.buf, self.G
+        if self.native:
+            adv, raw = torch.empty_like(b["adv"]), torch.empty_like(b["ret"])
+            _learn_native.ppo_gae_scaled(b["rew"], b["val"], dones, last_values, self.vn_scale, cfg.discount_factor, cfg.gae_lambda, adv, raw)
+        else:       # the header's two operations, then the plain recursion
+            mu, sigma = self.vn_scale[:, 0].view(G, 1, 1), self.vn_scale[:, 1].view(G, 1, 1)
+            adv, raw = compute_gae(b["rew"], b["val"] * sigma + mu, dones, last_values * sigma[:, 0] + mu[:, 0], cfg.discount_factor, cfg.gae_lambda)
+        self._moments_step(raw.view(G, -1))
+        mu, sigma = self.vn_scale[:, 0].view(G, 1, 1), self.vn_scale[:, 1].view(G, 1, 1)
+        b["ret"].copy_((raw - mu) / (sigma + 1e-8))
+        return adv
+
     # ------------------------------------------------------------------ update of one rollout
     def update(self, dones: torch.Tensor, starts: torch.Tensor, last_values: torch.Tensor, gen: torch.Generator,
                use_graph: bool) -> None:
-        """dones/starts [T, N]; last_values [G, N] (bootstrap, already zeroed where the next tick starts an episode)."""
+        """dones/starts [T, N]; last_values [G, N] (bootstrap, already zeroed where the next tick starts an episode; with ``value_norm``
+        a normalised critic output like ``buf["val"]``: the zero is then not a zero return, but ``dones`` of the last tick cuts it off)."""
         cfg, b = self.cfg, self.buf
-        if self.native:   # the reverse scan over the T ticks as one launch (csrc/cat_ppo.hip) instead of ~7 small ones per tick
+        if self.value_norm:
+            adv = self._scan_normalised(dones, last_values)
+        elif self.native:   # the reverse scan over the T ticks as one launch (csrc/cat_ppo.hip) instead of ~7 small ones per tick
             adv = torch.empty_like(b["adv"])
             _learn_native.ppo_gae(b["rew"], b["val"], dones, last_values, cfg.discount_factor, cfg.gae_lambda, adv, b["ret"])
         else:
@@ -476,7 +622,8 @@ class MAPPOTrainer:
             self.roles["+".join(grp)] = RoleLearner("+".join(grp), names, idx, self.R, self.N, self.tcfg.horizon, cfgs[grp[0]],
                                                     self.device, dt, seeds=[seed * 1000 + i for i in idx],
                                                     bptt=min(self.tcfg.bptt, self.tcfg.horizon),
-                                                    arch="lstm" if self.tcfg.recurrent else "mlp", vwidth=self.state_width)
+                                                    arch="lstm" if self.tcfg.recurrent else "mlp", vwidth=self.state_width,
+                                                    **({"value_norm": True} if self.tcfg.value_norm else {}))
         for rl in self.roles.values():
             mask = [r in self.tcfg.random_action_roles for r in rl.agent_roles]
             rl.random_rows = torch.tensor(mask, device=self.device).view(rl.G, 1) if any(mask) else None
@@ -783,6 +930,10 @@ class MAPPOTrainer:
             s = rl.stat.cpu()
             for g, a in enumerate(rl.agents):
                 out[f"{a}/policy_loss"], out[f"{a}/value_loss"], out[f"{a}/kl"] = float(s[0, g]), float(s[1, g]), float(s[2, g])
+            if rl.value_norm:           # the scale the critic's targets are normalised with: (0, 1) before the first update
+                sc = rl.vn_scale.cpu()
+                for g, a in enumerate(rl.agents):
+                    out[f"value_mean/{a}"], out[f"value_std/{a}"] = float(sc[g, 0]), float(sc[g, 1])
         ep = self._episode_stats()
         if ep is not None:
             e = ep()
@@ -897,6 +1048,8 @@ class MAPPOTrainer:
                 continue
             out[a] = dict(self.agent_models(a), optimizer=adam_state_dict(rl.fp, g, rl.m, rl.v, rl.steps, rl.cfg.learning_rate,
                                                                          (rl.BETA1, rl.BETA2), rl.EPS))
+            if rl.value_norm:           # the running moments the agent's critic was trained under: (n, mean, M2), f64
+                out[a]["vn_state"] = rl.vn_state[g].detach().cpu().clone()
         out[self.META_KEY] = {"format": "cat-mappo-3", "timestep": self.timestep, "num_rays": self.R, "recurrent": bool(self.tcfg.recurrent)}
         return out
 
@@ -904,10 +1057,13 @@ class MAPPOTrainer:
         """``roles``: restrict to these roles' models (reference ``copy_role_models``, which copies policy and value
         weights only: pass ``optimizer=False`` for that).  Accepts this class's checkpoints, a checkpoint written by the
         reference (skrl layout, no ``__cat__``; preprocessor entries are ignored, the reference configures none) and
-        round-2 files (``{"format": "cat-mappo-2", "models": ..., "optimizers": ...}``)."""
+        round-2 files (``{"format": "cat-mappo-2", "models": ..., "optimizers": ...}``).  With ``TrainerConfig.value_norm`` an agent's
+        ``vn_state`` is restored with its models (an agent entry without one starts a fresh scaler); without the option a checkpoint's
+        ``vn_state`` entries are ignored with one warning."""
         if sd.get("format") == "cat-mappo-2":
             sd = dict({a: dict(sd["models"][a], **({"optimizer": sd["optimizers"][a]} if a in sd.get("optimizers", {}) else {}))
                        for a in sd["models"]}, **{self.META_KEY: {"timestep": sd.get("timestep", 0)}})
+        ignored: List[str] = []
         for a in self.agents:
             if roles is not None and a.split("_")[0] not in roles:
                 continue
@@ -917,6 +1073,13 @@ class MAPPOTrainer:
             load_agent_state_dict(rl.fp, g, sd[a])
             if optimizer and "optimizer" in sd[a]:
                 load_adam_state_dict(rl.fp, g, rl.m, rl.v, rl.steps, sd[a]["optimizer"])
+            if rl.value_norm:           # goes with the value network: its outputs are in these units.  No entry: a fresh scaler
+                rl.set_value_moments(g, sd[a].get("vn_state"))
+            elif "vn_state" in sd[a]:
+                ignored.append(a)
+        if ignored:
+            warnings.warn(f"the checkpoint holds running value moments (vn_state) of {ignored}, which a trainer with value_norm=False ignores: "
+                          "their value networks were trained on normalised returns")
         if optimizer and roles is None:
             self.timestep = int(sd.get(self.META_KEY, {}).get("timestep", 0))
 

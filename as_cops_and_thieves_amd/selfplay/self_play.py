@@ -612,7 +612,7 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
                   query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False,
                   fused_eval: bool = False, league_eval: bool = False, role_training: bool = False,
-                  fused_collect: bool = False) -> Dict[str, object]:
+                  fused_collect: bool = False, value_norm: bool = False) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -641,6 +641,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
 
     ``fused_collect``: the training rollouts go through the one-launch collect tick (``TrainerConfig.fused_collect``; ValueError from the
     trainer where it cannot apply).  The evaluator is not affected.
+
+    ``value_norm``: the critics train on returns normalised by running per-agent moments (``TrainerConfig.value_norm``); the joint
+    checkpoints then carry each agent's moments (``vn_state``) beside its value network.
 
     With an initialised ``torch.distributed`` group of W > 1 ranks this is ONE data-parallel job: ``num_envs`` is the TOTAL,
     rank r simulates ``shard_envs(num_envs, r, W)``; the trainer all-reduces its gradient | KL buffer every optimiser step (all
@@ -676,6 +679,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         trainer_cfg = dataclasses.replace(trainer_cfg, episode_stats=True)
     if fused_collect:
         trainer_cfg = dataclasses.replace(trainer_cfg, fused_collect=True)
+    if value_norm:
+        trainer_cfg = dataclasses.replace(trainer_cfg, value_norm=True)
     out_dir = Path(out_dir)
     arch = {tc.cop_role_prefix: out_dir / "cops", tc.thief_role_prefix: out_dir / "thieves"}
     if chief:
@@ -892,6 +897,8 @@ def main() -> None:
                     "--timesteps, --horizon and the schedule options count decisions")
     ap.add_argument("--fused-collect", action="store_true", help="collect the training rollouts through the one-launch fused act kernel "
                     "(TrainerConfig.fused_collect: a GPU, bf16, the recurrent pair, 64 or 90 rays)")
+    ap.add_argument("--value-norm", action="store_true", help="train the critics on returns normalised by running per-agent moments "
+                    "(TrainerConfig.value_norm; off in the reference)")
     args = ap.parse_args()
     if args.role_training and args.gpus > 1:
         sys.exit("--role-training is a single-process mode: it cannot be combined with --gpus > 1")
@@ -920,7 +927,7 @@ def main() -> None:
                         eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
                         query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval,
                         league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}),
-                        **({"fused_collect": True} if args.fused_collect else {}))
+                        **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}))
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

@@ -75,6 +75,60 @@ typedef struct cat_ppo_gae {
 } cat_ppo_gae;
 int cat_ppo_gae_scan(const cat_ppo_gae *a, void *stream);
 
+/* The same scan over a critic that is trained on NORMALISED returns (running value normalisation, below): every value the scan
+ * reads -- values[g][t][n] and last_values[g][n] -- is denormalised first, V = v * sigma_g + mu_g with scale[g] = (mu_g, sigma_g):
+ * one fp32 multiply, then one fp32 add, each rounded (never a fused multiply-add).  adv is the advantage, ret = adv + V the RAW
+ * return.  Everything else is cat_ppo_gae_scan's arithmetic, instruction for instruction (one kernel template): the result is
+ * bit-equal to cat_ppo_gae_scan run on values and last_values denormalised by those two operations beforehand, and with
+ * scale = (0, 1) to cat_ppo_gae_scan itself.  Same grid, no atomics, capturable. */
+typedef struct cat_ppo_gae_scaled {
+    int32_t G, T, N, pad;
+    const float *rewards, *values;      /* [G][T][N] */
+    const uint8_t *dones;               /* [T][N] */
+    const float *last_values;           /* [G][N] */
+    float gamma, lambda;
+    float *adv, *ret;                   /* [G][T][N] */
+    const float *scale;                 /* [G][2] = (mu_g, sigma_g); device memory, not NULL */
+} cat_ppo_gae_scaled;
+int cat_ppo_gae_scan_scaled(const cat_ppo_gae_scaled *a, void *stream);
+
+/* Running moments (n, mean, M2 = sum of squared deviations from the mean) of each agent's M samples, in f64 and in ONE fixed
+ * order, so that the result is bit-reproducible and a host restatement of the order below reproduces it bit for bit.  Two
+ * launches, no atomics, capturable.  All arithmetic is f64 with every operation rounded on its own (no contraction of a product
+ * into a sum); divide and square root are the correctly rounded ones.
+ *
+ * Chunk launch: one workgroup of 256 threads per (g, chunk c); chunk c covers x[g][c * 4096 .. c * 4096 + 4095].
+ *   1. thread i: s_i = 0; for j = 0 .. 15 in this order: e = c * 4096 + i + 256 j; if e < M: s_i = s_i + (double)x[g][e]
+ *   2. halving tree in LDS: for stride = 128, 64, .., 1: s_i = s_i + s_{i + stride} for every i < stride; sum = s_0
+ *   3. n_c = the number of e < M in the chunk (as a double); mean_c = sum / n_c
+ *   4. steps 1 and 2 again over d * d, d = (double)x[g][e] - mean_c (the product rounded, then added); M2_c = that sum
+ *   5. partial[g][c] = (n_c, mean_c, M2_c)
+ * Merge launch: one workgroup per g.
+ *   1. t[0 .. P) = partial[g][0 .. chunks) followed by (0, 0, 0) up to P, the next power of two >= chunks;
+ *      for stride = P / 2, .., 1: t[i] = merge(t[i], t[i + stride]) for every i < stride; batch = t[0].
+ *      (This tree runs in place in partial[g]: after the call partial holds intermediate values.)
+ *   2. merge(a, b) = a if b.n == 0; b if a.n == 0; otherwise (Chan et al.), in this order of operations:
+ *        n     = a.n + b.n
+ *        delta = b.mean - a.mean
+ *        mean  = a.mean + delta * (b.n / n)
+ *        M2    = (a.M2 + b.M2) + (delta * delta) * (a.n * (b.n / n))
+ *   3. batch_out[g] = batch                                 (when batch_out != NULL)
+ *   4. state[g] = merge(state[g], batch)                    (when state != NULL)
+ *   5. scale_out[g] = (mu, sigma) = ((float)state.mean, (float)sqrt(state.M2 / state.n)), or (0, 1) while state.n == 0
+ *                                                           (when scale_out != NULL; needs state)
+ * 1 <= M and cat_ppo_moment_chunks(M) <= 65536; a larger M is CAT_PPO_ERR_BAD_ARG. */
+#define CAT_PPO_MOMENT_CHUNK 4096
+typedef struct cat_ppo_moments_args {
+    int32_t G, M;
+    const float *x;                     /* [G][M], contiguous */
+    double *partial;                    /* [G][chunks][3] scratch, chunks = cat_ppo_moment_chunks(M); caller-owned */
+    double *batch_out;                  /* [G][3] = (n, mean, M2) of this call's samples, or NULL */
+    double *state;                      /* [G][3], merged in place, or NULL */
+    float *scale_out;                   /* [G][2] = (mu, sigma) of the merged state, or NULL; needs state */
+} cat_ppo_moments_args;
+int cat_ppo_moment_chunks(int32_t M);   /* ceil(M / CAT_PPO_MOMENT_CHUNK); 0 for M <= 0 */
+int cat_ppo_moments(const cat_ppo_moments_args *a, void *stream);
+
 int cat_ppo_abi_version(void);
 const char *cat_ppo_last_error(void);
 int cat_ppo_loss_grad(const cat_ppo_loss *a, void *stream);

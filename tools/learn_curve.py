@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: does the learner learn?  Cops (trained) against uniformly random thieves on a map; prints the cop win
-rate of sampled-action evaluation episodes every few updates.  Usage: python tools/learn_curve.py [map] [envs] [updates] [lr] [max_step_count] [entropy_scale] [norm|raw] [horizon]"""
+rate of sampled-action evaluation episodes every few updates.  Usage: python tools/learn_curve.py [map] [envs] [updates] [lr] [max_step_count] [entropy_scale] [norm|raw] [horizon] [vn|novn]
+(vn: TrainerConfig.value_norm, running value normalisation; the value_loss column is then in normalised units)"""
 import sys, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
@@ -17,6 +18,7 @@ msc = int(sys.argv[5]) if len(sys.argv) > 5 else 400
 ent = float(sys.argv[6]) if len(sys.argv) > 6 else 0.02
 norm = (sys.argv[7] == "norm") if len(sys.argv) > 7 else False
 horizon = int(sys.argv[8]) if len(sys.argv) > 8 else 16
+vn = (sys.argv[9] == "vn") if len(sys.argv) > 9 else False
 rc = RoleConfig(random_timesteps=0, learning_starts=0, learning_rate=lr, entropy_loss_scale=ent)
 if name == "arena":   # an open 600 x 600 arena with one small block: cops and thieves spawn 50..200 px apart, so the
     import json, tempfile                       # cops' shaping reward (1.5 exp(-d/50) while a thief is in sight) is dense
@@ -33,10 +35,10 @@ else:
     the_map = load_preset(name)
 env = VecCopsEnv(the_map, num_envs=N, num_rays=64, max_step_count=msc, seed=1)
 ev = VecCopsEnv(the_map, num_envs=512, num_rays=64, max_step_count=msc, seed=99)
-tc = TrainerConfig(policy_freeze_duration=0, opponent_freeze_duration=0, random_action_roles=("thief",), normalize_inputs=norm, horizon=horizon)
+tc = TrainerConfig(policy_freeze_duration=0, opponent_freeze_duration=0, random_action_roles=("thief",), normalize_inputs=norm, horizon=horizon, value_norm=vn)
 tr = MAPPOTrainer(env, {"cop": rc, "thief": rc}, tc, seed=0)
 tr.set_frozen(role="thief", policy=True, value=True)
-evr = MAPPOTrainer(ev, {"cop": rc, "thief": rc}, TrainerConfig(horizon=16, graph_rollout=False, graph_update=False, normalize_inputs=norm), seed=1)
+evr = MAPPOTrainer(ev, {"cop": rc, "thief": rc}, TrainerConfig(horizon=16, graph_rollout=False, graph_update=False, normalize_inputs=norm, value_norm=vn), seed=1)
 t0 = time.time()
 for u in range(U + 1):
     if u % max(1, U // 10) == 0:
