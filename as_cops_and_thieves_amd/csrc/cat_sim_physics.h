@@ -88,10 +88,79 @@ __device__ int circle_poly_contact(const Lds &L, int sh, double rp, double cx, d
 // the sim's maps: agents x the deepest overlap of wall bbs an agent's bb can reach, + agent pairs) sizes the array, and a contact beyond it -- never
 // on a map cat_create accepted -- is dropped and flagged (CAT_DEVERR_CONTACT_DROPPED) instead of written.
 constexpr int kConD = 14;
+
+// The solver of a step whose contacts are all agent-wall (b = -1), at most kSolveReg per agent: lane = agent.  The lane keeps its body's vel / vb
+// and its own contacts' constants and accumulators in registers from [CP cpArbiterPreStep] to the last sweep, and stores them once.
+// Exact: the contacts are created agent by agent, so an agent's contacts k0 .. k0 + kn - 1 are consecutive in the list, and a wall contact reads
+// and writes only its own agent's vel / vb and its own accumulators -- in the list-order Gauss-Seidel of physics_env each body sees these very
+// operations on these very operands in this very order, whatever the other agents' contacts do in between.  The expressions are physics_env's
+// with b's terms at the values they take there for b < 0 (0.0): the forms that look redundant fix signs of zero and the operation order.
+constexpr int kSolveReg = 2;   // (4 were built: 10 - 23 VGPRs spilled in every instantiation; beyond 2 the list-order loop of physics_env runs)
+struct WallCon { double nx, ny, bias, bounce, jnAcc, jBiasAcc; int idx, first; };
+__device__ __forceinline__ void wall_con_load(WallCon &c, const Lds &L, const Params &p, int q, double pax, double pay, double vx, double vy)
+{   // [CP cpArbiterPreStep]
+    const double *cf = L.conf + kConD * q;
+    const int *ci = reinterpret_cast<const int *>(cf + 12);
+    c.first = ci[2]; c.idx = ci[3];
+    c.nx = cf[0]; c.ny = cf[1]; c.jnAcc = cf[9]; c.jBiasAcc = 0.0;
+    const double bdx = 0.0 - pax, bdy = 0.0 - pay;
+    const double dist = ((cf[4] - cf[2]) + bdx) * c.nx + ((cf[5] - cf[3]) + bdy) * c.ny;
+    c.bias = -p.bias_coef * fmin2(0.0, dist + p.slop) / p.dt;
+    c.bounce = ((0.0 - vx) * c.nx + (0.0 - vy) * c.ny) * 0.0;   // e = 0
+}
+__device__ __forceinline__ void wall_con_cached(const WallCon &c, double m_inv, double &vx, double &vy)
+{   // [CP cpArbiterApplyCachedImpulse], dt_coef = 1
+    if (c.first) return;
+    const double jx = (c.nx * c.jnAcc - c.ny * 0.0) * 1.0, jy = (c.nx * 0.0 + c.ny * c.jnAcc) * 1.0;
+    vx = vx + (-jx) * m_inv; vy = vy + (-jy) * m_inv;
+}
+__device__ __forceinline__ void wall_con_impulse(WallCon &c, double m_inv, double nMass, double &vx, double &vy, double &wx, double &wy)
+{   // [CP cpArbiterApplyImpulse]
+    const double vbn = (0.0 - wx) * c.nx + (0.0 - wy) * c.ny;
+    const double vrn = (0.0 - vx) * c.nx + (0.0 - vy) * c.ny;
+    const double jbn = (c.bias - vbn) * nMass;
+    const double jbnOld = c.jBiasAcc;
+    c.jBiasAcc = fmax2(jbnOld + jbn, 0.0);
+    const double jn = -(c.bounce + vrn) * nMass;
+    const double jnOld = c.jnAcc;
+    c.jnAcc = fmax2(jnOld + jn, 0.0);
+    const double jbx = c.nx * (c.jBiasAcc - jbnOld), jby = c.ny * (c.jBiasAcc - jbnOld);
+    const double dj = c.jnAcc - jnOld;
+    const double jx = c.nx * dj - c.ny * 0.0, jy = c.nx * 0.0 + c.ny * dj;   // cpvrotate, jt = 0
+    wx = wx + (-jbx) * m_inv; wy = wy + (-jby) * m_inv;
+    vx = vx + (-jx) * m_inv; vy = vy + (-jy) * m_inv;
+}
+__device__ __forceinline__ void solve_walls_reg(const Lds &L, const Params &p, int lane, int k0, int kn, double m_inv)
+{
+    if (kn == 0) return;
+    const int a = lane;
+    double vx = L.vel[2 * a], vy = L.vel[2 * a + 1], wx = L.vb[2 * a], wy = L.vb[2 * a + 1];
+    const double nMass = 1.0 / (m_inv + 0.0);
+    WallCon c0, c1;
+    {
+        const double pax = L.pos[2 * a], pay = L.pos[2 * a + 1];
+        wall_con_load(c0, L, p, k0, pax, pay, vx, vy);
+        if (kn > 1) wall_con_load(c1, L, p, k0 + 1, pax, pay, vx, vy);
+    }
+    wall_con_cached(c0, m_inv, vx, vy);
+    if (kn > 1) {
+        wall_con_cached(c1, m_inv, vx, vy);
+        for (int it = 0; it < p.iterations; it++) {
+            wall_con_impulse(c0, m_inv, nMass, vx, vy, wx, wy);
+            wall_con_impulse(c1, m_inv, nMass, vx, vy, wx, wy);
+        }
+        L.wjn[c1.idx] = c1.jnAcc;
+    } else {
+        for (int it = 0; it < p.iterations; it++) wall_con_impulse(c0, m_inv, nMass, vx, vy, wx, wy);
+    }
+    L.wjn[c0.idx] = c0.jnAcc;
+    L.vel[2 * a] = vx; L.vel[2 * a + 1] = vy; L.vb[2 * a] = wx; L.vb[2 * a + 1] = wy;
+}
+
 // [CP cpSpaceStep] for one env.  Executed wave-uniformly (every lane computes the same values and
 // stores them to the same LDS words) except the bb-overlap test, where lanes stride the walls.
 template <class D>
-__device__ void physics_env(const Lds &L, const Params &p, int S, int lane, PhaseClock &pc)
+__device__ __forceinline__ void physics_env(const Lds &L, const Params &p, int S, int lane, PhaseClock &pc)
 {
     const int A = D::A(p);
     const double dt = p.dt, rc = p.rc;
@@ -259,6 +328,22 @@ __device__ void physics_env(const Lds &L, const Params &p, int S, int lane, Phas
     const double m_inv = 1.0 / p.mass;
     const int q = lane;
     const bool own = q < nc;
+    {   // wall contacts only, at most kSolveReg per agent, each agent's consecutive in the list (they are created agent by agent): lane = agent.
+        // (The test that an agent's contacts ARE consecutive cannot fail for a list built above; it guards the solver's premise against a later
+        // change of the creation order, which would otherwise show only as a wrong result.)
+        int ka = -1, kb = -1;
+        if (own) { const int *ci = reinterpret_cast<const int *>(L.conf + kConD * q + 12); ka = ci[0]; kb = ci[1]; }
+        bool reg = __ballot(kb >= 0) == 0ull;
+        int k0 = 0, kn = 0;
+        for (int i = 0; reg && i < A; i++) {
+            const unsigned long long mk = __ballot(ka == i);
+            if (mk == 0ull) continue;
+            const int n_i = __popcll(mk), f_i = __builtin_ctzll(mk);
+            if (n_i > kSolveReg || mk != (((1ull << n_i) - 1ull) << f_i)) { reg = false; break; }
+            if (lane == i) { k0 = f_i; kn = n_i; }
+        }
+        if (reg) { solve_walls_reg(L, p, lane, k0, kn, m_inv); wave_sync(); return; }
+    }
     int ca = 0, cb = -1, cfirst = 1, cidx = 0;
     double nx = 0, ny = 0, nMass = 0, bias = 0, jBiasAcc = 0.0, jnAcc = 0, bounce = 0;
     if (own) {   // [CP cpArbiterPreStep]
