@@ -20,13 +20,14 @@
 //   physics_env              pymunk Space.step -> [CP cpSpaceStep]  (call site base_env.py:392)
 //   termination_captured     BaseEnv._termination_criterion       src/environments/base_env.py:521-554
 //
-// One translation unit: this file includes cat_sim_{common,geometry,fan,physics,scheduler}.h inside its anonymous namespace, then cat_sim_host.h.
+// One translation unit: this file includes cat_sim_{common,reward,geometry,fan,physics,scheduler}.h inside its anonymous namespace, then cat_sim_host.h.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +43,7 @@
 
 namespace {
 #include "cat_sim_common.h"
+#include "cat_sim_reward.h"
 #include "cat_sim_geometry.h"
 #include "cat_sim_fan.h"
 #include "cat_sim_physics.h"

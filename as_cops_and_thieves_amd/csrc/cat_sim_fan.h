@@ -210,7 +210,7 @@ __device__ __forceinline__ SetupRow setup_row(const double *pos, const Params &p
 }
 
 template <class D>
-__device__ void agent_setup(const Lds &L, const Params &p, const GridDesc &gd, int lane, const SetupRow &row)
+__device__ __forceinline__ void agent_setup(const Lds &L, const Params &p, const GridDesc &gd, int lane, const SetupRow &row)
 {
     const int A = D::A(p), R = D::R(p);
     const double r2 = p.ray_radius;
@@ -376,7 +376,7 @@ __device__ __forceinline__ void tree_walls_result(const Lds &L, const Params &p,
 // One 64-ray chunk c (agent c / cpa, rays (c % cpa) * 64 ...) of the env whose env area is in L; the scratch
 // union of L is the calling wave's.  Writes the chunk's observations to the env's output staging.
 template <class D, bool kRowGate = false>
-__device__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int lane,
+__device__ __forceinline__ void fan_chunk(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int lane,
                           int S, float cmax, int rew_mode, int c, PhaseClock &pc)
 {
     const int A = D::A(p), R = D::R(p);
@@ -833,7 +833,7 @@ __device__ __forceinline__ unsigned fan_slot(const Lds &L, const Params &p, cons
 // ACTIVE rays run the position-major fan of fan_chunk with the origin, the "inside" walls and the roster side per lane.
 // Requires (cat_create): every candidate list fits a four-byte row (fields of wall id + 1), shape ids S + A fit 6 bits, R <= kGroupRays.
 template <class D, bool kRowGate = false>
-__device__ void fan_group(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int lane,
+__device__ __forceinline__ void fan_group(const Lds &L, const Params &p, const LaunchArgs &la, const GridDesc &gd, long long env, int lane,
                           int S, float cmax, int rew_mode, int g, int gsz, PhaseClock &pc)
 {
     const int A = D::A(p), R = D::R(p);
@@ -1034,7 +1034,7 @@ __device__ void fan_group(const Lds &L, const Params &p, const LaunchArgs &la, c
 // Cop.reward / Thief.reward (cop.py:49-75, thief.py:48-69; lane = agent) from the per-agent minimum the
 // chunks left in L.dmin, and the f16 team positions (observation_spaces.py:92-95: positions BEFORE Space.step).
 template <class D>
-__device__ void rewards_and_positions(const Lds &L, const Params &p, const LaunchArgs &la, int lane, int rew_mode,
+__device__ __forceinline__ void rewards_and_positions(const Lds &L, const Params &p, const LaunchArgs &la, int lane, int rew_mode,
                                       int captured, int timeout, GAS const float *cop_lut, GAS const float *thief_lut, LateOut &late)
 {
     const int A = D::A(p);
@@ -1045,6 +1045,8 @@ __device__ void rewards_and_positions(const Lds &L, const Params &p, const Launc
         float r;
         if (captured) r = is_cop ? 1.0f : -1.0f;
         else if (timeout) r = is_cop ? -1.0f : 1.0f;
+        // (computing it instead -- reward_arith_f16, cat_sim_reward.h: equal to both tables at every distance -- was built and measured: the arithmetic on the slot's last
+        // link costs more than the cold table line, 30.7 against 30.2 us per launch)
         else if (my_dmin < 0x10000u) r = (is_cop ? cop_lut : thief_lut)[my_dmin & 0x7FFFu];
         else r = is_cop ? (float)(-0.02 - 0.02) : (float)0.15;
         late.reward = r;
@@ -1111,7 +1113,7 @@ __device__ __forceinline__ void emit_observations(const Lds &L, const Params &p,
 // BaseEnv._termination_criterion (base_env.py:521-554).  The wall-only LOS query is only consulted
 // for pairs inside the capture radius, so it is evaluated only there; lanes stride the walls.
 template <class D>
-__device__ int termination_captured(const Lds &L, const Params &p, int S, int lane)
+__device__ __forceinline__ int termination_captured(const Lds &L, const Params &p, int S, int lane)
 {
     const int A = D::A(p), nc = D::n_cops(p), npairs = (A - nc) * nc;   // <= 16
     // lane = pair (thief-major, as the reference's nested loops): inside the capture radius?

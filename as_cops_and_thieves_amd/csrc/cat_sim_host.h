@@ -1495,3 +1495,29 @@ extern "C" int cat_selftest_arith(int op, const double *a, const double *b, doub
     hipLaunchKernelGGL(selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), op, a, b, out, n);
     return hipGetLastError() == hipSuccess ? CAT_OK : CAT_ERR_HIP;
 }
+
+extern "C" int cat_reward_arith_host(const float *cop_lut, const float *thief_lut, float *out)
+{
+    if (out)
+        for (int i = 0; i < 2 * 32768; i++) out[i] = (float)ra_host_f16_to_f64(reward_arith_f16(i < 32768, (unsigned)i & 0x7FFFu));
+    return cop_lut && thief_lut ? reward_arith_scan(cop_lut, thief_lut) : -1;
+}
+
+// (on demand, host only: 64 k evaluations against a copy of the handle's tables -- no kernel and no device structure knows the value)
+extern "C" int cat_reward_arith_max(const cat_sim *s)
+{
+    if (!s) return CAT_ERR_BAD_ARG;
+    std::vector<float> lut(2 * 32768);
+    if (hipSetDevice(s->device) != hipSuccess) return CAT_ERR_NO_DEVICE;
+    if (hipMemcpy(lut.data(), s->parts[0].p.cop_lut, 32768 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(lut.data() + 32768, s->parts[0].p.thief_lut, 32768 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return CAT_ERR_HIP;
+    return reward_arith_scan(lut.data(), lut.data() + 32768);
+}
+
+extern "C" int cat_debug_reward_table(const cat_sim *s, float *out, void *stream)
+{
+    if (!s || !out) return CAT_ERR_BAD_ARG;
+    if (hipSetDevice(s->device) != hipSuccess) return CAT_ERR_NO_DEVICE;
+    hipLaunchKernelGGL(reward_table_kernel, dim3(2 * 32768 / 256), dim3(256), 0, static_cast<hipStream_t>(stream), out);
+    return hipGetLastError() == hipSuccess ? CAT_OK : CAT_ERR_HIP;
+}

@@ -6,7 +6,7 @@
 // Called wave-uniformly; lane i evaluates hull edge i (ClosestT / LerpT of its Minkowski edge), the
 // closest edge is then found by a scalar scan over the per-lane results (lowest index wins ties, as
 // in the sequential loop), and every lane finishes the winning edge identically.
-__device__ int circle_poly_contact(const Lds &L, int sh, double rp, double cx, double cy, double rc, int lane,
+__device__ __forceinline__ int circle_poly_contact(const Lds &L, int sh, double rp, double cx, double cy, double rc, int lane,
                                    double &nx, double &ny, double &p1x, double &p1y, double &p2x, double &p2y)
 {
     const int fc = uni(L.fc[sh]), first = fc & 0xFFFF, count = fc >> 16;

@@ -217,16 +217,48 @@ __device__ __forceinline__ void publish_slot(const Lds &L, int wave, int lane, i
     if (lane == 0) __hip_atomic_store(&L.ctrl[4 * wave + 2], n_units, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// Write-back of one finished slot tick: rewards (cop.py / thief.py), the counters of the state record, the record itself
-// (store_rec: the one-tick kernels store it every tick, the resident rollout kernel only after its last tick) and every
-// output.  env_out indexes the output buffers: the env slot, or row t * N + env of buffers with a leading T.
+// What a slot tick leaves that is final as soon as the slot's Space.step has run -- in the unit that ran it, or in the front where a tick that ends an
+// episode under auto_reset steps and resets inside it (slot_front) -- and L.flags are written: the counters of the state record, the record itself (store_rec:
+// the one-tick kernels store it every tick, the resident rollout kernel only after its last tick, cat_step_repeat at the tick its hold rule ends the slot's
+// window) and the episode flags (emit: this tick stores outputs; fold_t: as in slot_writeback).  The scheduler kernels call this right there, before the unit
+// (the front) counts as done, so that these stores are under way long before the slot's last ray is traced: the write-back is the one phase of a slot's chain that
+// nothing follows, and every launch ends with one.  Nothing a ray-fan unit reads or writes is touched: the fan reads the tick-start snapshot (L.fpos / ftc / fleaf).
+template <class D>
+__device__ __forceinline__ void slot_record(const Lds &Ls, const Params &p, const LaunchArgs &la, int e_s, long long env_out, int lane,
+                                            int tick, bool store_rec, int step2, int captured2, int timeout2, int rcount, int fold_t = -1)
+{
+    const bool emit = fold_t < 0 || store_rec;
+    const unsigned char term = (unsigned char)(captured2 || timeout2);
+    if (lane == 0) {   // a slot that went through a reset (rcount >= 0) starts its new episode: base_env.py:350
+        Ls.cnt[0] = step2; Ls.cnt[2] = rcount >= 0 ? 0 : term;
+        if (rcount >= 0) Ls.cnt[1] = rcount;
+    }
+    if (store_rec) store_state<D>(Ls, p, e_s, lane);
+    if (tick && emit && lane == 0) {
+        if (fold_t >= 0 && la.ticks) la.ticks[env_out] = fold_t + 1;
+        if (la.out.terminated) la.out.terminated[env_out] = term;       // entity.py:146
+        if (la.out.truncated) la.out.truncated[env_out] = (unsigned char)timeout2;  // :397
+        if (la.out.winner) la.out.winner[env_out] = (signed char)(captured2 ? 0 : (timeout2 ? 1 : -1));  // :399-406
+    }
+}
+// the same from the slot's flags, for the callers that have not read them
+template <class D>
+__device__ __forceinline__ void slot_record_early(const Lds &Ls, const Params &p, const LaunchArgs &la, int e_s, int t, int T, bool rep, int lane)
+{
+    const int step2 = uni(Ls.flags[0]), captured2 = uni(Ls.flags[1]), timeout2 = uni(Ls.flags[2]), rcount = uni(Ls.flags[3]);
+    const bool last = t + 1 >= T || (rep && (captured2 || timeout2));   // (the write-back's rule)
+    slot_record<D>(Ls, p, la, e_s, rep ? (long long)e_s : (long long)t * p.N + e_s, lane, 1, last, step2, captured2, timeout2, rcount, rep ? t : -1);
+}
+
+// Write-back of one finished slot tick: rewards (cop.py / thief.py), the shared observations and every observation output; with rec_done == false (reset_kernel's
+// run_units: no Space.step precedes it) also what slot_record stores.  env_out indexes the output buffers: the env slot, or row t * N + env of buffers with a leading T.
 // fold_t >= 0 (cat_step_repeat: tick fold_t of the slot's held-action window, env_out = the env slot): the tick's rewards are added to the slot's f32
 // accumulators in LDS (a left fold in tick order, plain adds), and only the window's last tick (store_rec) stores outputs: the sums, the tick count
 // and its own observations / flags.  A tick that is not the last leaves HBM alone.
 template <class D>
 __device__ __forceinline__ void slot_writeback(const Lds &Ls, const Params &p, const LaunchArgs &la, int e_s, long long env_out, int lane,
                                                int tick, bool store_rec, int step2, int captured2, int timeout2, int rcount,
-                                               GAS const float *cop_lut, GAS const float *thief_lut, PhaseClock &pc, int fold_t = -1)
+                                               GAS const float *cop_lut, GAS const float *thief_lut, PhaseClock &pc, int fold_t = -1, bool rec_done = false)
 {
     LateOut late;
     const bool emit = fold_t < 0 || store_rec;
@@ -239,23 +271,12 @@ __device__ __forceinline__ void slot_writeback(const Lds &Ls, const Params &p, c
             if (fold_t > 0) late.reward = racc[lane] + late.reward;
             if (!store_rec) racc[lane] = late.reward;
         }
-        if (store_rec && lane == 0 && la.ticks) la.ticks[env_out] = fold_t + 1;
     }
     PHASE(pc, 17);
-    const unsigned char term = (unsigned char)(captured2 || timeout2);
-    if (lane == 0) {   // a slot that went through a reset (rcount >= 0) starts its new episode: base_env.py:350
-        Ls.cnt[0] = step2; Ls.cnt[2] = rcount >= 0 ? 0 : term;
-        if (rcount >= 0) Ls.cnt[1] = rcount;
-    }
-    if (store_rec) store_state<D>(Ls, p, e_s, lane);
+    if (!rec_done) slot_record<D>(Ls, p, la, e_s, env_out, lane, tick, store_rec, step2, captured2, timeout2, rcount, fold_t);
     PHASE(pc, 18);
     if (emit) emit_observations<D>(Ls, p, la, env_out, lane, tick, late);
     PHASE(pc, 19);
-    if (tick && emit && lane == 0) {
-        if (la.out.terminated) la.out.terminated[env_out] = term;       // entity.py:146
-        if (la.out.truncated) la.out.truncated[env_out] = (unsigned char)timeout2;  // :397
-        if (la.out.winner) la.out.winner[env_out] = (signed char)(captured2 ? 0 : (timeout2 ? 1 : -1));  // :399-406
-    }
 }
 
 // Large kernels whose inlined phases share one loop (run_units, the resident rollout's scheduler): whatever is invariant across
@@ -1116,6 +1137,7 @@ __device__ __forceinline__ void rollout_body_pool(const Params *__restrict__ pp0
             if (la.actions && lane < D::A(p)) ap = la.actions[((size_t)((!kOneTick && la.repeat) ? 0 : t) * p.N + e_s) * D::A(p) + lane];   // repeat: one row, held
             if (lane == 0) ctrl[4 * slot + 1] = 0;
             const int n2 = slot_front<D>(Ls, (ParamsK)pp0, la, K->md, K->gd, e_s, lane, ap, la.synth_tick + (unsigned long long)t, 0, pc);   // 1: Space.step to come; 0: it ran inside (reset)
+            if (n2 == 0) slot_record_early<D>(Ls, p, la, e_s, t, T, !kOneTick && la.repeat != 0, lane);   // the tick stepped and reset inside the front: its record is final
             lds_release();
             if (lane == 0) __hip_atomic_store((unsigned *)&ctrl[4 * slot], rw_make(t + 1, n2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             PHASE(pc, 3);
@@ -1153,7 +1175,7 @@ __device__ __forceinline__ void rollout_body_pool(const Params *__restrict__ pp0
             // cleared by its reader: a slot that leaves at an earlier tick than its neighbours has no entry in the ring and reserves none afterwards, so no writer
             // waits for a position of its and no reader for an entry of its -- the same state in which a slot leaves after tick T - 1.
             const bool last = t + 1 >= T || (rep && (captured2 || timeout2));
-            slot_writeback<D>(Ls, p, la, e_s, eo, lane, 1, last, step2, captured2, timeout2, rcount, lut_c, lut_t, pc, rep ? t : -1);
+            slot_writeback<D>(Ls, p, la, e_s, eo, lane, 1, last, step2, captured2, timeout2, rcount, lut_c, lut_t, pc, rep ? t : -1, true);
             wave_sync();   // the write-back has read the slot's staging and flags; the next front overwrites them
             SSPREAD(slot, 13);
             if (!last) { if (lane == 0) ctrl[4 * slot + 2] = t + 1; todo |= 1u << slot; }
@@ -1228,6 +1250,9 @@ __device__ __forceinline__ void rollout_body_pool(const Params *__restrict__ pp0
                 PHASE(pc, 9);
                 physics_env<D>(Ls, p, uni(K->md.S), lane, pc);
                 PHASE(pc, 10);
+                // (after the physics phase mark, but inside the unit's SSPREAD interval: from this change on "unit 0: duration" of tools/wave_spread.py includes the
+                // record's store -- 1.2 -> 1.7 us in the median -- and the write-back is shorter by as much; not comparable with earlier profiles)
+                slot_record_early<D>(Ls, p, la, uni(ctrl[4 * slot + 3]), uni(ctrl[4 * slot + 2]), T, !kOneTick && la.repeat != 0, lane);
                 lds_release();   // the unit's LDS writes, before it counts as done
                 SSPREAD(slot, 3);
                 int old = 0;
@@ -1413,6 +1438,13 @@ __global__ void selftest_kernel(int op, const double *a, const double *b, double
     else if (op == 2) r = (double)f64_to_f16(a[i]);
     else if (op == 3) r = (double)obs_distance_f16(a[i], b[i], 0.0, 0.0);
     out[i] = r;
+}
+
+// cat_debug_reward_table: the DEVICE build of reward_arith_f16 over every float16 distance, out[role][index] (role 0 = cop, 1 = thief)
+__global__ void reward_table_kernel(float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * 32768) out[i] = f16_to_f32(reward_arith_f16(i < 32768, (unsigned)i & 0x7FFFu));
 }
 
 thread_local char g_create_err[256] = "";

@@ -271,6 +271,15 @@ int cat_bbtree_host(const void *map_blob, size_t blob_size, double *bb_out, int 
 int cat_selftest_arith(int op, const double *in_a, const double *in_b, double *out, int n, int device,
                        void *stream);
 
+/* The non-terminal rewards as arithmetic (csrc/cat_sim_reward.h), a bit-exact restatement of the two reward tables that the kernels do not use (measured
+   slower than the table load: DESIGN 4.9) and the tests keep exact.  cat_reward_arith_host (host only, no device): writes the HOST build's value for every
+   float16 distance to out[2][32768] (role 0 = cop, 1 = thief; out may be NULL) and returns the largest index m such that it equals both given tables bit
+   for bit at every index <= m (-1: none, or a table pointer is NULL).  cat_reward_arith_max: that index for the handle's tables (computed on demand from a copy of them).
+   cat_debug_reward_table: the DEVICE build's values, one small launch, out = DEVICE pointer to [2][32768] floats. */
+int cat_reward_arith_host(const float *cop_lut, const float *thief_lut, float *out);
+int cat_reward_arith_max(const cat_sim *sim);
+int cat_debug_reward_table(const cat_sim *sim, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
