@@ -38,7 +38,7 @@ MODULES = {
                       "cat_dense_wgrad_splits": (C.c_int, [C.c_int32] * 4), "cat_dense_wgrad": _ENTRY, "cat_dense_forward": _ENTRY,
                       "cat_dense_dgrad": _ENTRY, "cat_dense_sum_chunks2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])}),
     "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY}),
-    "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])}),
+    "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]), "cat_render_positions_update": _ENTRY}),
     "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
                          "cat_episodes_segment_summary": _ENTRY}),
     "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_collect_step": _ENTRY, "cat_act_league_step": _ENTRY}),
@@ -828,6 +828,51 @@ def episodes_segment_summary(state, quota, bounds, out) -> None:
         raise ValueError(f"out must be a contiguous, 8-byte aligned uint8 tensor of at least {S} x {C.sizeof(EpisodesSummaryBlock)} bytes")
     a = EpisodesSegmentSummary(N, A, S, (C.c_int32 * (EPISODES_MAX_SEGMENTS + 1))(*start), _ptr(quota), _episodes_state(state), out.data_ptr())
     _check(lib().cat_episodes_segment_summary(C.byref(a), _stream()), "cat_episodes_segment_summary")
+
+
+# ---------------------------------------------------------------------------------------------- position statistics
+POSITIONS_OCC, POSITIONS_SEEN, POSITIONS_SPAWN = 0, 1, 2      # CAT_POSITIONS_*: the planes of ``counts``
+POSITIONS_MAX_TICKS = 65536                                    # CAT_POSITIONS_MAX_TICKS: rows of one launch
+
+
+class PositionsArgs(C.Structure):
+    """include/cat_render.h cat_render_positions_args."""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("A", C.c_int32), ("n_cops", C.c_int32),
+                ("R", C.c_int32), ("cell", C.c_int32), ("Wc", C.c_int32), ("Hc", C.c_int32), ("G", C.c_int32), ("pad", C.c_int32),
+                ("team_positions", C.c_void_p), ("terminated", C.c_void_p), ("obs_type", C.c_void_p), ("group", C.c_void_p),
+                ("quota", C.c_void_p), ("counts", C.c_void_p), ("outside", C.c_void_p), ("rows", C.c_void_p), ("done", C.c_void_p)]
+
+
+def positions_update(team_positions, terminated, obs_type, group, quota, counts, outside, rows, done, n_cops: int, cell: int) -> PositionsArgs:
+    """team_positions f16 [T, N, A, 2], terminated u8 [T, N], obs_type u8 [T, N, A, R] or None, all contiguous; group / quota int32 [N]
+    or None; counts int64 [G, 3, A, Wc, Hc], outside int64 [G, A], rows int64 [G], done int32 [N] (``positions.PositionTracker`` owns
+    them).  One launch on the current stream (capturable); T <= POSITIONS_MAX_TICKS.  Returns the checked argument block: while every
+    buffer stays where it is, ``positions_launch`` repeats the launch without the checks."""
+    import torch
+    T, N, A, _ = team_positions.shape
+    G, _, _, Wc, Hc = counts.shape
+    assert team_positions.dtype == torch.float16 and team_positions.shape == (T, N, A, 2) and team_positions.is_contiguous()
+    assert terminated.dtype == torch.uint8 and terminated.shape == (T, N) and terminated.is_contiguous()
+    R = 0
+    if obs_type is not None:
+        R = obs_type.shape[3]
+        assert obs_type.dtype == torch.uint8 and obs_type.shape == (T, N, A, R) and obs_type.is_contiguous()
+    for t in (group, quota):
+        assert t is None or (t.dtype == torch.int32 and t.shape == (N,) and t.is_contiguous())
+    assert counts.dtype == torch.int64 and counts.shape == (G, 3, A, Wc, Hc) and counts.is_contiguous()
+    assert outside.dtype == torch.int64 and outside.shape == (G, A) and outside.is_contiguous()
+    assert rows.dtype == torch.int64 and rows.shape == (G,) and done.dtype == torch.int32 and done.shape == (N,)
+    dev = counts.device
+    assert all(t is None or t.device == dev for t in (team_positions, terminated, obs_type, group, quota, outside, rows, done))
+    a = PositionsArgs(T, N, A, int(n_cops), R, int(cell), Wc, Hc, G, 0, team_positions.data_ptr(), terminated.data_ptr(), _ptr(obs_type),
+                      _ptr(group), _ptr(quota), counts.data_ptr(), outside.data_ptr(), rows.data_ptr(), done.data_ptr())
+    positions_launch(a)
+    return a
+
+
+def positions_launch(a: PositionsArgs) -> None:
+    """One launch of ``cat_render_positions_update`` with an argument block ``positions_update`` has checked."""
+    _check(lib().cat_render_positions_update(C.byref(a), _stream()), "cat_render_positions_update")
 
 
 # ---------------------------------------------------------------------------------------------- the fused act tick

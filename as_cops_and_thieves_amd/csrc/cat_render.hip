@@ -264,7 +264,178 @@ __global__ __launch_bounds__(BLOCK) void render_tiles_kernel(const cat_render_sc
 
 int fail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_frames", msg); }
 
+// ---- position statistics (cat_render_positions_update; include/cat_render.h has the counting rule) ------------------------------
+// One wave per workgroup.  A lane owns one (slot, agent) and walks its T rows serially; a wave holds floor(64 / A) whole slots, so the
+// lanes of a slot never straddle a wave and the slot's "who sees whom" is two ballots.  An agent moves a few pixels per tick, so it
+// stays in a cell for several rows: the lane keeps (cell, run length) of the plane it is adding to in registers and issues one 64-bit
+// integer atomic when the cell or the plane changes, and one at the end.  For SEEN every lane scans its OWN R type bytes once (each
+// byte of obs_type is read once) into two bits, "I see a cop" and "I see a thief".
+constexpr int PBLOCK = 64;
+constexpr uint32_t COP4 = 0x01010101u, THIEF4 = 0x02020202u;      // CAT_COP / CAT_THIEF (cat_sim.h) in every byte of a dword
+
+// non-zero iff some byte of v equals the byte repeated in code4 (exact: the classic zero-byte test on v ^ code4)
+__device__ __forceinline__ uint32_t has_byte(uint32_t v, uint32_t code4)
+{
+    const uint32_t x = v ^ code4;
+    return (x - 0x01010101u) & ~x & 0x80808080u;
+}
+
+// bit 0: some of the R bytes at p is CAT_COP; bit 1: some is CAT_THIEF.  p has any alignment (rows of R = 90 start on 2-byte
+// boundaries, an odd R on any byte): bytes and halfwords up to a 4-byte boundary, dwords up to a 16-byte one, 16-byte loads over
+// the body, then the same in reverse.  Every load lies inside [p, p + R).
+__device__ __forceinline__ uint32_t scan_types(const uint8_t *p, int R)
+{
+    const uint8_t *const end = p + R;
+    uint32_t cop = 0, thief = 0;
+    if (((uintptr_t)p & 1) && p < end) {
+        const uint32_t b = *p;
+        cop |= b == 1u; thief |= b == 2u;
+        p += 1;
+    }
+    if (((uintptr_t)p & 2) && p + 2 <= end) {
+        const uint32_t h = *(const uint16_t *)p | 0xFFFF0000u;     // (0xFF is no type code)
+        cop |= has_byte(h, COP4); thief |= has_byte(h, THIEF4);
+        p += 2;
+    }
+    while (((uintptr_t)p & 15) && p + 4 <= end) {
+        const uint32_t v = *(const uint32_t *)p;
+        cop |= has_byte(v, COP4); thief |= has_byte(v, THIEF4);
+        p += 4;
+    }
+    while (p + 16 <= end) {
+        const uint4 v = *(const uint4 *)p;
+        cop |= has_byte(v.x, COP4) | has_byte(v.y, COP4) | has_byte(v.z, COP4) | has_byte(v.w, COP4);
+        thief |= has_byte(v.x, THIEF4) | has_byte(v.y, THIEF4) | has_byte(v.z, THIEF4) | has_byte(v.w, THIEF4);
+        p += 16;
+    }
+    while (p + 4 <= end) {
+        const uint32_t v = *(const uint32_t *)p;
+        cop |= has_byte(v, COP4); thief |= has_byte(v, THIEF4);
+        p += 4;
+    }
+    if (p + 2 <= end) {
+        const uint32_t h = *(const uint16_t *)p | 0xFFFF0000u;
+        cop |= has_byte(h, COP4); thief |= has_byte(h, THIEF4);
+        p += 2;
+    }
+    if (p < end) {
+        const uint32_t b = *p;
+        cop |= b == 1u; thief |= b == 2u;
+    }
+    return (cop ? 1u : 0u) | (thief ? 2u : 0u);
+}
+
+__device__ __forceinline__ void add64(int64_t *p, unsigned int v) { atomicAdd((unsigned long long *)p, (unsigned long long)v); }
+
+__global__ __launch_bounds__(PBLOCK) void positions_update_kernel(const cat_render_positions_args a, int slots_per_wave)
+{
+    const int lane = threadIdx.x, A = a.A;
+    const int sw = lane / A, ag = lane - sw * A;            // slot of the wave, agent
+    const long n = (long)blockIdx.x * slots_per_wave + sw;
+    const bool active = sw < slots_per_wave && n < a.N;
+    int g = -1, quota = 0, done = 0;
+    if (active) {
+        g = a.group ? a.group[n] : 0;
+        if (g >= a.G) g = -1;                               // no group of the buffers: not counted (and never an index)
+        if (a.quota) quota = a.quota[n];
+        done = a.done[n];
+    }
+    const bool limited = a.quota != nullptr, scan = a.obs_type != nullptr;
+    const bool cop = ag < a.n_cops;
+    // the lanes of the other role in my slot
+    unsigned long long opp = 0;
+    if (active) {
+        const int first = sw * A + (cop ? a.n_cops : 0), count = cop ? A - a.n_cops : a.n_cops;
+        if (count > 0) opp = ((1ull << count) - 1ull) << first;         // first + count <= 64 and count <= 16
+    }
+    const size_t cells = (size_t)a.Wc * (size_t)a.Hc, plane = (size_t)A * cells;
+    int64_t *const mine = g >= 0 ? a.counts + ((size_t)g * 3 * A + ag) * cells : nullptr;    // my cells of plane OCC; plane p is p * plane further
+    const uint32_t *const pos = (const uint32_t *)a.team_positions;
+    long run_off = -1, seen_off = -1;                       // the cell (with its plane) of the run under way
+    unsigned int run_n = 0, seen_n = 0, out_n = 0, rows_n = 0;
+    for (int t = 0; t < a.T; ++t) {
+        const size_t row = (size_t)t * (size_t)a.N + (size_t)n;
+        const bool counted = g >= 0 && (!limited || done < quota);      // the same in every lane of a slot
+        bool term = false;
+        uint32_t xy = 0;
+        if (counted) {
+            term = a.terminated[row] != 0;
+            xy = pos[row * A + ag];
+        }
+        uint32_t bits = 0;
+        if (scan && counted && !term) bits = scan_types(a.obs_type + (row * A + ag) * (size_t)a.R, a.R);
+        const unsigned long long sees_cop = __ballot(bits & 1u), sees_thief = __ballot(bits & 2u);
+        if (counted) {
+            rows_n += 1;
+            done += term;
+            const uint32_t xb = xy & 0xFFFFu, yb = xy >> 16;
+            const float x = (float)__builtin_bit_cast(_Float16, (uint16_t)xb), y = (float)__builtin_bit_cast(_Float16, (uint16_t)yb);
+            bool valid = (xb & 0x7C00u) != 0x7C00u && (yb & 0x7C00u) != 0x7C00u && x >= 0.0f && y >= 0.0f;
+            int cx = 0, cy = 0;
+            if (valid) {                                    // a finite f16 is below 65536: the int is exact
+                cx = (int)floorf(x) / a.cell;
+                cy = (int)floorf(y) / a.cell;
+                valid = cx < a.Wc && cy < a.Hc;
+            }
+            if (!valid) out_n += 1;
+            else {
+                const long c = (long)cx * a.Hc + cy;
+                const long off = term ? (long)(CAT_POSITIONS_SPAWN * plane) + c : c;
+                if (off == run_off) run_n += 1;
+                else {
+                    if (run_n) add64(mine + run_off, run_n);
+                    run_off = off; run_n = 1;
+                }
+                if (!term && ((cop ? sees_cop : sees_thief) & opp)) {
+                    const long soff = (long)(CAT_POSITIONS_SEEN * plane) + c;
+                    if (soff == seen_off) seen_n += 1;
+                    else {
+                        if (seen_n) add64(mine + seen_off, seen_n);
+                        seen_off = soff; seen_n = 1;
+                    }
+                }
+            }
+        }
+    }
+    if (run_n) add64(mine + run_off, run_n);
+    if (seen_n) add64(mine + seen_off, seen_n);
+    if (out_n) add64(a.outside + (size_t)g * A + ag, out_n);
+    if (active && ag == 0) a.done[n] = done;
+    // rows[g]: the slots of a wave mostly share one group -- one atomic per group and wave
+    const bool has_rows = ag == 0 && rows_n != 0;
+    unsigned long long pending = __ballot(has_rows);
+    while (pending) {                                       // (uniform over the wave)
+        const int leader = __ffsll((long long)pending) - 1;
+        const int gl = __shfl(g, leader);
+        const bool same = has_rows && g == gl;
+        unsigned int sum = same ? rows_n : 0u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        if (lane == leader) add64(a.rows + gl, sum);
+        pending &= ~__ballot(same);
+    }
+}
+
+int pfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_positions_update", msg); }
+
 }   // namespace
+
+extern "C" int cat_render_positions_update(const cat_render_positions_args *a, void *stream)
+{
+    if (!a) return pfail("NULL arguments");
+    if (a->T < 1 || a->T > CAT_POSITIONS_MAX_TICKS || a->N <= 0 || a->A <= 0 || a->A > CAT_RENDER_MAX_AGENTS || a->n_cops < 0 || a->n_cops > a->A)
+        return pfail("bad dimensions");
+    if (a->cell < 1) return pfail("cell must be >= 1");
+    if (a->Wc < 1 || a->Hc < 1) return pfail("the grid needs Wc >= 1 and Hc >= 1");
+    if (a->G < 1) return pfail("G must be >= 1");
+    if (!a->team_positions || !a->terminated || !a->counts || !a->outside || !a->rows || !a->done) return pfail("a required buffer is NULL");
+    if ((uintptr_t)a->team_positions & 3) return pfail("team_positions must be 4-byte aligned");
+    if (a->obs_type && a->R < 1) return pfail("obs_type needs R >= 1");
+    const int spw = PBLOCK / a->A;
+    const long blocks = ((long)a->N + spw - 1) / spw;
+    hipLaunchKernelGGL(positions_update_kernel, dim3((unsigned)blocks), dim3(PBLOCK), 0, (hipStream_t)stream, *a, spw);
+    return launched("cat_render_positions_update");
+}
 
 extern "C" int cat_render_abi_version(void) { return CAT_RENDER_ABI_VERSION; }
 extern "C" const char *cat_render_last_error(void) { return g_err; }

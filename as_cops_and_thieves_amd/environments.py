@@ -309,6 +309,12 @@ class VecCopsEnv:
     is given each row's tick count, so lengths, the histogram and the outcomes stay in env ticks; a return is the f64 sum of the fp32
     window sums (``EpisodeTracker.update``).  ``out["ticks"]`` is written by repeat calls only: after a later one-tick step it still
     holds the last repeat call's counts.
+
+    ``track_positions=CELL`` (needs ``auto_reset``): a ``positions.PositionTracker`` on the device adds the rows of ``step``, ``step_raw``
+    (one row per call, whatever ``repeat`` is) and ``rollout_random`` into occupancy / exposure / spawn maps on a grid of CELL x CELL pixels
+    over the batch's largest map window (``position_stats()``, ``position_tracker``); ``position_exposure=False`` leaves ``obs_type`` unread
+    and the SEEN plane zero; ``position_groups`` is the tracker's number of groups (``PositionTracker.set_groups``; every slot starts in
+    group 0).  An explicit ``reset`` feeds nothing.  Off by default: no buffer, no launch.
     """
 
     metadata = BaseEnv.metadata
@@ -318,11 +324,17 @@ class VecCopsEnv:
                  num_rays: int = 64, max_step_count: int = 400, time_step: float = 1 / 60.0,
                  auto_reset: bool = True, device=None, seed: int = 1, env_id_offset: int = 0,
                  physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True, query_order: str = "index",
-                 track_episodes: bool = False, frame_skip: int = 1):
+                 track_episodes: bool = False, frame_skip: int = 1, track_positions: Optional[int] = None,
+                 position_exposure: bool = True, position_groups: int = 1):
         gate = gate_mode(bbtree_gate, query_order)   # (before anything touches a device)
         self.frame_skip = check_repeat(frame_skip, "frame_skip")
         if track_episodes and not auto_reset:
             raise ValueError("track_episodes=True needs auto_reset=True: the accounting restarts a slot's episode at its terminal tick")
+        if track_positions is not None:
+            if not auto_reset:
+                raise ValueError("track_positions needs auto_reset=True: a terminal row counts as the spawn of the slot's next episode")
+            if isinstance(track_positions, bool) or not isinstance(track_positions, (int, np.integer)) or track_positions < 1:
+                raise ValueError(f"track_positions is the cell size in pixels, an integer >= 1, got {track_positions!r}")
         self.maps: List[Map] = list(maps) if isinstance(maps, (list, tuple)) else [maps]
         m0 = self.maps[0]
         for m in self.maps[1:]:
@@ -361,7 +373,13 @@ class VecCopsEnv:
         if track_episodes:
             from .episodes import EpisodeTracker
             self._tracker = EpisodeTracker(num_envs, self.possible_agents, max_step_count, self.device)
+        if track_episodes or track_positions is not None:
             self._tracked_rows: Dict[str, torch.Tensor] = {}
+        self._positions, self._exposure = None, bool(position_exposure)
+        if track_positions is not None:
+            from .positions import PositionTracker
+            window = (max(int(c.window[0]) for c in self._compiled), max(int(c.window[1]) for c in self._compiled))
+            self._positions = PositionTracker(num_envs, self.possible_agents, m0.cops_count, window, int(track_positions), int(position_groups), self.device)
 
     # episode accounting
     @property
@@ -383,9 +401,25 @@ class VecCopsEnv:
             self._tracker.clear()
         return stats
 
+    @property
+    def position_tracker(self):
+        """The ``PositionTracker`` that ``step`` / ``step_raw`` / ``rollout_random`` feed."""
+        if self._positions is None:
+            raise RuntimeError("this VecCopsEnv was built without track_positions=CELL: it keeps no position statistics")
+        return self._positions
+
+    def position_stats(self, clear: bool = False) -> list:
+        """``PositionTracker.summary()`` of the rows counted since the last clear (one synchronisation)."""
+        stats = self.position_tracker.summary()
+        if clear:
+            self._positions.clear()
+        return stats
+
     def _track(self, out, ticks=None) -> None:
         if self._tracker is not None:
             self._tracker.update(out["reward"], out["terminated"], out["truncated"], out["winner"], ticks=ticks)
+        if self._positions is not None:     # a frame-skip row counts once, at the window's last position
+            self._positions.update(out["team_positions"], out["terminated"], out["obs_type"] if self._exposure else None)
 
     def _repeat(self, repeat) -> int:
         """The ``repeat`` argument of ``step`` / ``step_raw``, checked: None is the constructor's ``frame_skip``."""
@@ -499,12 +533,12 @@ class VecCopsEnv:
         if ticks < 1:
             raise ValueError("ticks must be >= 1")
         done, cap = 0, 65536
-        if self._tracker is not None:
-            A = len(self.possible_agents)
-            cap = max(1, min(cap, self.TRACKED_ROLLOUT_BYTES // (self.num_envs * (4 * A + 3))))
+        keys = self._tracked_keys()
+        if keys:
+            cap = max(1, min(cap, self.TRACKED_ROLLOUT_BYTES // (self.num_envs * self._tracked_row_bytes(keys))))
         while ticks - 1 - done > 0:
             n = min(cap, ticks - 1 - done)
-            rows = {} if self._tracker is None else self._tracked_rollout_rows(min(cap, ticks - 1), n)
+            rows = {} if not keys else self._tracked_rollout_rows(min(cap, ticks - 1), n, keys)
             self._sim.rollout_fused(n, None, tick=tick0 + done, auto_reset=self.auto_reset, out=rows)
             self._track(rows)
             done += n
@@ -513,14 +547,27 @@ class VecCopsEnv:
         self._sim.check_errors()   # thousands of ticks went by inside one launch: a flag raised by any of them ends the run here, not never
         return out
 
-    def _tracked_rollout_rows(self, rows: int, n: int) -> Dict[str, torch.Tensor]:
-        """The first ``n`` rows of the ``[rows, N, ...]`` reward / flag buffers of a tracked ``rollout_random`` (kept, and grown when a
-        longer chunk comes)."""
+    def _tracked_keys(self) -> tuple:
+        """The output rows a tracked ``rollout_random`` keeps: the episode tracker's reward / flags, and with ``track_positions`` the
+        terminated flags, ``team_positions`` and (with exposure) ``obs_type``."""
+        keys = ("reward", "terminated", "truncated", "winner") if self._tracker is not None else ()
+        if self._positions is not None:
+            keys += tuple(k for k in ("terminated", "team_positions") if k not in keys) + (("obs_type",) if self._exposure else ())
+        return keys
+
+    def _tracked_row_bytes(self, keys) -> int:
+        """Bytes one env-tick of the kept rows takes (4 A + 3 for the episode tracker's alone)."""
         from .sim import _OUT_SPEC
-        keys = ("reward", "terminated", "truncated", "winner")
-        if not self._tracked_rows or self._tracked_rows["reward"].shape[0] < rows:
-            N, A = self.num_envs, len(self.possible_agents)
-            self._tracked_rows = {k: torch.zeros((rows,) + tuple(_OUT_SPEC[k][0](N, A, 0)), dtype=_OUT_SPEC[k][1], device=self.device)
+        A, R = len(self.possible_agents), self._cfg.n_rays
+        return sum(int(np.prod(_OUT_SPEC[k][0](1, A, R))) * torch.empty((), dtype=_OUT_SPEC[k][1]).element_size() for k in keys)
+
+    def _tracked_rollout_rows(self, rows: int, n: int, keys=("reward", "terminated", "truncated", "winner")) -> Dict[str, torch.Tensor]:
+        """The first ``n`` rows of the ``[rows, N, ...]`` buffers of a tracked ``rollout_random`` (kept, and grown when a longer chunk
+        comes)."""
+        from .sim import _OUT_SPEC
+        if not self._tracked_rows or self._tracked_rows[keys[0]].shape[0] < rows:
+            N, A, R = self.num_envs, len(self.possible_agents), self._cfg.n_rays
+            self._tracked_rows = {k: torch.zeros((rows,) + tuple(_OUT_SPEC[k][0](N, A, R)), dtype=_OUT_SPEC[k][1], device=self.device)
                                   for k in keys}
         return {k: self._tracked_rows[k][:n] for k in keys}
 

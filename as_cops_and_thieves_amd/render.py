@@ -117,6 +117,75 @@ def render_frame_reference(cmap: CompiledMap, positions: np.ndarray, n_cops: int
     return img
 
 
+def _heat_palette() -> np.ndarray:
+    """256 colours from white (level 0) over yellow, orange and red to dark red (level 255): integer interpolation between anchors."""
+    anchors = [(0, (255, 255, 255)), (64, (255, 237, 160)), (128, (254, 178, 76)), (192, (240, 59, 32)), (255, (128, 0, 38))]
+    pal = np.zeros((256, 3), dtype=np.uint8)
+    for (l0, c0), (l1, c1) in zip(anchors, anchors[1:]):
+        for level in range(l0, l1 + 1):
+            pal[level] = [c0[k] + (c1[k] - c0[k]) * (level - l0) // (l1 - l0) for k in range(3)]
+    return pal
+
+
+HEAT_PALETTE = _heat_palette()
+HEATMAP_PLANES = ("occ", "seen", "hidden", "spawn")     # hidden = occ - seen
+
+
+def render_heatmap(cmap: CompiledMap, plane: np.ndarray, cell: int, vmax: Optional[int] = None, palette: np.ndarray = HEAT_PALETTE) -> np.ndarray:
+    """A count map of ``positions.PositionTracker`` (one ``[Wc, Hc]`` plane of one group and agent, x-major) over the map's window as a
+    ``(W, H, 3)`` uint8 frame, on the host: pixel (x, y) is ``palette[min(255, plane[x // cell, y // cell] * 255 // vmax)]`` (level 0 when
+    ``vmax == 0``; ``vmax`` None = the plane's maximum), and the walls of ``render_rgb_array`` are drawn on top in their grey."""
+    W, H = int(cmap.window[0]), int(cmap.window[1])
+    plane = np.asarray(plane)
+    cell = int(cell)
+    if plane.ndim != 2 or cell < 1 or plane.shape[0] * cell < W or plane.shape[1] * cell < H:
+        raise ValueError(f"render_heatmap: a plane of {plane.shape} cells of {cell} px does not cover the {W}x{H} window")
+    palette = np.asarray(palette, dtype=np.uint8)
+    if palette.shape != (256, 3):
+        raise ValueError("render_heatmap: the palette must be [256, 3] uint8")
+    plane = plane.astype(np.int64)
+    vmax = int(plane.max()) if vmax is None else int(vmax)
+    level = np.minimum(255, plane * 255 // vmax) if vmax > 0 else np.zeros_like(plane)
+    level = np.clip(level, 0, 255)
+    img = palette[level[np.arange(W)[:, None] // cell, np.arange(H)[None, :] // cell]]
+    walls = render_rgb_array(cmap, np.zeros((0, 2)), 0, 0.0)
+    grey = (walls == 60).all(axis=2)
+    img[grey] = (60, 60, 60)
+    return img
+
+
+def write_heatmaps(directory, tracker, maps, group_names: Optional[Sequence[str]] = None, group_maps: Optional[Sequence[int]] = None,
+                   vmax: Optional[int] = None, palette: np.ndarray = HEAT_PALETTE, npz_name: str = "positions.npz") -> dict:
+    """The maps of a ``positions.PositionTracker`` as pictures: ``{group}/{agent}_{occ|seen|hidden|spawn}.png`` (``write_png`` of
+    ``render_heatmap``; hidden = occ - seen) under ``directory`` and the raw counts in ``positions.npz`` (``counts``, ``outside``, ``rows``,
+    ``done``, ``cell``, ``agents``, ``groups``).  ``maps``: the batch's maps (``Map`` or ``CompiledMap``; one or a list); ``group_maps[g]``:
+    the map group g is drawn over (default: the first); ``group_names``: the directory names (default ``group_0`` ..; None for a group
+    that gets no pictures).  One
+    synchronisation (``tracker.counts()``).  Returns those counts."""
+    from pathlib import Path
+    directory = Path(directory)
+    maps = list(maps) if isinstance(maps, (list, tuple)) else [maps]
+    compiled = [m if isinstance(m, CompiledMap) else m.compile() for m in maps]
+    G = tracker.G
+    names = [f"group_{g}" for g in range(G)] if group_names is None else [None if n is None else str(n) for n in group_names]
+    which = [0] * G if group_maps is None else [int(m) for m in group_maps]
+    if len(names) != G or len(which) != G or any(not 0 <= m < len(compiled) for m in which):
+        raise ValueError(f"write_heatmaps: {G} groups need {G} names and {G} map indices below {len(compiled)}")
+    c = tracker.counts()
+    directory.mkdir(parents=True, exist_ok=True)
+    np.savez_compressed(directory / npz_name, counts=c["counts"], outside=c["outside"], rows=c["rows"], done=c["done"],
+                        cell=np.int64(tracker.cell), agents=np.array(tracker.agents), groups=np.array(["" if n is None else n for n in names]))
+    for g in range(G):
+        if names[g] is None:
+            continue
+        (directory / names[g]).mkdir(parents=True, exist_ok=True)
+        for i, aid in enumerate(tracker.agents):
+            occ, seen, spawn = c["counts"][g, 0, i], c["counts"][g, 1, i], c["counts"][g, 2, i]
+            for plane_name, plane in zip(HEATMAP_PLANES, (occ, seen, occ - seen, spawn)):
+                write_png(directory / names[g] / f"{aid}_{plane_name}.png", render_heatmap(compiled[which[g]], plane, tracker.cell, vmax, palette))
+    return c
+
+
 def write_png(path, frame: np.ndarray) -> None:
     """Store a ``(W, H, 3)`` uint8 frame (x-major, as ``render_rgb_array`` returns it) as an 8-bit RGB PNG of W x H pixels, with
     ``zlib`` and ``struct`` only: one IDAT chunk, filter type 0 on every row."""

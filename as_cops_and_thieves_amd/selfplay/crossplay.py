@@ -8,6 +8,8 @@ the thieves of file j play the first episode of each slot (``self_play.evaluate_
 pass, so a K x K table takes ceil(K^2 / 32) passes instead of K^2.  ``--random-column`` adds a last column: thieves acting uniformly at
 random, a fixed yardstick.  ``payoff.json`` holds the file lists and the matrices ``cop_win_rate``, ``cop_wins``, ``thief_wins``,
 ``timeouts`` (the three counts add up to the episodes of a cell) and ``mean_length`` (ticks of the counted episodes), rows = cop files.
+``--heatmaps DIR [--cell C]``: position statistics of the counted episodes, one group per cell of the table -- occupancy, exposure, hidden
+and spawn maps per agent under ``DIR/{cop file}__{thief file}/`` and the raw counts in ``DIR/positions.npz`` (``positions.py``).
 """
 from __future__ import annotations
 
@@ -36,10 +38,13 @@ def policy_files(directory, role: str) -> List[Path]:
 def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool = False, greedy: bool = False, num_rays: int = 64,
               n_cops: Optional[int] = None, n_thieves: Optional[int] = None, max_step_count: int = 2000, seed: int = 0, device=None,
               fused: Union[str, bool] = "kernel", normalize_inputs: bool = False, env_factory=None, log=None,
-              frame_skip: int = 1) -> Dict[str, object]:
+              frame_skip: int = 1, heatmaps=None, cell: int = 8) -> Dict[str, object]:
     """``cops`` / ``thieves``: an archive directory or a list of checkpoint files.  ``episodes`` slots per cell; sampled actions, or the
     largest logit with ``greedy``.  ``env_factory(num_envs, seed)``: build the env some other way (``map_name`` etc. are then unused).
     ``frame_skip``: env ticks per decision (``evaluate_league``); ``mean_length`` stays in env ticks.
+    ``heatmaps``: a directory -- the env is built with ``track_positions=cell`` and one group per cell of a pass, and every pass writes its
+    cells' heatmaps there (``render.write_heatmaps``; ``positions.npz`` holds the first pass, ``positions_pass{p}.npz`` the later ones).  An
+    ``env_factory``'s env must then bring a ``position_tracker`` of at least as many groups as a pass has segments.
     The sampled actions draw from torch's global generator: seed it for a reproducible table.  Returns what the module's docstring lists."""
     cop_files = [Path(f) for f in (cops if isinstance(cops, (list, tuple)) else policy_files(cops, "cop"))]
     thief_files = [Path(f) for f in (thieves if isinstance(thieves, (list, tuple)) else policy_files(thieves, "thief"))]
@@ -54,7 +59,9 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
     if env_factory is None:
         from ..environments import VecCopsEnv
         from ..maps import load_preset
-        env = VecCopsEnv(load_preset(map_name, n_cops, n_thieves), N, num_rays=num_rays, max_step_count=max_step_count, seed=seed, device=device)
+        track = {} if heatmaps is None else {"track_positions": int(cell), "position_groups": per_pass}
+        env = VecCopsEnv(load_preset(map_name, n_cops, n_thieves), N, num_rays=num_rays, max_step_count=max_step_count, seed=seed, device=device,
+                         **track)
     else:
         env = env_factory(N, seed)
     agents = list(env.possible_agents)
@@ -92,7 +99,13 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
             quota.append(0)
         loaded.clear()
         actor.set_matchups(segments)
-        res = evaluate_league(env, player, quota, frame_skip=frame_skip)
+        res = evaluate_league(env, player, quota, frame_skip=frame_skip, **({} if heatmaps is None else {"positions": True}))
+        if heatmaps is not None:
+            from ..render import write_heatmaps
+            tracker = env.position_tracker
+            names = [f"{cop_files[i].stem}__{RANDOM if j == RANDOM else thief_files[j].stem}" for i, j in chunk]
+            write_heatmaps(heatmaps, tracker, env.maps, group_names=names + [None] * (tracker.G - len(names)),
+                           npz_name="positions.npz" if passes == 0 else f"positions_pass{passes}.npz")
         length = res["length"].cpu()
         for s, (i, j) in enumerate(chunk):
             col = columns.index(j)
@@ -123,10 +136,12 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", type=Path, required=True)
     ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat)")
+    ap.add_argument("--heatmaps", type=Path, default=None, metavar="DIR", help="write per-cell occupancy / exposure / spawn heatmaps and positions.npz there")
+    ap.add_argument("--cell", type=int, default=8, help="with --heatmaps: the grid's cell size in pixels")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     res = crossplay(args.cops, args.thieves, args.map, args.episodes, args.random_column, args.greedy, args.rays, args.n_cops, args.n_thieves,
-                    args.max_step_count, args.seed, log=print, frame_skip=args.frame_skip)
+                    args.max_step_count, args.seed, log=print, frame_skip=args.frame_skip, heatmaps=args.heatmaps, cell=args.cell)
     args.out.write_text(json.dumps(res, indent=1))
     print(f"[cross-play] {len(res['cops'])} x {len(res['thieves'])} cells in {res['passes']} pass(es) -> {args.out}")
 

@@ -308,16 +308,20 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
 
 
 @torch.no_grad()
-def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1) -> Dict[str, object]:
+def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1, positions: bool = False) -> Dict[str, object]:
     """``evaluate_agents``' loop -- the first episode of every slot, one poll per tick -- under the match-ups of a ``LeagueActor``: all its
     segments play at once.  ``episodes_per_segment``: an int or one int per segment -- only the first that many slots of a segment count
     (None: all of them; 0 for a segment that merely fills the env).  Returns per segment (lists in segment order) ``cop_wins`` (winner 0),
     ``thief_wins`` (winner 1 before the step limit), ``timeouts`` (the step limit ran out; not the cops' win) -- the three add up to the
     segment's counted slots -- and ``episodes``; per slot ``winner`` (int8, -1 where nothing counted) and ``length`` (ticks of the counted
     episode, int32); and ``ticks``, the steps of the loop played.  ``frame_skip`` k > 1: one decision per ``env.step(actions, repeat=k)``;
-    ``length`` stays in env ticks (the sum of the slot's ``infos["ticks"]``), ``ticks`` counts decisions."""
+    ``length`` stays in env ticks (the sum of the slot's ``infos["ticks"]``), ``ticks`` counts decisions.
+    ``positions``: the env's ``position_tracker`` (``VecCopsEnv(track_positions=CELL, position_groups >= segments)``) is cleared and set up
+    like the accounting here -- one group per segment, a quota of the first episode of every counted slot, none of the others -- so that
+    afterwards it holds the maps of exactly the counted episodes; ``out["positions"]`` is its ``summary()``."""
     N = env.num_envs
     assert N == actor.N and actor.table is not None
+    tracker = env.position_tracker if positions else None      # (an env without one raises here, before anything is played)
     skip = _skip_kw(frame_skip)
     segments = actor.segments
     quota = episodes_per_segment
@@ -331,6 +335,10 @@ def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1) 
             assert 0 <= q <= hi - lo, (lo, hi, q)
             open_[lo + q:hi] = False
     counted = open_.clone()
+    if tracker is not None:
+        tracker.clear()
+        tracker.set_groups(bounds=[0] + [hi for _, hi in segments])
+        tracker.set_quota(open_.to(torch.int32))
     obs, _ = env.reset()
     actor.reset()
     starts = torch.ones(N, dtype=torch.bool, device=dev)
@@ -364,6 +372,8 @@ def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1) 
         out["thief_wins"].append(int(((w[lo:hi] == 1) & ~t[lo:hi]).sum()))
         out["timeouts"].append(int(((w[lo:hi] != 0) & t[lo:hi]).sum()))
         out["episodes"].append(hi - lo)
+    if tracker is not None:
+        out["positions"] = tracker.summary()
     return out
 
 
@@ -612,7 +622,7 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
                   query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False,
                   fused_eval: bool = False, league_eval: bool = False, role_training: bool = False,
-                  fused_collect: bool = False, value_norm: bool = False) -> Dict[str, object]:
+                  fused_collect: bool = False, value_norm: bool = False, position_stats: Optional[int] = None) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -645,6 +655,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     ``value_norm``: the critics train on returns normalised by running per-agent moments (``TrainerConfig.value_norm``); the joint
     checkpoints then carry each agent's moments (``vn_state``) beside its value network.
 
+    ``position_stats=CELL``: the evaluation env is built with ``track_positions=CELL`` and after every iteration's evaluation rank 0 writes
+    the heatmaps of that evaluation's rows (``render.write_heatmaps``) into ``positions_iter_{i}/`` of the run directory, then clears the
+    maps.  The simultaneous mode only (ValueError with ``role_training``); envs of an ``env_factory`` must bring their own ``position_tracker``.
+
     With an initialised ``torch.distributed`` group of W > 1 ranks this is ONE data-parallel job: ``num_envs`` is the TOTAL,
     rank r simulates ``shard_envs(num_envs, r, W)``; the trainer all-reduces its gradient | KL buffer every optimiser step (all
     ranks hold identical parameters at all times); rank 0 alone evaluates and writes files, the others wait and read them."""
@@ -657,6 +671,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     chief = rank == 0
     if role_training and multi:                  # every rank sees the same two facts: all refuse, none is left in a collective
         raise ValueError("role_training is a single-process mode: multi-rank role training is not supported")
+    if role_training and position_stats is not None:
+        raise ValueError("position_stats writes the heatmaps of the simultaneous mode's evaluations: it cannot be combined with role_training")
     if role_training and tracked_eval:
         raise ValueError("role_training books its outcomes through evaluate_league (one poll per tick): it cannot be combined with tracked_eval")
 
@@ -703,6 +719,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                                                              env_id_offset=off, query_order=query_order, track_episodes=track))
         env_factory = train_factory = make(episode_stats)
         eval_factory = make(tracked_eval)
+        if position_stats is not None:
+            eval_factory = lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
+                                                          env_id_offset=off, query_order=query_order, track_episodes=tracked_eval,
+                                                          track_positions=position_stats)
     n_local, offset = shard_envs(num_envs, rank, world)
     if multi:
         # checked on EVERY rank from the same numbers, so that all of them refuse together (a rank that raised alone would leave the others in the
@@ -721,6 +741,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     for what, e, attr in (("tracked_eval", eval_env, "episode_tracker"), ("episode_stats", env, "episode_stats")):
         if {"tracked_eval": tracked_eval, "episode_stats": episode_stats}[what] and not hasattr(e, attr):
             raise TypeError(f"{what}=True needs envs with an {attr!r} (VecCopsEnv(track_episodes=True)); the env_factory's have none")
+    if position_stats is not None and not hasattr(eval_env, "position_tracker"):
+        raise TypeError("position_stats needs an evaluation env with a 'position_tracker' (VecCopsEnv(track_positions=CELL)); the env_factory's has none")
+    if position_stats is not None:
+        eval_env.position_tracker.clear()
     role_cfg = role_cfg or {"cop": CFG_AGENT, "thief": CFG_AGENT}        # self_play_driver.py passes CFG_AGENT
     trainer = MAPPOTrainer(env, role_cfg, trainer_cfg, seed=seed, **({"split_roles": True} if role_training else {}))
     if role_training:  # per role a bank of archived opponents over the training env; one bank over the evaluation env for the booking
@@ -786,6 +810,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                 else:
                     ev = {cop: evaluate_agent(eval_env, evaluator, trainer, cop, thief, arch[thief], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval, frame_skip=trainer_cfg.frame_skip),
                           thief: evaluate_agent(eval_env, evaluator, trainer, thief, cop, arch[cop], tc, rng, log, tracked=tracked_eval, fused_eval=fused_eval, frame_skip=trainer_cfg.frame_skip)}
+                if position_stats is not None:
+                    from ..render import write_heatmaps
+                    write_heatmaps(out_dir / f"positions_iter_{it}", eval_env.position_tracker, getattr(eval_env, "maps", None) or load_preset(map_name, n_cops, n_thieves))
+                    eval_env.position_tracker.clear()
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -895,6 +923,8 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one per GPU: --envs is the TOTAL, sharded across them")
     ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat) in training and in the evaluations; above 1 "
                     "--timesteps, --horizon and the schedule options count decisions")
+    ap.add_argument("--position-stats", type=int, default=None, metavar="CELL", help="occupancy / exposure / spawn heatmaps of every iteration's evaluation "
+                    "on a grid of CELL x CELL pixels, written to positions_iter_N/ in --out")
     ap.add_argument("--fused-collect", action="store_true", help="collect the training rollouts through the one-launch fused act kernel "
                     "(TrainerConfig.fused_collect: a GPU, bf16, the recurrent pair, 64 or 90 rays)")
     ap.add_argument("--value-norm", action="store_true", help="train the critics on returns normalised by running per-agent moments "
@@ -927,7 +957,8 @@ def main() -> None:
                         eval_envs=args.eval_envs, seed=args.seed, log=print if rank == 0 else (lambda *a, **k: None),
                         query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval,
                         league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}),
-                        **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}))
+                        **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}),
+                        **({"position_stats": args.position_stats} if args.position_stats is not None else {}))
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

@@ -37,8 +37,11 @@ def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_st
 @torch.no_grad()
 def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, ticks: int = 2000, rays: bool = False, seed: int = 0,
           num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None, n_thieves: Optional[int] = None, device=None,
-          log=print, fused_act: bool = False, greedy: bool = False, frame_skip: int = 1) -> Dict[str, object]:
-    """``frame_skip`` k > 1: the policies decide once per ``env.step(actions, repeat=k)`` and one frame is drawn per decision; ``ticks`` is then
+          log=print, fused_act: bool = False, greedy: bool = False, frame_skip: int = 1, heatmap: Optional[int] = None) -> Dict[str, object]:
+    """``heatmap=CELL``: a ``positions.PositionTracker`` on a grid of CELL x CELL pixels is fed every decision's rows of the slots still
+    playing (this env does not auto-reset, so the terminal row holds the episode's last position and counts as occupancy, and there is no
+    spawn map), and ``heatmaps/`` next to the clips receives the pictures and ``positions.npz`` (``render.write_heatmaps``).
+    ``frame_skip`` k > 1: the policies decide once per ``env.step(actions, repeat=k)`` and one frame is drawn per decision; ``ticks`` is then
     the most decisions played, a slot's ``length`` stays in env ticks (the sum of its ``infos["ticks"]``).
     ``fused_act``: no trainer is built -- a ``PolicyActor`` reads the checkpoint's policy blocks and acts (on a GPU: one launch per tick,
     ``include/cat_act.h``).  ``greedy`` (with ``fused_act``): the most probable action instead of a draw."""
@@ -69,6 +72,11 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
             if open_host[k]:
                 write_png(dirs[k] / f"frame_{t:05d}.png", frames[k, :W, :H])
 
+    tracker = None
+    if heatmap is not None:
+        from ..positions import PositionTracker
+        tracker = PositionTracker(N, env.possible_agents, len(env.cops), (W, H), heatmap, 1, env.device)
+        never = torch.zeros(N, dtype=torch.uint8, device=env.device)
     obs, _ = env.reset()
     who = actor if actor is not None else runner
     starts = torch.ones(N, dtype=torch.bool, device=who.device)
@@ -86,6 +94,10 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
         obs, _, terms, _, infos = env.step(actions, **skip)
         starts = torch.zeros_like(starts)
         save(t, open_host)
+        if tracker is not None:
+            raw = env.raw_outputs()
+            tracker.set_groups([0 if o else -1 for o in open_host])
+            tracker.update(raw["team_positions"], never, raw["obs_type"])
         done = terms[who.agents[0]].cpu().tolist()
         win = infos["winner"].cpu().tolist()
         if skip:
@@ -104,6 +116,9 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
               **({"fused_act": True, "greedy": bool(greedy)} if fused_act else {}), **({"frame_skip": frame_skip} if skip else {}),
               "slots": [{"env": k, "winner": winner[k], "length": length[k], "terminated": ended[k], "frames": frames_of[k]} for k in slots]}
     (out_dir / "episode.json").write_text(json.dumps(result, indent=1))
+    if tracker is not None:
+        from ..render import write_heatmaps
+        write_heatmaps(out_dir / "heatmaps", tracker, env.maps)
     for s in result["slots"]:
         log(f"[watch] env {s['env']}: {'winner ' + str(s['winner']) if s['terminated'] else 'no termination'} after {s['length']} ticks")
     env.close()
@@ -125,13 +140,17 @@ def main(argv=None) -> int:
                     "GPU one launch per tick)")
     ap.add_argument("--greedy", action="store_true", help="with --fused-act: the most probable action instead of a draw")
     ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat); one frame per decision, --ticks counts decisions")
+    ap.add_argument("--heatmap", type=int, default=None, metavar="CELL", help="also write occupancy / exposure heatmaps of the episodes played, on a "
+                    "grid of CELL x CELL pixels, into heatmaps/ next to the clips")
     args = ap.parse_args(argv)
+    if args.heatmap is not None and args.heatmap < 1:
+        ap.error("--heatmap must be >= 1")
     if args.envs < 1 or args.ticks < 1 or args.frame_skip < 1:
         ap.error("--envs, --ticks and --frame-skip must be >= 1")
     if args.greedy and not args.fused_act:
         ap.error("--greedy needs --fused-act")
     watch(args.map, args.envs, args.out, args.checkpoint, args.ticks, args.rays, args.seed, args.num_rays, args.max_steps,
-          fused_act=args.fused_act, greedy=args.greedy, frame_skip=args.frame_skip)
+          fused_act=args.fused_act, greedy=args.greedy, frame_skip=args.frame_skip, heatmap=args.heatmap)
     return 0
 
 

@@ -71,6 +71,53 @@ int cat_render_abi_version(void);
 const char *cat_render_last_error(void);
 int cat_render_frames(const cat_render_scene *scene, const cat_render_args *a, void *stream);
 
+/*
+ * Position statistics: where the agents spend their time.  cat_render_positions_update adds T >= 1 consecutive rows of N slots (the
+ * env core's team_positions / obs_type / terminated buffers, with a leading T from cat_rollout_fused) into per-group count maps on a
+ * grid of cell x cell pixels, in ONE launch without allocation or synchronisation (capturable with the env tick it follows).
+ * positions.PositionTracker (NumPy) defines every number.
+ *
+ *   Grid: Wc = ceil(W / cell), Hc = ceil(H / cell) cells, W x H the largest map window of the batch; all groups share it.
+ *   group[n] in 0 .. G-1 is the group of slot n, anything else (-1) means "not counted"; NULL = every slot in group 0.
+ *   counts [G][3][A][Wc][Hc] int64, x-major like the frames, planes CAT_POSITIONS_OCC / _SEEN / _SPAWN; outside [G][A] int64;
+ *   rows [G] int64 slot-rows counted; done [N] int32 terminal rows the slot has had.
+ *
+ *   Row t of slot n, g = group[n]: skipped if g is no group, or if quota is non-NULL and done[n] >= quota[n].  Otherwise rows[g] += 1;
+ *   term = terminated[t][n] != 0; for every agent a, (x, y) are the two f16 values of team_positions[t][n][a].  The position is valid
+ *   iff both are finite, x >= 0, y >= 0, cx = (int)floor(x) / cell < Wc and cy = (int)floor(y) / cell < Hc (integer division).
+ *   Invalid: outside[g][a] += 1.  Valid and term: counts[g][SPAWN][a][cx][cy] += 1 (the env resets a slot inside its terminal tick, so
+ *   a terminal row holds the first position of the NEW episode; the position at which the old one ended is not available).  Valid and
+ *   not term: counts[g][OCC][a][cx][cy] += 1 and, if obs_type is given and seen(a) holds, counts[g][SEEN][a][cx][cy] += 1.  Finally
+ *   done[n] += term.
+ *   seen(a): some agent b of the OTHER role has a ray k with obs_type[t][n][b][k] == a's role code (CAT_COP = 1 for a < n_cops,
+ *   CAT_THIEF = 2 after).  This is role-level: with two agents of one role it says "an agent of my role is in an opponent's sight";
+ *   obs_type cannot tell which one.
+ *
+ * All sums are integers (64-bit global atomics): the result does not depend on the order or on how rows are chunked into launches.
+ */
+#define CAT_POSITIONS_OCC 0
+#define CAT_POSITIONS_SEEN 1
+#define CAT_POSITIONS_SPAWN 2
+#define CAT_POSITIONS_MAX_TICKS 65536    /* = CAT_MAX_ROLLOUT_TICKS */
+
+typedef struct cat_render_positions_args {
+    int32_t T, N, A, n_cops;      /* rows, slots, agents (<= CAT_RENDER_MAX_AGENTS), agents [0, n_cops) are cops */
+    int32_t R, cell, Wc, Hc;      /* rays per agent (obs_type only), cell size in pixels (>= 1), grid cells */
+    int32_t G, pad;               /* groups (>= 1) */
+    const uint16_t *team_positions; /* [T][N][A][2] float16 bits (cat_outputs.team_positions), 4-byte aligned */
+    const uint8_t *terminated;    /* [T][N] */
+    const uint8_t *obs_type;      /* [T][N][A][R] ObjectType, any byte alignment, or NULL = no SEEN plane */
+    const int32_t *group;         /* [N] or NULL = all slots in group 0 */
+    const int32_t *quota;         /* [N] or NULL = unlimited */
+    int64_t *counts;              /* [G][3][A][Wc][Hc] */
+    int64_t *outside;             /* [G][A] */
+    int64_t *rows;                /* [G] */
+    int32_t *done;                /* [N] */
+} cat_render_positions_args;
+
+/* An entry added after ABI version 1 was fixed (cat_render_frames and its two structs are unchanged). */
+int cat_render_positions_update(const cat_render_positions_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
