@@ -38,7 +38,8 @@ MODULES = {
                       "cat_dense_wgrad_splits": (C.c_int, [C.c_int32] * 4), "cat_dense_wgrad": _ENTRY, "cat_dense_forward": _ENTRY,
                       "cat_dense_dgrad": _ENTRY, "cat_dense_sum_chunks2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])}),
     "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY}),
-    "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]), "cat_render_positions_update": _ENTRY}),
+    "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]), "cat_render_positions_update": _ENTRY,
+                        "cat_render_positions_ends_update": _ENTRY}),
     "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
                          "cat_episodes_segment_summary": _ENTRY}),
     "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_collect_step": _ENTRY, "cat_act_league_step": _ENTRY}),
@@ -873,6 +874,45 @@ def positions_update(team_positions, terminated, obs_type, group, quota, counts,
 def positions_launch(a: PositionsArgs) -> None:
     """One launch of ``cat_render_positions_update`` with an argument block ``positions_update`` has checked."""
     _check(lib().cat_render_positions_update(C.byref(a), _stream()), "cat_render_positions_update")
+
+
+POSITIONS_CAPTURE, POSITIONS_TIMEOUT = 0, 1                   # CAT_POSITIONS_*: the planes of ``ends``
+
+
+class PositionsEndsArgs(C.Structure):
+    """include/cat_render.h cat_render_positions_ends_args."""
+    _fields_ = [("T", C.c_int32), ("N", C.c_int32), ("A", C.c_int32), ("cell", C.c_int32),
+                ("Wc", C.c_int32), ("Hc", C.c_int32), ("G", C.c_int32), ("pad", C.c_int32),
+                ("final_positions", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("group", C.c_void_p),
+                ("quota", C.c_void_p), ("done_before", C.c_void_p), ("ends", C.c_void_p), ("ends_outside", C.c_void_p)]
+
+
+def positions_ends_update(final_positions, terminated, truncated, group, quota, done_before, ends, ends_outside, cell: int) -> PositionsEndsArgs:
+    """final_positions f16 [T, N, A, 2], terminated / truncated u8 [T, N], all contiguous; group / quota / done_before int32 [N] or None;
+    ends int64 [G, 2, A, Wc, Hc], ends_outside int64 [G, 2, A].  One launch of ``cat_render_positions_ends_update`` on the current stream
+    (capturable); T <= POSITIONS_MAX_TICKS.  ``done_before`` is read, not written: launch this BEFORE the ``positions_update`` of the same rows
+    advances it.  Returns the checked argument block for ``positions_ends_launch``."""
+    import torch
+    T, N, A, _ = final_positions.shape
+    G, _, _, Wc, Hc = ends.shape
+    assert final_positions.dtype == torch.float16 and final_positions.shape == (T, N, A, 2) and final_positions.is_contiguous()
+    for t in (terminated, truncated):
+        assert t.dtype == torch.uint8 and t.shape == (T, N) and t.is_contiguous()
+    for t in (group, quota, done_before):
+        assert t is None or (t.dtype == torch.int32 and t.shape == (N,) and t.is_contiguous())
+    assert ends.dtype == torch.int64 and ends.shape == (G, 2, A, Wc, Hc) and ends.is_contiguous()
+    assert ends_outside.dtype == torch.int64 and ends_outside.shape == (G, 2, A) and ends_outside.is_contiguous()
+    dev = ends.device
+    assert all(t is None or t.device == dev for t in (final_positions, terminated, truncated, group, quota, done_before, ends_outside))
+    a = PositionsEndsArgs(T, N, A, int(cell), Wc, Hc, G, 0, final_positions.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), _ptr(group),
+                          _ptr(quota), _ptr(done_before), ends.data_ptr(), ends_outside.data_ptr())
+    positions_ends_launch(a)
+    return a
+
+
+def positions_ends_launch(a: PositionsEndsArgs) -> None:
+    """One launch of ``cat_render_positions_ends_update`` with an argument block ``positions_ends_update`` has checked."""
+    _check(lib().cat_render_positions_ends_update(C.byref(a), _stream()), "cat_render_positions_ends_update")
 
 
 # ---------------------------------------------------------------------------------------------- the fused act tick

@@ -107,6 +107,9 @@ def lib() -> C.CDLL:
     L.cat_step_fused.argtypes = [vp, vp, u64, i32, vp, vp]
     L.cat_rollout_fused.argtypes = [vp, i32, vp, u64, i32, vp, vp]
     L.cat_step_repeat.argtypes = [vp, i32, vp, i32, vp, vp, vp]       # sim, k, actions, auto_reset, out, ticks, stream
+    if hasattr(L, "cat_bind_final_positions"):   # absent from diagnostic builds of earlier sources (tools/final_positions_bench.py times one)
+        L.cat_bind_final_positions.argtypes = [vp, vp]                  # sim, buf (DEVICE u16, or None = detach)
+        L.cat_bind_final_positions.restype = i32
     L.cat_get_state.argtypes = [vp, vp, vp]
     L.cat_set_state.argtypes = [vp, vp, vp]
     L.cat_random_actions.argtypes = [vp, u64, vp, vp]
@@ -154,4 +157,4 @@ EXPORTED_SYMBOLS = ("cat_abi_version", "cat_one_tick_kernel", "cat_rollout_kerne
                     "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_step_repeat", "cat_get_state", "cat_set_state", "cat_random_actions",
                     "cat_set_seed", "cat_device_errors", "cat_arm_kernel_timing", "cat_num_agents", "cat_num_shapes", "cat_selftest_arith", "cat_debug_grid_lookup",
                     "cat_grid_build_host", "cat_grid_lookup_host", "cat_grid_bytes_host", "cat_grid_free_host", "cat_map_wall_bb_depth_host",
-                    "cat_bbtree_host", "cat_reward_arith_host", "cat_reward_arith_max", "cat_debug_reward_table")
+                    "cat_bbtree_host", "cat_reward_arith_host", "cat_reward_arith_max", "cat_debug_reward_table", "cat_bind_final_positions")

@@ -416,7 +416,45 @@ __global__ __launch_bounds__(PBLOCK) void positions_update_kernel(const cat_rend
     }
 }
 
+// Capture / timeout maps: lane = (slot of the wave, agent) as above; a slot's rows in order (the quota rule counts its terminal rows), and only a
+// terminal row -- one in an episode's length -- reads a position and adds: one atomic each, no runs to merge.
+__global__ __launch_bounds__(PBLOCK) void positions_ends_kernel(const cat_render_positions_ends_args a, int slots_per_wave)
+{
+    const int lane = threadIdx.x, A = a.A;
+    const int sw = lane / A, ag = lane - sw * A;
+    const long n = (long)blockIdx.x * slots_per_wave + sw;
+    if (sw >= slots_per_wave || n >= a.N) return;
+    int g = a.group ? a.group[n] : 0;
+    if (g < 0 || g >= a.G) return;                          // no group of the buffers: not counted (and never an index)
+    const bool limited = a.quota != nullptr;
+    const int quota = limited ? a.quota[n] : 0;
+    int done = a.done_before ? a.done_before[n] : 0;
+    const size_t cells = (size_t)a.Wc * (size_t)a.Hc;
+    const uint32_t *const pos = (const uint32_t *)a.final_positions;
+    for (int t = 0; t < a.T; ++t) {
+        if (limited && done >= quota) break;                // done only grows: every later row is skipped too
+        const size_t row = (size_t)t * (size_t)a.N + (size_t)n;
+        if (a.terminated[row] == 0) continue;
+        done += 1;
+        const int plane = a.truncated[row] != 0 ? CAT_POSITIONS_TIMEOUT : CAT_POSITIONS_CAPTURE;
+        const uint32_t xy = pos[row * A + ag];
+        const uint32_t xb = xy & 0xFFFFu, yb = xy >> 16;
+        const float x = (float)__builtin_bit_cast(_Float16, (uint16_t)xb), y = (float)__builtin_bit_cast(_Float16, (uint16_t)yb);
+        bool valid = (xb & 0x7C00u) != 0x7C00u && (yb & 0x7C00u) != 0x7C00u && x >= 0.0f && y >= 0.0f;
+        int cx = 0, cy = 0;
+        if (valid) {                                        // a finite f16 is below 65536: the int is exact
+            cx = (int)floorf(x) / a.cell;
+            cy = (int)floorf(y) / a.cell;
+            valid = cx < a.Wc && cy < a.Hc;
+        }
+        const size_t pa = ((size_t)g * 2 + plane) * A + ag;
+        if (!valid) add64(a.ends_outside + pa, 1u);
+        else add64(a.ends + pa * cells + (size_t)cx * a.Hc + cy, 1u);
+    }
+}
+
 int pfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_positions_update", msg); }
+int efail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_positions_ends_update", msg); }
 
 }   // namespace
 
@@ -435,6 +473,21 @@ extern "C" int cat_render_positions_update(const cat_render_positions_args *a, v
     const long blocks = ((long)a->N + spw - 1) / spw;
     hipLaunchKernelGGL(positions_update_kernel, dim3((unsigned)blocks), dim3(PBLOCK), 0, (hipStream_t)stream, *a, spw);
     return launched("cat_render_positions_update");
+}
+
+extern "C" int cat_render_positions_ends_update(const cat_render_positions_ends_args *a, void *stream)
+{
+    if (!a) return efail("NULL arguments");
+    if (a->T < 1 || a->T > CAT_POSITIONS_MAX_TICKS || a->N <= 0 || a->A <= 0 || a->A > CAT_RENDER_MAX_AGENTS) return efail("bad dimensions");
+    if (a->cell < 1) return efail("cell must be >= 1");
+    if (a->Wc < 1 || a->Hc < 1) return efail("the grid needs Wc >= 1 and Hc >= 1");
+    if (a->G < 1) return efail("G must be >= 1");
+    if (!a->final_positions || !a->terminated || !a->truncated || !a->ends || !a->ends_outside) return efail("a required buffer is NULL");
+    if ((uintptr_t)a->final_positions & 3) return efail("final_positions must be 4-byte aligned");
+    const int spw = PBLOCK / a->A;
+    const long blocks = ((long)a->N + spw - 1) / spw;
+    hipLaunchKernelGGL(positions_ends_kernel, dim3((unsigned)blocks), dim3(PBLOCK), 0, (hipStream_t)stream, *a, spw);
+    return launched("cat_render_positions_ends_update");
 }
 
 extern "C" int cat_render_abi_version(void) { return CAT_RENDER_ABI_VERSION; }

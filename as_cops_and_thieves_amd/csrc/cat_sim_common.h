@@ -201,8 +201,12 @@ struct PhaseClock { __device__ __forceinline__ void flush(int) {} };
 struct LaunchArgs {
     cat_outputs out;
     const int *actions;
-    const unsigned char *mask;
-    const double *positions;
+    union {                         // one pointer slot, by launch kind -- the struct keeps its size, and the Prologue behind it its place in the kernarg segment
+        const unsigned char *mask;  //   reset: which envs to reset, or null (read by reset_kernel alone)
+        unsigned short *final_pos;  //   step / rollout: cat_bind_final_positions' buffer (addressed like out.team_positions), or null; the host fills it from the handle
+    };                              // (as a field of its own behind `ticks`, 16 bytes more of launch arguments: the one-tick kernel measured 0.6 % slower with nothing
+                                    //  bound and no other change -- profiles/final_positions.txt.  NOT shared with `positions`: the auto-reset inside a step reads that)
+    const double *positions;        // reset: injected spawn positions, or null (spawn_and_reset: also inside a step's auto-reset, where it must be null)
     int use_done_mask;
     int auto_reset;                 // step / rollout: episodes that end with a tick are reset inside the same launch
     unsigned long long synth_tick;  // step / rollout with actions == NULL: Philox actions of this tick (rollout: of the first tick)

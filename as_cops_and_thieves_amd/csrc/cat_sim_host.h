@@ -556,6 +556,7 @@ struct cat_sim {
     hipStream_t side = nullptr;                       // two parts: the second one's stream ...
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // ... forked from and joined to the caller's
     hipEvent_t t_start = nullptr, t_stop = nullptr;   // cat_arm_kernel_timing
+    uint16_t *final_pos = nullptr;                    // cat_bind_final_positions: copied into the LaunchArgs of every stepping launch
     std::vector<MapDesc> maps;
     std::vector<void *> allocs;
     std::string one_tick_name, rollout_name;
@@ -1261,7 +1262,7 @@ extern "C" int cat_step(cat_sim *s, const int32_t *actions, const cat_outputs *o
     LaunchArgs la;
     memset(&la, 0, sizeof la);
     if (out) la.out = *out;
-    la.actions = actions;
+    la.actions = actions; la.final_pos = s->final_pos;
     const int rc = launch_parts(s, la, stream, kFnStep);
     if (rc != CAT_OK) return rc;
     HIP_TRY(s, hipGetLastError());
@@ -1278,6 +1279,7 @@ extern "C" int cat_step_fused(cat_sim *s, const int32_t *actions, uint64_t synth
     if (out) la.out = *out;
     la.actions = actions; la.synth_tick = synth_tick;
     la.auto_reset = auto_reset ? 1 : 0;   // finished episodes are reset inside the same launch (no second kernel)
+    la.final_pos = s->final_pos;
     const int rc = launch_parts(s, la, stream, kFnStep);
     if (rc != CAT_OK) return rc;
     HIP_TRY(s, hipGetLastError());
@@ -1295,6 +1297,7 @@ extern "C" int cat_rollout_fused(cat_sim *s, int T, const int32_t *actions, uint
     if (out) la.out = *out;
     la.actions = actions; la.synth_tick = synth_tick0; la.T = T;
     la.auto_reset = auto_reset ? 1 : 0;
+    la.final_pos = s->final_pos;
     const int rc = launch_parts(s, la, stream, kFnRollout);
     if (rc != CAT_OK) return rc;
     HIP_TRY(s, hipGetLastError());
@@ -1313,9 +1316,18 @@ extern "C" int cat_step_repeat(cat_sim *s, int k, const int32_t *actions, int au
     if (out) la.out = *out;
     la.actions = actions; la.T = k; la.repeat = 1; la.ticks = ticks;
     la.auto_reset = auto_reset ? 1 : 0;
+    la.final_pos = s->final_pos;
     const int rc = launch_parts(s, la, stream, kFnRollout);
     if (rc != CAT_OK) return rc;
     HIP_TRY(s, hipGetLastError());
+    return CAT_OK;
+}
+
+// End-of-episode positions: the handle keeps the pointer, every stepping entry hands it to its launch (see include/cat_sim.h).  No device call.
+extern "C" int cat_bind_final_positions(cat_sim *s, uint16_t *buf)
+{
+    if (!s) return CAT_ERR_BAD_ARG;
+    s->final_pos = buf;
     return CAT_OK;
 }
 

@@ -456,9 +456,11 @@ __device__ __forceinline__ void spawn_and_reset(const Lds &L, const Params &p, c
 // last tick's positions, the tick-start snapshot, Entity._perform_action with lane = agent, the in-kernel auto-reset of an
 // episode that ends with this tick, and the per-agent ray-fan setup.  Leaves L.flags for the write-back and returns the
 // number of work units to publish (ray-fan units [+ Space.step]).  act_pref: lane i's action when la.actions is set.
+// row_t: the launch's tick (0 in the one-tick kernels), for the end-of-episode positions of cat_bind_final_positions -- an int the callers hold anyway; the
+// output row is formed from it on the rare path, as slot_record_early derives it (row_t * N + env; the env slot under cat_step_repeat).
 template <class D>
 __device__ __forceinline__ int slot_front(const Lds &L, ParamsK pk, const LaunchArgs &la, const MapDesc &md, const GridDesc &gd,
-                                          int env, int lane, int act_pref, unsigned long long synth_tick, int n_fan, PhaseClock &pc)
+                                          int env, int row_t, int lane, int act_pref, unsigned long long synth_tick, int n_fan, PhaseClock &pc)
 {
     // three sub-phases, each from a freshly laundered parameter pointer: what one has loaded does not stay alive through the next
     // (the rare auto-reset path inlines Space.step and the spawn sampling between the two common ones)
@@ -498,18 +500,25 @@ __device__ __forceinline__ int slot_front(const Lds &L, ParamsK pk, const Launch
     {
         const Params &p = *(const Params *)launder(pk);
         n_units = n_fan + 1;
-        if (la.auto_reset && (captured || timeout)) {
-            // The episode ends with this tick and the caller wants the slot reset in the same call: the terminal
-            // observations would be overwritten by the reset's (the rewards of a terminal tick are constants), so the
-            // slot's ray chunks are those of the NEW episode.  The reset needs the stepped state (stale circle caches
-            // and leaf bbs, quirk Q1), so the owner runs Space.step here instead of queueing it.
-            physics_env<D>(L, p, uni(md.S), lane, pc);                // :392
-            rcount = uni(L.cnt[1]) + 1;
-            spawn_and_reset<D>(L, p, la, md, env, (unsigned)rcount, lane);   // base_env.py:286-352
-            wave_sync();
-            copy_snapshot(L, D::A(p), lane);
-            n_units -= 1; step_store = 0;
-            row = setup_row(L.fpos, p, gd, lane, D::A(p));           // the agents have moved to their spawn points
+        if (captured || timeout) {   // (the one branch of the common path: everything behind it is the rare path)
+            // End-of-episode positions (cat_bind_final_positions): the tick-start snapshot of a tick that ends an episode -- what the termination check
+            // read and what team_positions carries unless the auto-reset below replaces the snapshot by the new episode's spawn points.  Rows of
+            // other ticks are not touched.
+            if (la.final_pos && lane < 2 * D::A(p))
+                G(la.final_pos)[((size_t)(la.repeat ? 0 : row_t) * (size_t)p.N + (size_t)env) * (size_t)(2 * D::A(p)) + lane] = (unsigned short)f64_to_f16(L.fpos[lane]);
+            if (la.auto_reset) {
+                // The episode ends with this tick and the caller wants the slot reset in the same call: the terminal
+                // observations would be overwritten by the reset's (the rewards of a terminal tick are constants), so the
+                // slot's ray chunks are those of the NEW episode.  The reset needs the stepped state (stale circle caches
+                // and leaf bbs, quirk Q1), so the owner runs Space.step here instead of queueing it.
+                physics_env<D>(L, p, uni(md.S), lane, pc);                // :392
+                rcount = uni(L.cnt[1]) + 1;
+                spawn_and_reset<D>(L, p, la, md, env, (unsigned)rcount, lane);   // base_env.py:286-352
+                wave_sync();
+                copy_snapshot(L, D::A(p), lane);
+                n_units -= 1; step_store = 0;
+                row = setup_row(L.fpos, p, gd, lane, D::A(p));           // the agents have moved to their spawn points
+            }
         }
     }
     {
@@ -607,7 +616,7 @@ __device__ __forceinline__ void rollout_body(const Params *__restrict__ pp0, con
             if (lane == 0) ctrl[4 * slot + 1] = 0;
             const int n_fan = fan_units<D>(p, unit_span<D, kOneTick>(p, K->gd));
 #ifndef CAT_ABL_NOFRONT
-            const int n2 = slot_front<D>(Ls, (ParamsK)pp0, la, K->md, K->gd, e_s, lane, ap, la.synth_tick + (unsigned long long)t, n_fan, pc);
+            const int n2 = slot_front<D>(Ls, (ParamsK)pp0, la, K->md, K->gd, e_s, kOneTick ? 0 : t, lane, ap, la.synth_tick + (unsigned long long)t, n_fan, pc);
 #else
             const int n2 = n_fan + 1;
             if (lane == 0) { Ls.flags[0] = 1; Ls.flags[1] = 0; Ls.flags[2] = 0; Ls.flags[3] = -1; }
@@ -1136,7 +1145,7 @@ __device__ __forceinline__ void rollout_body_pool(const Params *__restrict__ pp0
             int ap = 0;
             if (la.actions && lane < D::A(p)) ap = la.actions[((size_t)((!kOneTick && la.repeat) ? 0 : t) * p.N + e_s) * D::A(p) + lane];   // repeat: one row, held
             if (lane == 0) ctrl[4 * slot + 1] = 0;
-            const int n2 = slot_front<D>(Ls, (ParamsK)pp0, la, K->md, K->gd, e_s, lane, ap, la.synth_tick + (unsigned long long)t, 0, pc);   // 1: Space.step to come; 0: it ran inside (reset)
+            const int n2 = slot_front<D>(Ls, (ParamsK)pp0, la, K->md, K->gd, e_s, kOneTick ? 0 : t, lane, ap, la.synth_tick + (unsigned long long)t, 0, pc);   // 1: Space.step to come; 0: it ran inside (reset)
             if (n2 == 0) slot_record_early<D>(Ls, p, la, e_s, t, T, !kOneTick && la.repeat != 0, lane);   // the tick stepped and reset inside the front: its record is final
             lds_release();
             if (lane == 0) __hip_atomic_store((unsigned *)&ctrl[4 * slot], rw_make(t + 1, n2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

@@ -315,6 +315,15 @@ class VecCopsEnv:
     over the batch's largest map window (``position_stats()``, ``position_tracker``); ``position_exposure=False`` leaves ``obs_type`` unread
     and the SEEN plane zero; ``position_groups`` is the tracker's number of groups (``PositionTracker.set_groups``; every slot starts in
     group 0).  An explicit ``reset`` feeds nothing.  Off by default: no buffer, no launch.
+
+    ``final_positions=True``: where episodes END.  Under auto-reset a terminal row's ``team_positions`` is already the spawn point of the next
+    episode; with this option the env owns a float16 ``[N, A, 2]`` buffer, bound to the env core for its whole life
+    (``CatSim.bind_final_positions``), and ``step`` / ``step_raw`` (``repeat=k`` included) / ``rollout_random`` expose it as
+    ``infos["final_positions"]`` / ``out["final_positions"]`` (a view of the buffer, not a copy).  Where ``terminated`` is set the row holds
+    the tick-start positions of the tick that ended the episode -- what the termination check read.  EVERY OTHER ROW IS NOT WRITTEN: it keeps
+    the positions of that slot's last episode end, and NaN (``0x7E00``) before the slot's first.  Mask with ``terminated``.  The buffer's
+    address never changes, so a HIP graph captured over the env's ticks keeps filling it.  With ``track_positions`` the tracker also keeps the
+    capture / timeout maps (``PositionTracker(final_positions=True)``).  Off by default: no buffer, no bind, nothing changes.
     """
 
     metadata = BaseEnv.metadata
@@ -325,7 +334,7 @@ class VecCopsEnv:
                  auto_reset: bool = True, device=None, seed: int = 1, env_id_offset: int = 0,
                  physical: Optional[PhysicalParams] = None, bbtree_gate: bool = True, query_order: str = "index",
                  track_episodes: bool = False, frame_skip: int = 1, track_positions: Optional[int] = None,
-                 position_exposure: bool = True, position_groups: int = 1):
+                 position_exposure: bool = True, position_groups: int = 1, final_positions: bool = False):
         gate = gate_mode(bbtree_gate, query_order)   # (before anything touches a device)
         self.frame_skip = check_repeat(frame_skip, "frame_skip")
         if track_episodes and not auto_reset:
@@ -373,13 +382,20 @@ class VecCopsEnv:
         if track_episodes:
             from .episodes import EpisodeTracker
             self._tracker = EpisodeTracker(num_envs, self.possible_agents, max_step_count, self.device)
+        self._final_pos = self._final_rows = None
+        if final_positions:
+            from .sim import FINAL_POS_NAN
+            self._final_pos = torch.full((num_envs, len(everyone), 2), FINAL_POS_NAN, dtype=torch.int16, device=self.device).view(torch.float16)
+            self._sim.bind_final_positions(self._final_pos)
+            self._sim.out["final_positions"] = self._final_pos      # (not a field of cat_outputs: the sim's launches never look it up)
         if track_episodes or track_positions is not None:
             self._tracked_rows: Dict[str, torch.Tensor] = {}
         self._positions, self._exposure = None, bool(position_exposure)
         if track_positions is not None:
             from .positions import PositionTracker
             window = (max(int(c.window[0]) for c in self._compiled), max(int(c.window[1]) for c in self._compiled))
-            self._positions = PositionTracker(num_envs, self.possible_agents, m0.cops_count, window, int(track_positions), int(position_groups), self.device)
+            self._positions = PositionTracker(num_envs, self.possible_agents, m0.cops_count, window, int(track_positions), int(position_groups), self.device,
+                                              final_positions=bool(final_positions))
 
     # episode accounting
     @property
@@ -419,7 +435,8 @@ class VecCopsEnv:
         if self._tracker is not None:
             self._tracker.update(out["reward"], out["terminated"], out["truncated"], out["winner"], ticks=ticks)
         if self._positions is not None:     # a frame-skip row counts once, at the window's last position
-            self._positions.update(out["team_positions"], out["terminated"], out["obs_type"] if self._exposure else None)
+            ends = {"final_positions": out["final_positions"], "truncated": out["truncated"]} if "final_positions" in out else {}
+            self._positions.update(out["team_positions"], out["terminated"], out["obs_type"] if self._exposure else None, **ends)
 
     def _repeat(self, repeat) -> int:
         """The ``repeat`` argument of ``step`` / ``step_raw``, checked: None is the constructor's ``frame_skip``."""
@@ -483,6 +500,8 @@ class VecCopsEnv:
         infos = {"winner": out["winner"].clone(), "terminated": terminated, "truncated": truncated}
         if repeat > 1:
             infos["ticks"] = out["ticks"].clone()
+        if self._final_pos is not None:
+            infos["final_positions"] = self._final_pos      # a view: rows without ``terminated`` are not written (see the class docstring)
         terminations = {aid: terminated for aid in self.possible_agents}
         truncations = {aid: truncated for aid in self.possible_agents}
         return self._obs(), rewards, terminations, truncations, infos
@@ -539,7 +558,16 @@ class VecCopsEnv:
         while ticks - 1 - done > 0:
             n = min(cap, ticks - 1 - done)
             rows = {} if not keys else self._tracked_rollout_rows(min(cap, ticks - 1), n, keys)
-            self._sim.rollout_fused(n, None, tick=tick0 + done, auto_reset=self.auto_reset, out=rows)
+            if self._final_pos is not None:     # the resident launch's [T, N, A, 2] twin where a tracker reads it, else nothing (nobody sees these rows)
+                twin = self._final_rollout_rows(min(cap, ticks - 1), n) if self._positions is not None else None
+                self._sim.bind_final_positions(twin)
+            try:
+                self._sim.rollout_fused(n, None, tick=tick0 + done, auto_reset=self.auto_reset, out=rows)
+            finally:
+                if self._final_pos is not None:
+                    self._sim.bind_final_positions(self._final_pos)
+            if self._final_pos is not None and self._positions is not None:
+                rows = dict(rows, final_positions=twin)
             self._track(rows)
             done += n
         out = self._sim.step_fused(None, tick=tick0 + ticks - 1, auto_reset=self.auto_reset)
@@ -553,13 +581,16 @@ class VecCopsEnv:
         keys = ("reward", "terminated", "truncated", "winner") if self._tracker is not None else ()
         if self._positions is not None:
             keys += tuple(k for k in ("terminated", "team_positions") if k not in keys) + (("obs_type",) if self._exposure else ())
+            if self._final_pos is not None and "truncated" not in keys:
+                keys += ("truncated",)
         return keys
 
     def _tracked_row_bytes(self, keys) -> int:
         """Bytes one env-tick of the kept rows takes (4 A + 3 for the episode tracker's alone)."""
         from .sim import _OUT_SPEC
         A, R = len(self.possible_agents), self._cfg.n_rays
-        return sum(int(np.prod(_OUT_SPEC[k][0](1, A, R))) * torch.empty((), dtype=_OUT_SPEC[k][1]).element_size() for k in keys)
+        final = 4 * A if self._final_pos is not None and self._positions is not None else 0     # the [T, N, A, 2] f16 twin
+        return final + sum(int(np.prod(_OUT_SPEC[k][0](1, A, R))) * torch.empty((), dtype=_OUT_SPEC[k][1]).element_size() for k in keys)
 
     def _tracked_rollout_rows(self, rows: int, n: int, keys=("reward", "terminated", "truncated", "winner")) -> Dict[str, torch.Tensor]:
         """The first ``n`` rows of the ``[rows, N, ...]`` buffers of a tracked ``rollout_random`` (kept, and grown when a longer chunk
@@ -570,6 +601,15 @@ class VecCopsEnv:
             self._tracked_rows = {k: torch.zeros((rows,) + tuple(_OUT_SPEC[k][0](N, A, R)), dtype=_OUT_SPEC[k][1], device=self.device)
                                   for k in keys}
         return {k: self._tracked_rows[k][:n] for k in keys}
+
+    def _final_rollout_rows(self, rows: int, n: int) -> torch.Tensor:
+        """The first ``n`` rows of the ``[rows, N, A, 2]`` end-of-episode buffer of a tracked ``rollout_random`` (kept, grown when a longer
+        chunk comes, NaN-filled when made: the tracker reads terminal rows only, and those the launch writes)."""
+        from .sim import FINAL_POS_NAN
+        if self._final_rows is None or self._final_rows.shape[0] < rows:
+            self._final_rows = torch.full((rows, self.num_envs, len(self.possible_agents), 2), FINAL_POS_NAN, dtype=torch.int16,
+                                          device=self.device).view(torch.float16)
+        return self._final_rows[:n]
 
     def render(self, env_ids: Optional[Sequence[int]] = None, rays: bool = False) -> torch.Tensor:
         """``rgb_array`` frames of the env slots ``env_ids`` (default ``[0]``), drawn on the GPU in one launch

@@ -16,9 +16,21 @@ The counting rule, for row t of slot n with ``g = group[n]``:
 3. finally ``done[n] += terminated[t, n] != 0``.
 
 With auto-reset the env resets a slot INSIDE its terminal tick, so a terminal row's buffers hold the first observation of the new episode:
-that is why such a row counts as a spawn, and why the position at which the old episode ended is not available (capture-location maps
-would need a pre-reset position from the env core).  A frame-skip row (``step_raw(actions, repeat=k)``) counts once: one count per
-decision, at the window's last position.
+that is why such a row counts as a spawn.  A frame-skip row (``step_raw(actions, repeat=k)``) counts once: one count per decision, at the
+window's last position.
+
+Where an episode ENDED is a separate input: the env core's end-of-episode positions (``CatSim.bind_final_positions``: on a terminal row the
+tick-start positions of the episode that ended -- the ones the termination check read -- any other row holds nothing to read).  A tracker
+built with ``final_positions=True`` and fed ``update(..., final_positions=, truncated=)`` also keeps ``ends`` int64 ``[G, 2, A, Wc, Hc]``
+(planes ``CAPTURE`` / ``TIMEOUT``) and ``ends_outside`` ``[G, 2, A]`` (``cat_render_positions_ends_update``).  The ends rule, for row t of
+slot n (``_update_ends_host`` defines it):
+
+1. the row is skipped exactly when rule 1 above skips it (``done[n]`` as it stands BEFORE this row);
+2. otherwise, if ``terminated[t, n] != 0``: plane = ``TIMEOUT`` if ``truncated[t, n] != 0`` else ``CAPTURE``, and for every agent a the
+   f16 pair ``final_positions[t, n, a]`` is valid by the rule above; an invalid one adds to ``ends_outside[g, plane, a]``, a valid one to
+   ``ends[g, plane, a, cx, cy]``.  A row that is not terminal adds nothing and its ``final_positions`` are never read.
+
+So a slot's ``quota``-th terminal row is the last whose end is counted, as it is the last whose spawn is.
 
 ``seen(a)`` is ROLE-LEVEL: it holds when some agent of the other role has a ray whose ``obs_type`` is a's role code (``COP`` for a cop,
 ``THIEF`` for a thief).  With two agents of one role it says "an agent of my role is in an opponent's sight"; ``obs_type`` cannot tell
@@ -36,6 +48,8 @@ from .constants import ObjectType
 
 OCC, SEEN, SPAWN = ln.POSITIONS_OCC, ln.POSITIONS_SEEN, ln.POSITIONS_SPAWN
 PLANES = ("occ", "seen", "spawn")
+CAPTURE, TIMEOUT = ln.POSITIONS_CAPTURE, ln.POSITIONS_TIMEOUT
+END_PLANES = ("capture", "timeout")
 INT32_MAX = 2 ** 31 - 1
 _COP, _THIEF = ObjectType.COP.value, ObjectType.THIEF.value
 
@@ -50,9 +64,12 @@ class PositionTracker:
     """Per-group occupancy / exposure / spawn maps (``include/cat_render.h`` ``cat_render_positions_update``).
 
     ``agents``: the env's agent ids, cops first (``n_cops`` of them); ``window``: ``(W, H)`` pixels, the largest ``int(window)`` over
-    the batch's maps; ``cell``: cell size in pixels; ``n_groups``: G.  Every slot starts in group 0 without a quota."""
+    the batch's maps; ``cell``: cell size in pixels; ``n_groups``: G.  Every slot starts in group 0 without a quota.
+    ``final_positions=True``: the tracker also keeps the capture / timeout maps (``ends``, ``ends_outside``) and ``update`` takes the
+    end-of-episode positions; without it nothing of that exists and every result is the same as before, key for key."""
 
-    def __init__(self, num_envs: int, agents: Sequence[str], n_cops: int, window, cell: int, n_groups: int = 1, device=None):
+    def __init__(self, num_envs: int, agents: Sequence[str], n_cops: int, window, cell: int, n_groups: int = 1, device=None,
+                 final_positions: bool = False):
         self.N, self.agents, self.A, self.n_cops = int(num_envs), list(agents), len(agents), int(n_cops)
         self.G = int(n_groups)
         if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or cell < 1:
@@ -68,18 +85,24 @@ class PositionTracker:
             self.device = torch.device("cuda", torch.cuda.current_device())
         G, A, N = self.G, self.A, self.N
         # ONE allocation: counts, outside, rows and (as int32) done -- counts() brings all of them to the host in one copy
+        # (with final_positions: ends and ends_outside behind them)
         n_counts, n_out = G * 3 * A * self.Wc * self.Hc, G * A
-        self._flat = torch.zeros(n_counts + n_out + G + (N + 1) // 2, dtype=torch.int64, device=self.device)
+        self.final_positions = bool(final_positions)
+        n_base = n_counts + n_out + G + (N + 1) // 2
+        n_ends, n_eout = (G * 2 * A * self.Wc * self.Hc, G * 2 * A) if self.final_positions else (0, 0)
+        self._flat = torch.zeros(n_base + n_ends + n_eout, dtype=torch.int64, device=self.device)
         self._counts = self._flat[:n_counts].view(G, 3, A, self.Wc, self.Hc)
         self._outside = self._flat[n_counts:n_counts + n_out].view(G, A)
         self._rows = self._flat[n_counts + n_out:n_counts + n_out + G]
-        self._done = self._flat[n_counts + n_out + G:].view(torch.int32)[:N]
+        self._done = self._flat[n_counts + n_out + G:n_base].view(torch.int32)[:N]
+        self._ends = self._flat[n_base:n_base + n_ends].view(G, 2, A, self.Wc, self.Hc) if self.final_positions else None
+        self._ends_outside = self._flat[n_base + n_ends:].view(G, 2, A) if self.final_positions else None
         # ONE group and ONE quota buffer for the tracker's life: the update launch takes their pointers by value, so a launch captured
         # in a HIP graph keeps reading them, and set_groups / set_quota after the capture reach the replays
         self._group = torch.zeros(N, dtype=torch.int32, device=self.device)
         self._quota = torch.full((N,), INT32_MAX, dtype=torch.int32, device=self.device)
         self._gpu = self.device.type == "cuda"
-        self._last = (None, None)     # (what the last one-launch update was given, its checked argument block)
+        self._last = (None, None)     # (what the last one-launch update was given, its checked argument blocks: ends or None, positions)
         if self._gpu:
             ln.lib()     # a missing kernel library is an error here, not at the first update
 
@@ -115,16 +138,27 @@ class PositionTracker:
             self._quota.copy_(torch.as_tensor(quota).to(torch.int32).reshape(self.N))
 
     # ------------------------------------------------------------------ feeding
-    def update(self, team_positions, terminated, obs_type=None) -> None:
+    def update(self, team_positions, terminated, obs_type=None, final_positions=None, truncated=None) -> None:
         """One row ``[N, ...]`` or T consecutive rows ``[T, N, ...]``: team_positions f16 ``[.., N, A, 2]``, terminated ``[.., N]`` (uint8
-        or bool), obs_type u8 ``[.., N, A, R]`` or None (no SEEN plane).  An env feeds the same output buffers tick after tick: a call
-        with the buffers of the one before (same addresses, shapes, strides and types) launches again from the checked argument block."""
+        or bool), obs_type u8 ``[.., N, A, R]`` or None (no SEEN plane).  ``final_positions`` f16 ``[.., N, A, 2]`` with ``truncated``
+        ``[.., N]`` (both or neither; a tracker built with ``final_positions=True`` only): the same rows' end-of-episode positions, added to
+        the capture / timeout maps (``update_ends``) before ``done`` advances over these rows.  An env feeds the same output buffers tick
+        after tick: a call with the buffers of the one before (same addresses, shapes, strides and types) launches again from the checked
+        argument blocks."""
+        if (final_positions is None) != (truncated is None):
+            raise ValueError("PositionTracker.update: final_positions and truncated go together")
         given = None
         if self._gpu:
-            given = tuple(None if t is None else (t.data_ptr(), t.shape, t.stride(), t.dtype) for t in (team_positions, terminated, obs_type))
+            given = tuple(None if t is None else (t.data_ptr(), t.shape, t.stride(), t.dtype)
+                          for t in (team_positions, terminated, obs_type, final_positions, truncated))
             if given == self._last[0]:
-                ln.positions_launch(self._last[1])
+                if self._last[1][0] is not None:
+                    ln.positions_ends_launch(self._last[1][0])
+                ln.positions_launch(self._last[1][1])
                 return
+        eargs = None
+        if final_positions is not None:      # first: it reads ``done`` as it stands before these rows
+            eargs = self.update_ends(final_positions, terminated, truncated)
         if team_positions.dim() == 3:
             team_positions, terminated = team_positions[None], terminated[None]
             obs_type = None if obs_type is None else obs_type[None]
@@ -145,9 +179,67 @@ class PositionTracker:
                 args = ln.positions_update(team_positions[sl], terminated[sl], None if obs_type is None else obs_type[sl], self._group, self._quota,
                                            self._counts, self._outside, self._rows, self._done, self.n_cops, self.cell)
             same = all(t is None or t.data_ptr() == g[0] for t, g in zip((team_positions, terminated, obs_type), given))   # nothing was converted
-            self._last = (given, args) if same and T <= ln.POSITIONS_MAX_TICKS else (None, None)
+            same = same and (final_positions is None or eargs is not None)
+            self._last = (given, (eargs, args)) if same and T <= ln.POSITIONS_MAX_TICKS else (None, None)
         else:
             self._update_host(team_positions.numpy(), terminated.numpy(), None if obs_type is None else obs_type.numpy())
+
+    def update_ends(self, final_positions, terminated, truncated):
+        """The capture / timeout maps alone (a tracker built with ``final_positions=True``): one row or T rows of end-of-episode positions
+        f16 ``[.., N, A, 2]`` with their ``terminated`` / ``truncated`` flags ``[.., N]``, under the ends rule of the module docstring.
+        ``done`` is read as it stands and not advanced -- ``update`` calls this first and then counts the same rows; a caller whose
+        occupancy rows carry other flags (an env without auto-reset) calls it on its own.  On a GPU: one launch per 65536 rows; returns the
+        launch's argument block if it can be repeated as it is (one launch, nothing converted), else None."""
+        if not self.final_positions:
+            raise ValueError("PositionTracker: this tracker was built without final_positions=True and keeps no capture / timeout maps")
+        if final_positions.dim() == 3:
+            final_positions, terminated, truncated = final_positions[None], terminated[None], truncated[None]
+        T = final_positions.shape[0]
+        if tuple(final_positions.shape) != (T, self.N, self.A, 2) or tuple(terminated.shape) != (T, self.N) or tuple(truncated.shape) != (T, self.N):
+            raise ValueError(f"PositionTracker.update_ends: expected [T, {self.N}, {self.A}, 2] final positions and [T, {self.N}] flags, got "
+                             f"{tuple(final_positions.shape)}, {tuple(terminated.shape)}, {tuple(truncated.shape)}")
+        if any(t.device != self.device for t in (final_positions, terminated, truncated)):
+            raise ValueError(f"PositionTracker.update_ends: the rows must lie on {self.device}")
+        as_u8 = lambda t: (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)).contiguous()
+        before = tuple(t.data_ptr() for t in (final_positions, terminated, truncated))
+        final_positions, terminated, truncated = final_positions.to(torch.float16).contiguous(), as_u8(terminated), as_u8(truncated)
+        if not self._gpu:
+            self._update_ends_host(final_positions.numpy(), terminated.numpy(), truncated.numpy())
+            return None
+        done = self._done
+        for t0 in range(0, T, ln.POSITIONS_MAX_TICKS):
+            sl = slice(t0, min(T, t0 + ln.POSITIONS_MAX_TICKS))
+            if t0:      # a later chunk: the slots' terminal rows so far, carried along in a copy
+                done = done + terminated[t0 - ln.POSITIONS_MAX_TICKS:t0].ne(0).sum(0, dtype=torch.int32)
+            eargs = ln.positions_ends_update(final_positions[sl], terminated[sl], truncated[sl], self._group, self._quota, done,
+                                             self._ends, self._ends_outside, self.cell)
+        same = before == tuple(t.data_ptr() for t in (final_positions, terminated, truncated))
+        return eargs if same and T <= ln.POSITIONS_MAX_TICKS else None
+
+    def _update_ends_host(self, final_pos, terminated, truncated) -> None:
+        """The ends rule in NumPy: slots in parallel, rows in order.  Reads ``done`` as it stands before these rows and leaves it alone
+        (``_update_host`` over the same rows advances it): the count of a slot's terminal rows runs along in a copy."""
+        ends, ends_outside = self._ends.numpy(), self._ends_outside.numpy()   # views
+        group, quota, done = self._group.numpy(), self._quota.numpy(), self._done.numpy().copy()
+        cell = self.cell
+        agent = np.arange(self.A)[None, :]
+        for t in range(final_pos.shape[0]):
+            ends_here = (group >= 0) & (group < self.G) & (done < quota) & (terminated[t] != 0)
+            idx = np.nonzero(ends_here)[0]
+            done += ends_here
+            if not idx.size:
+                continue
+            g = group[idx]
+            plane = np.where(truncated[t, idx] != 0, TIMEOUT, CAPTURE)
+            xy = final_pos[t, idx].astype(np.float32)
+            x, y = xy[..., 0], xy[..., 1]
+            valid = np.isfinite(x) & np.isfinite(y) & (x >= 0) & (y >= 0)
+            cx = np.floor(np.where(valid, x, 0.0)).astype(np.int64) // cell
+            cy = np.floor(np.where(valid, y, 0.0)).astype(np.int64) // cell
+            valid &= (cx < self.Wc) & (cy < self.Hc)
+            gg, pp, aa = (np.broadcast_to(v, valid.shape) for v in (g[:, None], plane[:, None], agent))
+            np.add.at(ends_outside, (gg[~valid], pp[~valid], aa[~valid]), 1)
+            np.add.at(ends, (gg[valid], pp[valid], aa[valid], cx[valid], cy[valid]), 1)
 
     def _update_host(self, pos, terminated, obs_type=None) -> None:
         """The counting rule in NumPy: slots in parallel, rows in order."""
@@ -184,29 +276,42 @@ class PositionTracker:
             done[idx] += term
 
     def clear(self) -> None:
-        """Zero the maps, ``outside``, ``rows`` and the terminal rows counted towards the quota; the groups and the quota stay."""
+        """Zero the maps (the capture / timeout maps and ``ends_outside`` included), ``outside``, ``rows`` and the terminal rows counted
+        towards the quota; the groups and the quota stay."""
         self._flat.zero_()
 
     # ------------------------------------------------------------------ reading
     def tensors(self) -> Dict[str, torch.Tensor]:
         """The buffers as they lie on the device (views of the tracker's state: no copy, no synchronisation)."""
-        return {"counts": self._counts, "outside": self._outside, "rows": self._rows, "done": self._done, "group": self._group,
-                "quota": self._quota}
+        t = {"counts": self._counts, "outside": self._outside, "rows": self._rows, "done": self._done, "group": self._group,
+             "quota": self._quota}
+        if self.final_positions:
+            t.update(ends=self._ends, ends_outside=self._ends_outside)
+        return t
 
     def counts(self) -> Dict[str, np.ndarray]:
         """Host copies of ``counts`` int64 ``[G, 3, A, Wc, Hc]`` (planes OCC, SEEN, SPAWN; x-major like the frames), ``outside``
-        ``[G, A]``, ``rows`` ``[G]`` and ``done`` int32 ``[N]``: one copy, one synchronisation."""
+        ``[G, A]``, ``rows`` ``[G]`` and ``done`` int32 ``[N]``: one copy, one synchronisation.  A tracker built with
+        ``final_positions=True`` adds ``ends`` int64 ``[G, 2, A, Wc, Hc]`` (planes CAPTURE, TIMEOUT) and ``ends_outside`` ``[G, 2, A]``."""
         flat = self._flat.cpu().numpy().copy()
         G, A, N = self.G, self.A, self.N
         n_counts, n_out = G * 3 * A * self.Wc * self.Hc, G * A
-        return {"counts": flat[:n_counts].reshape(G, 3, A, self.Wc, self.Hc), "outside": flat[n_counts:n_counts + n_out].reshape(G, A),
-                "rows": flat[n_counts + n_out:n_counts + n_out + G], "done": flat[n_counts + n_out + G:].view(np.int32)[:N]}
+        n_base = n_counts + n_out + G + (N + 1) // 2
+        c = {"counts": flat[:n_counts].reshape(G, 3, A, self.Wc, self.Hc), "outside": flat[n_counts:n_counts + n_out].reshape(G, A),
+             "rows": flat[n_counts + n_out:n_counts + n_out + G], "done": flat[n_counts + n_out + G:n_base].view(np.int32)[:N]}
+        if self.final_positions:
+            n_ends = G * 2 * A * self.Wc * self.Hc
+            c["ends"] = flat[n_base:n_base + n_ends].reshape(G, 2, A, self.Wc, self.Hc)
+            c["ends_outside"] = flat[n_base + n_ends:].reshape(G, 2, A)
+        return c
 
     def summary(self) -> List[Dict[str, object]]:
         """Per group: ``rows`` and, per agent id, ``outside``, ``occupied`` / ``seen`` / ``spawns`` (the planes' sums), ``cells_visited``
         (cells with OCC > 0), ``seen_fraction`` = sum(SEEN) / sum(OCC) (0 without occupancy) and the argmax cells ``(cx, cy)`` of OCC
-        (``top_cell``) and of OCC - SEEN (``top_hidden_cell``, the most-used hidden cell); None where the plane is all zero.  Formed
-        on the host from ``counts()``: one synchronisation."""
+        (``top_cell``) and of OCC - SEEN (``top_hidden_cell``, the most-used hidden cell); None where the plane is all zero.  A tracker
+        built with ``final_positions=True`` adds ``captures`` / ``timeouts`` (the CAPTURE / TIMEOUT planes' sums: episode ends counted at a
+        valid position) and their argmax cells ``top_capture_cell`` / ``top_timeout_cell``.  Formed on the host from ``counts()``: one
+        synchronisation."""
         c = self.counts()
         out = []
         for g in range(self.G):
@@ -219,5 +324,8 @@ class PositionTracker:
                 per_agent[aid] = {"outside": int(c["outside"][g, i]), "occupied": n_occ, "seen": int(seen.sum()), "spawns": int(spawn.sum()),
                                   "cells_visited": int((occ > 0).sum()), "seen_fraction": float(seen.sum()) / n_occ if n_occ else 0.0,
                                   "top_cell": top(occ), "top_hidden_cell": top(hidden)}
+                if self.final_positions:
+                    cap, tmo = c["ends"][g, CAPTURE, i], c["ends"][g, TIMEOUT, i]
+                    per_agent[aid].update(captures=int(cap.sum()), timeouts=int(tmo.sum()), top_capture_cell=top(cap), top_timeout_cell=top(tmo))
             out.append({"rows": int(c["rows"][g]), "agents": per_agent})
         return out

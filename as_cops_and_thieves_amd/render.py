@@ -129,6 +129,7 @@ def _heat_palette() -> np.ndarray:
 
 HEAT_PALETTE = _heat_palette()
 HEATMAP_PLANES = ("occ", "seen", "hidden", "spawn")     # hidden = occ - seen
+HEATMAP_END_PLANES = ("capture", "timeout")             # a tracker with final positions: where episodes ended
 
 
 def render_heatmap(cmap: CompiledMap, plane: np.ndarray, cell: int, vmax: Optional[int] = None, palette: np.ndarray = HEAT_PALETTE) -> np.ndarray:
@@ -160,8 +161,9 @@ def write_heatmaps(directory, tracker, maps, group_names: Optional[Sequence[str]
     ``render_heatmap``; hidden = occ - seen) under ``directory`` and the raw counts in ``positions.npz`` (``counts``, ``outside``, ``rows``,
     ``done``, ``cell``, ``agents``, ``groups``).  ``maps``: the batch's maps (``Map`` or ``CompiledMap``; one or a list); ``group_maps[g]``:
     the map group g is drawn over (default: the first); ``group_names``: the directory names (default ``group_0`` ..; None for a group
-    that gets no pictures).  One
-    synchronisation (``tracker.counts()``).  Returns those counts."""
+    that gets no pictures).  A tracker that keeps the capture / timeout maps (``final_positions=True``) also gets
+    ``{group}/{agent}_{capture|timeout}.png`` and ``ends`` / ``ends_outside`` in the npz; any other tracker gets exactly the files and
+    arrays above.  One synchronisation (``tracker.counts()``).  Returns those counts."""
     from pathlib import Path
     directory = Path(directory)
     maps = list(maps) if isinstance(maps, (list, tuple)) else [maps]
@@ -173,7 +175,8 @@ def write_heatmaps(directory, tracker, maps, group_names: Optional[Sequence[str]
         raise ValueError(f"write_heatmaps: {G} groups need {G} names and {G} map indices below {len(compiled)}")
     c = tracker.counts()
     directory.mkdir(parents=True, exist_ok=True)
-    np.savez_compressed(directory / npz_name, counts=c["counts"], outside=c["outside"], rows=c["rows"], done=c["done"],
+    extra = {k: c[k] for k in ("ends", "ends_outside") if k in c}
+    np.savez_compressed(directory / npz_name, counts=c["counts"], outside=c["outside"], rows=c["rows"], done=c["done"], **extra,
                         cell=np.int64(tracker.cell), agents=np.array(tracker.agents), groups=np.array(["" if n is None else n for n in names]))
     for g in range(G):
         if names[g] is None:
@@ -183,6 +186,10 @@ def write_heatmaps(directory, tracker, maps, group_names: Optional[Sequence[str]
             occ, seen, spawn = c["counts"][g, 0, i], c["counts"][g, 1, i], c["counts"][g, 2, i]
             for plane_name, plane in zip(HEATMAP_PLANES, (occ, seen, occ - seen, spawn)):
                 write_png(directory / names[g] / f"{aid}_{plane_name}.png", render_heatmap(compiled[which[g]], plane, tracker.cell, vmax, palette))
+            if "ends" in c:
+                for k, plane_name in enumerate(HEATMAP_END_PLANES):
+                    write_png(directory / names[g] / f"{aid}_{plane_name}.png",
+                              render_heatmap(compiled[which[g]], c["ends"][g, k, i], tracker.cell, vmax, palette))
     return c
 
 

@@ -59,7 +59,7 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
     if env_factory is None:
         from ..environments import VecCopsEnv
         from ..maps import load_preset
-        track = {} if heatmaps is None else {"track_positions": int(cell), "position_groups": per_pass}
+        track = {} if heatmaps is None else {"track_positions": int(cell), "position_groups": per_pass, "final_positions": True}
         env = VecCopsEnv(load_preset(map_name, n_cops, n_thieves), N, num_rays=num_rays, max_step_count=max_step_count, seed=seed, device=device,
                          **track)
     else:

@@ -722,7 +722,7 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         if position_stats is not None:
             eval_factory = lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
                                                           env_id_offset=off, query_order=query_order, track_episodes=tracked_eval,
-                                                          track_positions=position_stats)
+                                                          track_positions=position_stats, final_positions=True)
     n_local, offset = shard_envs(num_envs, rank, world)
     if multi:
         # checked on EVERY rank from the same numbers, so that all of them refuse together (a rank that raised alone would leave the others in the

@@ -28,10 +28,11 @@ from .self_play import _initial_states, _skip_kw, _trainer_actions
 
 
 def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None,
-             n_thieves: Optional[int] = None, device=None) -> VecCopsEnv:
+             n_thieves: Optional[int] = None, device=None, final_positions: bool = False) -> VecCopsEnv:
     """The env ``watch`` plays on (its reset state is what frame 0 shows)."""
     preset = load_preset(map_name, n_cops, n_thieves)
-    return VecCopsEnv(preset, envs, num_rays=num_rays, max_step_count=max_step_count, seed=seed, device=device, auto_reset=False)
+    return VecCopsEnv(preset, envs, num_rays=num_rays, max_step_count=max_step_count, seed=seed, device=device, auto_reset=False,
+                      final_positions=final_positions)
 
 
 @torch.no_grad()
@@ -40,7 +41,8 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
           log=print, fused_act: bool = False, greedy: bool = False, frame_skip: int = 1, heatmap: Optional[int] = None) -> Dict[str, object]:
     """``heatmap=CELL``: a ``positions.PositionTracker`` on a grid of CELL x CELL pixels is fed every decision's rows of the slots still
     playing (this env does not auto-reset, so the terminal row holds the episode's last position and counts as occupancy, and there is no
-    spawn map), and ``heatmaps/`` next to the clips receives the pictures and ``positions.npz`` (``render.write_heatmaps``).
+    spawn map), and ``heatmaps/`` next to the clips receives the pictures and ``positions.npz`` (``render.write_heatmaps``).  The env is
+    built with ``final_positions=True``, so the capture / timeout maps of the episodes played are among them.
     ``frame_skip`` k > 1: the policies decide once per ``env.step(actions, repeat=k)`` and one frame is drawn per decision; ``ticks`` is then
     the most decisions played, a slot's ``length`` stays in env ticks (the sum of its ``infos["ticks"]``).
     ``fused_act``: no trainer is built -- a ``PolicyActor`` reads the checkpoint's policy blocks and acts (on a GPU: one launch per tick,
@@ -48,7 +50,7 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
     out_dir = Path(out_dir)
     skip = _skip_kw(frame_skip)
     torch.manual_seed(seed)
-    env = make_env(map_name, envs, seed, num_rays, max_step_count, n_cops, n_thieves, device)
+    env = make_env(map_name, envs, seed, num_rays, max_step_count, n_cops, n_thieves, device, final_positions=heatmap is not None)
     if greedy and not fused_act:
         raise ValueError("greedy=True needs fused_act=True (the default path samples, as self_play.evaluate_agents)")
     actor = None
@@ -75,7 +77,7 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
     tracker = None
     if heatmap is not None:
         from ..positions import PositionTracker
-        tracker = PositionTracker(N, env.possible_agents, len(env.cops), (W, H), heatmap, 1, env.device)
+        tracker = PositionTracker(N, env.possible_agents, len(env.cops), (W, H), heatmap, 1, env.device, final_positions=True)
         never = torch.zeros(N, dtype=torch.uint8, device=env.device)
     obs, _ = env.reset()
     who = actor if actor is not None else runner
@@ -98,6 +100,7 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
             raw = env.raw_outputs()
             tracker.set_groups([0 if o else -1 for o in open_host])
             tracker.update(raw["team_positions"], never, raw["obs_type"])
+            tracker.update_ends(raw["final_positions"], raw["terminated"], raw["truncated"])     # where the slots that ended just now did
         done = terms[who.agents[0]].cpu().tolist()
         win = infos["winner"].cpu().tolist()
         if skip:

@@ -42,6 +42,9 @@ class CatSimError(RuntimeError):
     pass
 
 
+FINAL_POS_NAN = 0x7E00   # float16 quiet NaN: the pre-fill of a final-positions buffer (rows of ticks that end no episode keep it)
+
+
 class CatSim:
     def __init__(self, cfg: SimConfig, maps: Sequence[CompiledMap], slot_map_ids=None,
                  device: Optional[torch.device | int | str] = None, debug_hit_shape: bool = False):
@@ -171,6 +174,32 @@ class CatSim:
                                             self.out["ticks"].data_ptr(), self._stream()), "cat_step_repeat")
         return self.out
 
+    def bind_final_positions(self, buf: Optional[torch.Tensor]) -> None:
+        """End-of-episode positions (cat_bind_final_positions).  While ``buf`` is bound, every stepping call writes the tick-start positions of
+        every slot-row whose ``terminated`` flag that tick sets -- where the episode ended, which under auto-reset ``team_positions`` no longer
+        shows -- into the row ``team_positions`` of the same call would use, and touches no other row: pre-fill the buffer (``FINAL_POS_NAN``).
+        ``buf``: a contiguous ``torch.float16`` tensor on the sim's device, ``[N, A, 2]`` (``step`` / ``step_fused`` / ``step_repeat``) or
+        ``[T, N, A, 2]`` (``rollout_fused`` of up to T ticks; the one-tick calls then use row 0), or None to detach.  Anything else raises
+        ``ValueError`` before any native call.  The sim keeps a reference.  A captured graph keeps writing to the buffer bound at capture:
+        rebinding needs a recapture."""
+        if buf is not None:
+            self.check_final_positions(buf, self.N, self.A, self.device)
+        self._check(self._L.cat_bind_final_positions(self._h, None if buf is None else buf.data_ptr()), "cat_bind_final_positions")
+        self._final_pos = buf
+
+    @staticmethod
+    def check_final_positions(buf, N: int, A: int, device) -> None:
+        if not isinstance(buf, torch.Tensor):
+            raise ValueError(f"final positions: a torch tensor or None is needed, got {type(buf).__name__}")
+        if buf.dtype != torch.float16:
+            raise ValueError(f"final positions: dtype must be torch.float16, got {buf.dtype}")
+        if tuple(buf.shape) != (N, A, 2) and not (buf.dim() == 4 and buf.shape[0] >= 1 and tuple(buf.shape[1:]) == (N, A, 2)):
+            raise ValueError(f"final positions: shape must be {(N, A, 2)} or (T, {N}, {A}, 2), got {tuple(buf.shape)}")
+        if buf.device != torch.device(device):
+            raise ValueError(f"final positions: the buffer must live on {device}, got {buf.device}")
+        if not buf.is_contiguous():
+            raise ValueError("final positions: the buffer must be contiguous")
+
     def rollout_buffers(self, T: int) -> Dict[str, torch.Tensor]:
         """Caller-owned output buffers with a leading T for ``rollout_fused`` (cached per T)."""
         cache = self.__dict__.setdefault("_rollout_bufs", {})
@@ -198,6 +227,9 @@ class CatSim:
             if actions.shape != (T, self.N, self.A):
                 raise ValueError(f"actions must have shape {(T, self.N, self.A)}, got {tuple(actions.shape)}")
             ptr = actions.data_ptr()
+        fp = getattr(self, "_final_pos", None)
+        if fp is not None and (fp.dim() != 4 or fp.shape[0] < T):
+            raise ValueError(f"rollout_fused(T={T}) with final positions bound needs a [T, N, A, 2] buffer, the bound one is {tuple(fp.shape)}")
         view = nat.CatOutputs(*[bufs[k].data_ptr() if k in bufs else None for k in nat.OUT_FIELDS])
         self._check(self._L.cat_rollout_fused(self._h, T, ptr, int(tick), int(auto_reset), C.byref(view), self._stream()),
                     "cat_rollout_fused")

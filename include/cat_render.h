@@ -86,7 +86,7 @@ int cat_render_frames(const cat_render_scene *scene, const cat_render_args *a, v
  *   term = terminated[t][n] != 0; for every agent a, (x, y) are the two f16 values of team_positions[t][n][a].  The position is valid
  *   iff both are finite, x >= 0, y >= 0, cx = (int)floor(x) / cell < Wc and cy = (int)floor(y) / cell < Hc (integer division).
  *   Invalid: outside[g][a] += 1.  Valid and term: counts[g][SPAWN][a][cx][cy] += 1 (the env resets a slot inside its terminal tick, so
- *   a terminal row holds the first position of the NEW episode; the position at which the old one ended is not available).  Valid and
+ *   a terminal row holds the first position of the NEW episode; where the old one ended: cat_render_positions_ends_update below).  Valid and
  *   not term: counts[g][OCC][a][cx][cy] += 1 and, if obs_type is given and seen(a) holds, counts[g][SEEN][a][cx][cy] += 1.  Finally
  *   done[n] += term.
  *   seen(a): some agent b of the OTHER role has a ray k with obs_type[t][n][b][k] == a's role code (CAT_COP = 1 for a < n_cops,
@@ -117,6 +117,42 @@ typedef struct cat_render_positions_args {
 
 /* An entry added after ABI version 1 was fixed (cat_render_frames and its two structs are unchanged). */
 int cat_render_positions_update(const cat_render_positions_args *a, void *stream);
+
+/*
+ * Where episodes END: capture and timeout maps.  cat_render_positions_ends_update adds T >= 1 consecutive rows of the env core's end-of-episode
+ * positions (cat_bind_final_positions, include/cat_sim.h: on a terminal row the tick-start positions of the episode that ended, any other row is
+ * never read) into ends [G][2][A][Wc][Hc] int64, planes CAT_POSITIONS_CAPTURE / _TIMEOUT, and ends_outside [G][2][A] int64, on the grid and with
+ * the groups of cat_render_positions_update.  One launch, no allocation, no synchronisation (capturable).
+ *
+ *   Row t of slot n, g = group[n]: skipped if g is no group, or if quota is non-NULL and d[n] >= quota[n], where d[n] starts at done_before[n]
+ *   (0 where done_before is NULL) and grows by one with every terminal row of the slot in this call -- the quota rule of
+ *   cat_render_positions_update.  done_before is only read: give this entry the positions update's `done` BEFORE that update has advanced it over
+ *   the same rows (run this entry first, or pass a copy).  Only rows with terminated[t][n] != 0 count: plane = truncated[t][n] != 0 ? TIMEOUT :
+ *   CAPTURE; for every agent a, (x, y) are the two f16 values of final_positions[t][n][a], valid iff both are finite, x >= 0, y >= 0,
+ *   cx = (int)floor(x) / cell < Wc and cy = (int)floor(y) / cell < Hc (integer division).  Invalid: ends_outside[g][plane][a] += 1.
+ *   Valid: ends[g][plane][a][cx][cy] += 1.
+ *
+ * All sums are integers (64-bit global atomics): the result does not depend on the order or on how rows are chunked into launches (with
+ * done_before carried along).  positions.PositionTracker (NumPy) defines every number.
+ */
+#define CAT_POSITIONS_CAPTURE 0
+#define CAT_POSITIONS_TIMEOUT 1
+
+typedef struct cat_render_positions_ends_args {
+    int32_t T, N, A, cell;          /* rows, slots, agents (<= CAT_RENDER_MAX_AGENTS), cell size in pixels (>= 1) */
+    int32_t Wc, Hc, G, pad;         /* grid cells, groups (>= 1) */
+    const uint16_t *final_positions;/* [T][N][A][2] float16 bits, 4-byte aligned; read on terminal rows only */
+    const uint8_t *terminated;      /* [T][N] */
+    const uint8_t *truncated;       /* [T][N] */
+    const int32_t *group;           /* [N] or NULL = all slots in group 0 */
+    const int32_t *quota;           /* [N] or NULL = unlimited */
+    const int32_t *done_before;     /* [N] terminal rows each slot had before row 0, or NULL = none; read only */
+    int64_t *ends;                  /* [G][2][A][Wc][Hc] */
+    int64_t *ends_outside;          /* [G][2][A] */
+} cat_render_positions_ends_args;
+
+/* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
+int cat_render_positions_ends_update(const cat_render_positions_ends_args *a, void *stream);
 
 #ifdef __cplusplus
 }

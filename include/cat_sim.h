@@ -206,6 +206,20 @@ int cat_rollout_fused(cat_sim *sim, int T, const int32_t *actions, uint64_t synt
 int cat_step_repeat(cat_sim *sim, int k, const int32_t *actions, int auto_reset,
                     const cat_outputs *out, int32_t *ticks, void *stream);
 
+/* END-OF-EPISODE POSITIONS.  An entry added after ABI version 1 was fixed (cat_outputs and CAT_ABI_VERSION are unchanged: the handle keeps the pointer).
+   Under auto-reset a slot that ends an episode is stepped, respawned and traced for its new episode inside the same tick, so the terminal row's
+   team_positions already holds the spawn point of the NEXT episode.  While a buffer is bound, every stepping entry -- cat_step, cat_step_fused,
+   cat_rollout_fused, cat_step_repeat, auto_reset 0 or 1 -- writes, for every slot-row whose `terminated` flag that tick sets, the float16 bits
+   (as team_positions) of the 2A tick-start body positions: the ones the termination check read (base_env.py:521-554) and team_positions would have
+   carried without the reset (observation_spaces.py:92-95).  The buffer is addressed exactly like team_positions of the same call: [N,A,2] for the
+   one-tick entries and for cat_step_repeat (the window's last played tick: the only one that can be terminal), [T,N,A,2] for cat_rollout_fused (row
+   t*N + env), and must be that large.  Rows that are not terminal are NOT TOUCHED: the caller pre-fills them (a NaN pattern such as 0x7E00), and the
+   common path gains no store.  cat_reset / cat_reset_done write nothing.  With auto_reset == 0 a terminal row equals team_positions of the same call.
+   No allocation, no synchronisation, no device call (capturable); takes effect from the next launch.  The pointer travels in the launch arguments, so
+   a HIP graph captured with a buffer bound keeps writing to THAT buffer: rebinding or detaching needs a recapture.
+   No reference counterpart (the reference resets in a separate call: its positions at the end of an episode are simply still there). */
+int cat_bind_final_positions(cat_sim *sim, uint16_t *buf);   /* DEVICE, or NULL = detach (the default) */
+
 /* Env-state access (the reference cannot checkpoint env state). D2D copies. */
 int cat_get_state(cat_sim *sim, const cat_state *dst, void *stream);
 int cat_set_state(cat_sim *sim, const cat_state *src, void *stream);
