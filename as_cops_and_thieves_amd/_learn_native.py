@@ -30,7 +30,8 @@ MODULES = {
     "cat_trunk": (2, {"cat_trunk_out_positions": _QUERY, "cat_trunk_supported": _QUERY, "cat_trunk_backward_blocks": _QUERY,
                       "cat_trunk_forward": _ENTRY, "cat_trunk_backward": _ENTRY, "cat_trunk_grad_finish": _ENTRY}),
     "cat_ppo": (2, {"cat_ppo_loss_grad": _ENTRY, "cat_ppo_adam_step": _ENTRY, "cat_ppo_gae_scan": _ENTRY, "cat_ppo_gae_scan_scaled": _ENTRY,
-                    "cat_ppo_moment_chunks": (C.c_int, [C.c_int32]), "cat_ppo_moments": _ENTRY}),
+                    "cat_ppo_moment_chunks": (C.c_int, [C.c_int32]), "cat_ppo_moments": _ENTRY,
+                    "cat_ppo_loss_grad_dev": _ENTRY, "cat_ppo_adam_step_dev": _ENTRY, "cat_ppo_schedule_step": _ENTRY}),
     "cat_dense": (2, {"cat_dense_bias_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
                       "cat_dense_act_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
                       "cat_dense_sum_chunks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -149,6 +150,22 @@ class PpoAdam(C.Structure):
                 ("kl_out", C.c_void_p), ("norm_partial", C.c_void_p),
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("grad_norm_clip", C.c_float), ("kl_threshold", C.c_float)]
+
+
+class PpoLossDev(C.Structure):
+    _fields_ = PpoLoss._fields_ + [("hyper", C.c_void_p)]
+
+
+class PpoAdamDev(C.Structure):
+    _fields_ = PpoAdam._fields_ + [("hyper", C.c_void_p)]
+
+
+class PpoSchedule(C.Structure):
+    _fields_ = [("G", C.c_int32), ("mode", C.c_int32), ("anneal_mask", C.c_int32), ("pad", C.c_int32),
+                ("hyper", C.c_void_p), ("sched_active", C.c_void_p),
+                ("kl_target", C.c_float), ("kl_factor", C.c_float), ("lr_factor", C.c_float), ("lr_min", C.c_float), ("lr_max", C.c_float),
+                ("progress", C.c_float),
+                ("lr0", C.c_float), ("lr1", C.c_float), ("ent0", C.c_float), ("ent1", C.c_float), ("clip0", C.c_float), ("clip1", C.c_float)]
 
 
 class TrunkFinish(C.Structure):
@@ -402,6 +419,71 @@ def ppo_adam_step(ar, col_train, epoch_active, m, v, steps, master, lp, kl_out, 
     a = PpoAdam(G, P, 256, 0, ar.data_ptr(), col_train.data_ptr(), epoch_active.data_ptr(), m.data_ptr(), v.data_ptr(), steps.data_ptr(),
                 master.data_ptr(), _ptr(lp), kl_out.data_ptr(), scratch.data_ptr(), lr, beta1, beta2, eps, grad_norm_clip, kl_threshold or 0.0)
     _check(lib().cat_ppo_adam_step(C.byref(a), _stream()), "cat_ppo_adam_step")
+
+
+# the hyper block of the _dev entries: fp32 [G, PPO_HYPER_STRIDE] on the device (include/cat_ppo.h)
+PPO_HYPER_STRIDE = 8                                                    # CAT_PPO_HYPER_STRIDE
+HYPER_LR, HYPER_ENTROPY, HYPER_RATIO_CLIP, HYPER_KL_SUM, HYPER_KL_COUNT = range(5)      # CAT_PPO_HYPER_*
+SCHED_KL, SCHED_ANNEAL = 1, 2                                           # cat_ppo_schedule.mode (bits)
+ANNEAL_LR, ANNEAL_ENTROPY, ANNEAL_RATIO_CLIP = 1, 2, 4                  # cat_ppo_schedule.anneal_mask (bits)
+SCHED_MAX_AGENTS = 8                                                    # CAT_ROLLOUT_MAX_AGENTS
+
+
+def _hyper_ok(hyper, G: int, like) -> None:
+    import torch
+    assert hyper.dtype == torch.float32 and hyper.is_contiguous() and hyper.shape == (G, PPO_HYPER_STRIDE) and hyper.device == like.device
+
+
+def ppo_loss_grad_dev(logits, values, actions, old_logp, adv, ret, hyper, value_scale: float):
+    """``ppo_loss_grad`` with agent g's ratio clip and entropy scale read from ``hyper`` fp32 [G, 8] on the device (columns HYPER_RATIO_CLIP
+    and HYPER_ENTROPY) at the time the kernel runs: a captured call follows the block without a recapture."""
+    import torch
+    G = logits.shape[0]
+    M = logits[0].numel() // 4
+    for t, dt in ((logits, torch.bfloat16), (values, torch.bfloat16), (actions, torch.int64), (old_logp, torch.float32),
+                  (adv, torch.float32), (ret, torch.float32)):
+        assert t.dtype == dt and t.is_contiguous() and t.shape[0] == G
+    assert values[0].numel() == M and actions[0].numel() == M and old_logp[0].numel() == M and adv[0].numel() == M and ret[0].numel() == M
+    _hyper_ok(hyper, G, logits)
+    d_logits, d_values = torch.empty_like(logits), torch.empty_like(values)
+    partial = torch.empty(G, PPO_CHUNKS, 4, dtype=torch.float32, device=logits.device)
+    a = PpoLossDev(G, M, PPO_CHUNKS, 0, logits.data_ptr(), values.data_ptr(), actions.data_ptr(), old_logp.data_ptr(), adv.data_ptr(),
+                   ret.data_ptr(), 0.0, value_scale, 0.0, 0.0, d_logits.data_ptr(), d_values.data_ptr(), partial.data_ptr(), hyper.data_ptr())
+    _check(lib().cat_ppo_loss_grad_dev(C.byref(a), _stream()), "cat_ppo_loss_grad_dev")
+    return torch.bmm(ones_row(G, PPO_CHUNKS, logits.device), partial).squeeze(1), d_logits, d_values
+
+
+def ppo_adam_step_dev(ar, col_train, epoch_active, m, v, steps, master, lp, kl_out, scratch, hyper, beta1, beta2, eps, grad_norm_clip,
+                      kl_threshold) -> None:
+    """``ppo_adam_step`` with agent g's learning rate read from ``hyper`` fp32 [G, 8] on the device (column HYPER_LR); an agent that enters
+    the step with ``epoch_active`` set adds its KL to HYPER_KL_SUM and 1 to HYPER_KL_COUNT."""
+    import torch
+    G, P = master.shape
+    for t in (ar, col_train, epoch_active, m, v, steps, master, kl_out, scratch):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert ar.shape == (G, P + 1) and col_train.shape == (G, P) and scratch.shape == (G, 256) and kl_out.shape == (G,)
+    assert lp is None or (lp.dtype == torch.bfloat16 and lp.is_contiguous() and lp.shape == (G, P))
+    _hyper_ok(hyper, G, master)
+    a = PpoAdamDev(G, P, 256, 0, ar.data_ptr(), col_train.data_ptr(), epoch_active.data_ptr(), m.data_ptr(), v.data_ptr(), steps.data_ptr(),
+                   master.data_ptr(), _ptr(lp), kl_out.data_ptr(), scratch.data_ptr(), 0.0, beta1, beta2, eps, grad_norm_clip,
+                   kl_threshold or 0.0, hyper.data_ptr())
+    _check(lib().cat_ppo_adam_step_dev(C.byref(a), _stream()), "cat_ppo_adam_step_dev")
+
+
+def ppo_schedule_step(hyper, sched_active, mode: int, *, kl_target: float = 0.008, kl_factor: float = 2.0, lr_factor: float = 1.5,
+                      lr_min: float = 1e-6, lr_max: float = 1e-2, anneal_mask: int = 0, progress: float = 0.0,
+                      lr=(0.0, 0.0), entropy=(0.0, 0.0), ratio_clip=(0.0, 0.0)) -> None:
+    """The schedule rule on ``hyper`` fp32 [G, 8] in place (one tiny launch; include/cat_ppo.h): ``mode`` = SCHED_ANNEAL (the fields of
+    ``anneal_mask`` <- x0 + (x1 - x0) * progress from the (x0, x1) pairs), SCHED_KL (the KL-adaptive learning rate of the agents with
+    ``sched_active`` fp32 [G] set, from the epoch's KL sum, which is cleared) or both (the anneal first)."""
+    import torch
+    G = hyper.shape[0]
+    assert 1 <= G <= SCHED_MAX_AGENTS
+    _hyper_ok(hyper, G, hyper)
+    assert sched_active.dtype == torch.float32 and sched_active.is_contiguous() and sched_active.shape == (G,) and sched_active.device == hyper.device
+    a = PpoSchedule(G, mode, anneal_mask, 0, hyper.data_ptr(), sched_active.data_ptr(), kl_target, kl_factor, lr_factor, lr_min, lr_max,
+                    progress, lr[0], lr[1], entropy[0], entropy[1], ratio_clip[0], ratio_clip[1])
+    _check(lib().cat_ppo_schedule_step(C.byref(a), _stream()), "cat_ppo_schedule_step")
 
 
 class PpoGae(C.Structure):

@@ -1,5 +1,6 @@
-// cat_ppo.hip -- libcat_learn.so, part 3 of 8: PPO loss + gradient, the optimiser step, the GAE scan (plain and over a normalised
-// critic) and the running f64 moments of the returns (include/cat_ppo.h).
+// cat_ppo.hip -- libcat_learn.so, part 3 of 8: PPO loss + gradient, the optimiser step (each also with its hyper-parameters read from
+// device memory), the schedule rule on those, the GAE scan (plain and over a normalised critic) and the running f64 moments of the
+// returns (include/cat_ppo.h).
 //
 // The first two are a few flops per element over at most a few million elements: as library elementwise kernels they are
 // ~110 launches of ~5 us per minibatch step inside the replayed HIP graph (each a dependent graph node), about a tenth
@@ -9,6 +10,7 @@
 // consumer), never a semaphore-style single-pass reduction.
 #include "cat_learn_common.h"
 #include "cat_ppo.h"
+#include "cat_rollout.h"
 #include <type_traits>
 
 namespace {
@@ -34,12 +36,21 @@ __device__ __forceinline__ void block_sum(float (&v)[N], float *lds)
         for (int i = 0; i < N; ++i) v[i] = lds[i] + lds[N + i] + lds[2 * N + i] + lds[3 * N + i];
 }
 
-__global__ __launch_bounds__(BLOCK) void ppo_loss_kernel(const cat_ppo_loss a)
+// Args = cat_ppo_loss_dev: the ratio clip and the entropy scale are agent g's words of the hyper block in device memory (a replayed
+// graph sees what the block holds then); nothing else differs.
+template <class Args>
+__global__ __launch_bounds__(BLOCK) void ppo_loss_kernel(const Args a)
 {
+    constexpr bool DEV = std::is_same<Args, cat_ppo_loss_dev>::value;
     __shared__ float lds[4 * 4];
     const int g = blockIdx.y, M = a.M;
     const size_t base = (size_t)g * M;
-    const float inv_m = 1.0f / (float)M, lo = 1.0f - a.ratio_clip, hi = 1.0f + a.ratio_clip;
+    float ratio_clip = a.ratio_clip, entropy_scale = a.entropy_scale;
+    if constexpr (DEV) {
+        const float *h = a.hyper + (size_t)g * CAT_PPO_HYPER_STRIDE;
+        ratio_clip = h[CAT_PPO_HYPER_RATIO_CLIP]; entropy_scale = h[CAT_PPO_HYPER_ENTROPY];
+    }
+    const float inv_m = 1.0f / (float)M, lo = 1.0f - ratio_clip, hi = 1.0f + ratio_clip;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < M; i += gridDim.x * BLOCK) {
         const size_t s = base + i;
@@ -66,7 +77,7 @@ __global__ __launch_bounds__(BLOCK) void ppo_loss_kernel(const cat_ppo_loss a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float onehot = (j == act) ? 1.0f : 0.0f;
-            dz[j] = inv_m * (-dsurr * (onehot - p[j]) + a.entropy_scale * p[j] * (lp[j] + ent));
+            dz[j] = inv_m * (-dsurr * (onehot - p[j]) + entropy_scale * p[j] * (lp[j] + ent));
         }
         *(bf16x4 *)((__bf16 *)a.d_logits + 4 * s) = __builtin_convertvector(dz, bf16x4);
         ((__bf16 *)a.d_values)[s] = (__bf16)(2.0f * a.value_scale * inv_m * dv);
@@ -78,7 +89,8 @@ __global__ __launch_bounds__(BLOCK) void ppo_loss_kernel(const cat_ppo_loss a)
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void grad_norm_kernel(const cat_ppo_adam a)
+template <class Args>
+__global__ __launch_bounds__(BLOCK) void grad_norm_kernel(const Args a)
 {
     __shared__ float lds[4];
     const int g = blockIdx.y, P = a.P;
@@ -92,8 +104,12 @@ __global__ __launch_bounds__(BLOCK) void grad_norm_kernel(const cat_ppo_adam a)
     if (threadIdx.x == 0) a.norm_partial[(size_t)g * gridDim.x + blockIdx.x] = acc[0];
 }
 
-__global__ __launch_bounds__(BLOCK) void adam_kernel(const cat_ppo_adam a)
+// Args = cat_ppo_adam_dev: the learning rate is agent g's word of the hyper block, and the thread that rewrites epoch_active[g] adds the
+// minibatch's KL to the block's sum when the agent entered the step active (include/cat_ppo.h); nothing else differs.
+template <class Args>
+__global__ __launch_bounds__(BLOCK) void adam_kernel(const Args a)
 {
+    constexpr bool DEV = std::is_same<Args, cat_ppo_adam_dev>::value;
     __shared__ float lds[4];
     __shared__ float s_scale, s_active;
     const int g = blockIdx.y, P = a.P;
@@ -105,11 +121,22 @@ __global__ __launch_bounds__(BLOCK) void adam_kernel(const cat_ppo_adam a)
         const float norm = sqrtf(acc[0]), kl = ar[P];
         s_scale = fminf(a.grad_norm_clip / (norm + 1e-6f), 1.0f);
         // the gate is idempotent (a 0/1 factor), so blocks that read epoch_active after block 0 rewrote it agree
-        const float active = a.epoch_active[g] * ((a.kl_threshold > 0.0f && !(kl <= a.kl_threshold)) ? 0.0f : 1.0f);
+        const float was = a.epoch_active[g];
+        const float active = was * ((a.kl_threshold > 0.0f && !(kl <= a.kl_threshold)) ? 0.0f : 1.0f);
         s_active = active;
-        if (blockIdx.x == 0) { a.epoch_active[g] = active; a.kl_out[g] = kl; }
+        if (blockIdx.x == 0) {
+            if constexpr (DEV) {    // block 0 is the only writer of epoch_active[g], so ``was`` is the value the step was entered with
+                if (was != 0.0f) {
+                    float *h = a.hyper + (size_t)g * CAT_PPO_HYPER_STRIDE;
+                    h[CAT_PPO_HYPER_KL_SUM] += kl; h[CAT_PPO_HYPER_KL_COUNT] += 1.0f;
+                }
+            }
+            a.epoch_active[g] = active; a.kl_out[g] = kl;
+        }
     }
     __syncthreads();
+    float lr = a.lr;
+    if constexpr (DEV) lr = a.hyper[(size_t)g * CAT_PPO_HYPER_STRIDE + CAT_PPO_HYPER_LR];
     const float scale = s_scale, active = s_active, b1 = a.beta1, b2 = a.beta2;
     const size_t row = (size_t)g * P;
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < P; i += gridDim.x * BLOCK) {
@@ -121,7 +148,7 @@ __global__ __launch_bounds__(BLOCK) void adam_kernel(const cat_ppo_adam a)
         v += gate * (1.0f - b2) * (gr * gr - v);
         const float s = fmaxf(st, 1.0f);
         const float bc1 = 1.0f - powf(b1, s), bc2 = 1.0f - powf(b2, s);
-        w -= gate * a.lr * (m / bc1) / (sqrtf(v / bc2) + a.eps);
+        w -= gate * lr * (m / bc1) / (sqrtf(v / bc2) + a.eps);
         a.steps[row + i] = st; a.m[row + i] = m; a.v[row + i] = v; a.master[row + i] = w;
         if (a.lp) ((__bf16 *)a.lp)[row + i] = (__bf16)w;
     }
@@ -261,6 +288,63 @@ __global__ __launch_bounds__(BLOCK) void moments_merge_kernel(const cat_ppo_mome
     }
 }
 
+// ---- the schedule rule on the hyper block (include/cat_ppo.h has the order; every operation below is one rounded fp32 operation)
+__device__ __forceinline__ float annealed(float x0, float x1, float progress)
+{
+#pragma clang fp contract(off)
+    const float d = x1 - x0;
+    const float p = d * progress;
+    return x0 + p;
+}
+
+// one workgroup, thread g = agent g
+__global__ __launch_bounds__(64) void schedule_kernel(const cat_ppo_schedule a)
+{
+#pragma clang fp contract(off)
+    const int g = threadIdx.x;
+    if (g >= a.G) return;
+    float *h = a.hyper + (size_t)g * CAT_PPO_HYPER_STRIDE;
+    if (a.mode & CAT_PPO_SCHED_ANNEAL) {
+        if (a.anneal_mask & CAT_PPO_ANNEAL_LR) h[CAT_PPO_HYPER_LR] = annealed(a.lr0, a.lr1, a.progress);
+        if (a.anneal_mask & CAT_PPO_ANNEAL_ENTROPY) h[CAT_PPO_HYPER_ENTROPY] = annealed(a.ent0, a.ent1, a.progress);
+        if (a.anneal_mask & CAT_PPO_ANNEAL_RATIO_CLIP) h[CAT_PPO_HYPER_RATIO_CLIP] = annealed(a.clip0, a.clip1, a.progress);
+    }
+    if (a.mode & CAT_PPO_SCHED_KL) {
+        const float hi = a.kl_target * a.kl_factor, lo = a.kl_target / a.kl_factor;
+        const float count = h[CAT_PPO_HYPER_KL_COUNT];
+        if (count > 0.0f && a.sched_active[g] != 0.0f) {
+            const float kl = h[CAT_PPO_HYPER_KL_SUM] / count;
+            float lr = h[CAT_PPO_HYPER_LR];
+            if (kl > hi) lr = fmaxf(lr / a.lr_factor, a.lr_min);
+            else if (kl < lo) lr = fminf(lr * a.lr_factor, a.lr_max);
+            h[CAT_PPO_HYPER_LR] = lr;
+        }
+        h[CAT_PPO_HYPER_KL_SUM] = 0.0f; h[CAT_PPO_HYPER_KL_COUNT] = 0.0f;
+    }
+}
+
+// the checks cat_ppo_loss_grad and cat_ppo_loss_grad_dev share
+template <class Args>
+int loss_checked(const Args *a, const char *who)
+{
+    if (!a || a->G <= 0 || a->G > 65535 || a->M <= 0 || a->chunks <= 0 || a->chunks > CAT_PPO_MAX_CHUNKS)
+        return fail(CAT_PPO_ERR_BAD_ARG, who, "bad dimensions");
+    if (!a->logits || !a->values || !a->actions || !a->old_logp || !a->adv || !a->ret || !a->d_logits || !a->d_values || !a->partial)
+        return fail(CAT_PPO_ERR_BAD_ARG, who, "a required buffer is NULL");
+    if (((uintptr_t)a->logits % 8) || ((uintptr_t)a->d_logits % 8))
+        return fail(CAT_PPO_ERR_BAD_ARG, who, "logits must be 8-byte aligned");
+    return CAT_PPO_OK;
+}
+
+template <class Args>
+int adam_checked(const Args *a, const char *who)
+{
+    if (!a || a->G <= 0 || a->G > 65535 || a->P <= 0 || a->chunks <= 0 || a->chunks > CAT_PPO_MAX_CHUNKS)
+        return fail(CAT_PPO_ERR_BAD_ARG, who, "bad dimensions");
+    if (!a->ar || !a->col_train || !a->epoch_active || !a->m || !a->v || !a->steps || !a->master || !a->kl_out || !a->norm_partial)
+        return fail(CAT_PPO_ERR_BAD_ARG, who, "a required buffer is NULL");
+    return CAT_PPO_OK;
+}
 
 }   // namespace
 
@@ -269,13 +353,16 @@ extern "C" const char *cat_ppo_last_error(void) { return g_err; }
 
 extern "C" int cat_ppo_loss_grad(const cat_ppo_loss *a, void *stream)
 {
-    if (!a || a->G <= 0 || a->G > 65535 || a->M <= 0 || a->chunks <= 0 || a->chunks > CAT_PPO_MAX_CHUNKS)
-        return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_loss_grad: bad dimensions");
-    if (!a->logits || !a->values || !a->actions || !a->old_logp || !a->adv || !a->ret || !a->d_logits || !a->d_values || !a->partial)
-        return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_loss_grad: a required buffer is NULL");
-    if (((uintptr_t)a->logits % 8) || ((uintptr_t)a->d_logits % 8))
-        return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_loss_grad: logits must be 8-byte aligned");
-    hipLaunchKernelGGL(ppo_loss_kernel, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    if (const int rc = loss_checked(a, "cat_ppo_loss_grad")) return rc;
+    hipLaunchKernelGGL(ppo_loss_kernel<cat_ppo_loss>, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    return launched();
+}
+
+extern "C" int cat_ppo_loss_grad_dev(const cat_ppo_loss_dev *a, void *stream)
+{
+    if (const int rc = loss_checked(a, "cat_ppo_loss_grad_dev")) return rc;
+    if (!a->hyper) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_loss_grad_dev: hyper is NULL");
+    hipLaunchKernelGGL(ppo_loss_kernel<cat_ppo_loss_dev>, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
     return launched();
 }
 
@@ -318,11 +405,32 @@ extern "C" int cat_ppo_moments(const cat_ppo_moments_args *a, void *stream)
 
 extern "C" int cat_ppo_adam_step(const cat_ppo_adam *a, void *stream)
 {
-    if (!a || a->G <= 0 || a->G > 65535 || a->P <= 0 || a->chunks <= 0 || a->chunks > CAT_PPO_MAX_CHUNKS)
-        return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_adam_step: bad dimensions");
-    if (!a->ar || !a->col_train || !a->epoch_active || !a->m || !a->v || !a->steps || !a->master || !a->kl_out || !a->norm_partial)
-        return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_adam_step: a required buffer is NULL");
-    hipLaunchKernelGGL(grad_norm_kernel, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
-    hipLaunchKernelGGL(adam_kernel, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    if (const int rc = adam_checked(a, "cat_ppo_adam_step")) return rc;
+    hipLaunchKernelGGL(grad_norm_kernel<cat_ppo_adam>, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(adam_kernel<cat_ppo_adam>, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    return launched();
+}
+
+extern "C" int cat_ppo_adam_step_dev(const cat_ppo_adam_dev *a, void *stream)
+{
+    if (const int rc = adam_checked(a, "cat_ppo_adam_step_dev")) return rc;
+    if (!a->hyper) return fail(CAT_PPO_ERR_BAD_ARG, "cat_ppo_adam_step_dev: hyper is NULL");
+    hipLaunchKernelGGL(grad_norm_kernel<cat_ppo_adam_dev>, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(adam_kernel<cat_ppo_adam_dev>, dim3(a->chunks, a->G), dim3(BLOCK), 0, (hipStream_t)stream, *a);
+    return launched();
+}
+
+extern "C" int cat_ppo_schedule_step(const cat_ppo_schedule *a, void *stream)
+{
+    const char *who = "cat_ppo_schedule_step";
+    if (!a || a->G <= 0 || a->G > CAT_ROLLOUT_MAX_AGENTS) return fail(CAT_PPO_ERR_BAD_ARG, who, "G must be 1..CAT_ROLLOUT_MAX_AGENTS");
+    if (!a->hyper) return fail(CAT_PPO_ERR_BAD_ARG, who, "hyper is NULL");
+    if (!a->sched_active) return fail(CAT_PPO_ERR_BAD_ARG, who, "sched_active is NULL");
+    if (a->mode < 1 || a->mode > (CAT_PPO_SCHED_KL | CAT_PPO_SCHED_ANNEAL)) return fail(CAT_PPO_ERR_BAD_ARG, who, "mode must be 1..3");
+    if (!(a->lr_factor >= 1.0f)) return fail(CAT_PPO_ERR_BAD_ARG, who, "lr_factor must be >= 1");
+    if (!(a->kl_factor >= 1.0f)) return fail(CAT_PPO_ERR_BAD_ARG, who, "kl_factor must be >= 1");
+    if (!(a->lr_min <= a->lr_max)) return fail(CAT_PPO_ERR_BAD_ARG, who, "lr_min must be <= lr_max");
+    if (!(a->progress >= 0.0f && a->progress <= 1.0f)) return fail(CAT_PPO_ERR_BAD_ARG, who, "progress must lie in [0, 1]");
+    hipLaunchKernelGGL(schedule_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a);
     return launched();
 }

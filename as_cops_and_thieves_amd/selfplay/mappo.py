@@ -57,6 +57,45 @@ class RoleConfig:
     kl_threshold: float = 0.015
     random_timesteps: int = 10_000
     learning_starts: int = 15_000
+    # Schedules (build-side options; the reference trains at constant values).  All defaults mean "off": see ``scheduled``.
+    lr_schedule: str = "constant"          # "constant", "linear" (learning_rate -> lr_final over schedule_updates updates) or
+                                           # "kl_adaptive" (skrl's KLAdaptiveLR [SKRL-RECALL], per agent: after every epoch the rate is
+                                           # divided by lr_factor where the epoch's mean minibatch KL is above lr_kl_target * lr_kl_factor,
+                                           # multiplied where it is below lr_kl_target / lr_kl_factor, and kept inside [lr_min, lr_max])
+    lr_final: Optional[float] = None       # end value for "linear"
+    lr_kl_target: float = 0.008            # the next five: KLAdaptiveLR's defaults.  Not ``kl_threshold``, which stays the early-stop gate
+    lr_kl_factor: float = 2.0
+    lr_factor: float = 1.5
+    lr_min: float = 1e-6
+    lr_max: float = 1e-2
+    entropy_final: Optional[float] = None      # linear anneal of entropy_loss_scale to this value
+    ratio_clip_final: Optional[float] = None   # linear anneal of ratio_clip to this value
+    schedule_updates: int = 0              # updates over which the linear anneals run: progress = min(1, finished updates / this)
+
+
+LR_SCHEDULES = ("constant", "linear", "kl_adaptive")
+
+
+def scheduled(cfg: RoleConfig) -> bool:
+    """True when ``cfg`` asks for any schedule: its learner then keeps the three hyper-parameters in device memory (``RoleLearner.hyper``)."""
+    return cfg.lr_schedule != "constant" or cfg.entropy_final is not None or cfg.ratio_clip_final is not None
+
+
+def check_schedule(cfg: RoleConfig) -> None:
+    """ValueError naming the field of a schedule configuration that cannot run."""
+    if cfg.lr_schedule not in LR_SCHEDULES:
+        raise ValueError(f"RoleConfig.lr_schedule must be one of {LR_SCHEDULES}, got {cfg.lr_schedule!r}")
+    if cfg.lr_schedule == "linear" and cfg.lr_final is None:
+        raise ValueError('RoleConfig.lr_final: lr_schedule="linear" needs the end value')
+    linear = cfg.lr_schedule == "linear" or cfg.entropy_final is not None or cfg.ratio_clip_final is not None
+    if linear and (isinstance(cfg.schedule_updates, bool) or not isinstance(cfg.schedule_updates, int) or cfg.schedule_updates <= 0):
+        raise ValueError(f"RoleConfig.schedule_updates must be a positive number of updates for a linear schedule, got {cfg.schedule_updates!r}")
+    if not cfg.lr_factor >= 1.0:            # the KL rule's numbers: what cat_ppo_schedule_step rejects, whatever the mode
+        raise ValueError(f"RoleConfig.lr_factor must be >= 1, got {cfg.lr_factor!r}")
+    if not cfg.lr_kl_factor >= 1.0:
+        raise ValueError(f"RoleConfig.lr_kl_factor must be >= 1, got {cfg.lr_kl_factor!r}")
+    if not cfg.lr_min <= cfg.lr_max:
+        raise ValueError(f"RoleConfig.lr_min must be <= lr_max, got {cfg.lr_min!r} > {cfg.lr_max!r}")
 
 
 CFG_AGENT = RoleConfig()                                                                       # mappo_config.py:41-50
@@ -287,6 +326,47 @@ def moments_scale(state: torch.Tensor) -> torch.Tensor:
     return torch.stack([torch.where(empty, torch.zeros_like(mean), mean).float(), torch.where(empty, torch.ones_like(sigma), sigma).float()], -1)
 
 
+# ---------------------------------------------------------------------------------------------- hyper-parameter schedules
+# ``cat_ppo_schedule_step`` restated from include/cat_ppo.h on fp32 CPU tensors: every line is one rounded fp32 operation on whole arrays,
+# in the header's order, so the block is the kernel's bit for bit.  The learner's CPU path runs it; the GPU path launches the kernel.
+HYPER_STRIDE = _learn_native.PPO_HYPER_STRIDE
+HYPER_LR, HYPER_ENTROPY, HYPER_RATIO_CLIP = _learn_native.HYPER_LR, _learn_native.HYPER_ENTROPY, _learn_native.HYPER_RATIO_CLIP
+HYPER_KL_SUM, HYPER_KL_COUNT = _learn_native.HYPER_KL_SUM, _learn_native.HYPER_KL_COUNT
+SCHED_KL, SCHED_ANNEAL = _learn_native.SCHED_KL, _learn_native.SCHED_ANNEAL
+ANNEAL_LR, ANNEAL_ENTROPY, ANNEAL_RATIO_CLIP = _learn_native.ANNEAL_LR, _learn_native.ANNEAL_ENTROPY, _learn_native.ANNEAL_RATIO_CLIP
+
+
+@torch.no_grad()
+def schedule_step(hyper: torch.Tensor, sched_active: torch.Tensor, mode: int, *, kl_target: float = 0.008, kl_factor: float = 2.0,
+                  lr_factor: float = 1.5, lr_min: float = 1e-6, lr_max: float = 1e-2, anneal_mask: int = 0, progress: float = 0.0,
+                  lr=(0.0, 0.0), entropy=(0.0, 0.0), ratio_clip=(0.0, 0.0)) -> None:
+    """``_learn_native.ppo_schedule_step`` on the CPU: ``hyper`` fp32 [G, 8] in place, ``sched_active`` fp32 [G]; same arguments, same checks."""
+    assert hyper.dtype == torch.float32 and hyper.dim() == 2 and hyper.shape[1] == HYPER_STRIDE and hyper.device.type == "cpu"
+    assert sched_active.dtype == torch.float32 and sched_active.shape == (hyper.shape[0],)
+    f = lambda x: torch.tensor(x, dtype=torch.float32)          # a launch argument: the Python float rounded to fp32
+    if mode not in (SCHED_KL, SCHED_ANNEAL, SCHED_KL | SCHED_ANNEAL):
+        raise ValueError(f"schedule_step: mode must be 1..3, got {mode!r}")
+    if not (f(lr_factor) >= 1 and f(kl_factor) >= 1 and f(lr_min) <= f(lr_max) and 0 <= f(progress) <= 1):
+        raise ValueError("schedule_step: needs lr_factor >= 1, kl_factor >= 1, lr_min <= lr_max and progress in [0, 1]")
+    if mode & SCHED_ANNEAL:
+        for bit, col, (x0, x1) in ((ANNEAL_LR, HYPER_LR, lr), (ANNEAL_ENTROPY, HYPER_ENTROPY, entropy), (ANNEAL_RATIO_CLIP, HYPER_RATIO_CLIP, ratio_clip)):
+            if anneal_mask & bit:
+                d = f(x1) - f(x0)
+                p = d * f(progress)
+                hyper[:, col] = f(x0) + p
+    if mode & SCHED_KL:
+        hi = f(kl_target) * f(kl_factor)
+        lo = f(kl_target) / f(kl_factor)
+        count, old = hyper[:, HYPER_KL_COUNT], hyper[:, HYPER_LR]
+        kl = hyper[:, HYPER_KL_SUM] / torch.where(count > 0, count, torch.ones_like(count))
+        down = torch.maximum(old / f(lr_factor), f(lr_min))
+        up = torch.minimum(old * f(lr_factor), f(lr_max))
+        new = torch.where(kl > hi, down, torch.where(kl < lo, up, old))
+        hyper[:, HYPER_LR] = torch.where((count > 0) & (sched_active != 0), new, old)
+        hyper[:, HYPER_KL_SUM] = 0.0
+        hyper[:, HYPER_KL_COUNT] = 0.0
+
+
 class RoleLearner:
     """G agents that share one ``RoleConfig`` -- the agents of a role, or of both roles when the roles are configured
     alike (the reference's driver: ``CFG_AGENT`` for everyone) -- as stacked policy + value networks over one flat
@@ -357,6 +437,48 @@ class RoleLearner:
                 self._vn_partial = torch.empty(G, _learn_native.ppo_moment_chunks(T * N), 3, dtype=torch.float64, device=device)
                 self._vn_batch = torch.zeros(G, 3, dtype=torch.float64, device=device)
             self._vn_frozen = torch.zeros(G, 1, dtype=torch.bool, device=device)               # agents whose value network is frozen
+        check_schedule(cfg)
+        self.scheduled = scheduled(cfg)
+        if self.scheduled:      # the learning rate, entropy scale and ratio clip of every agent live in device memory (include/cat_ppo.h: the hyper
+            # block); the step kernels read them there, so the captured graphs follow the schedule rule without a recapture
+            if G > _learn_native.SCHED_MAX_AGENTS:
+                raise ValueError(f"a scheduled learner holds at most {_learn_native.SCHED_MAX_AGENTS} agents, not {G}")
+            self.hyper = torch.zeros(G, HYPER_STRIDE, **f32)
+            self.sched_active = torch.ones(G, **f32)           # 1 = the agent's policy is being trained (``set_frozen``)
+            self.updates_done = 0                              # finished ``update`` calls: the linear anneals' clock
+            self.anneal_mask = ((ANNEAL_LR if cfg.lr_schedule == "linear" else 0) | (ANNEAL_ENTROPY if cfg.entropy_final is not None else 0) |
+                                (ANNEAL_RATIO_CLIP if cfg.ratio_clip_final is not None else 0))
+            for g in range(G):
+                self.set_schedule(g, None)
+
+    # ------------------------------------------------------------------ hyper-parameter schedules
+    def set_schedule(self, g: int, entry: Optional[dict]) -> None:
+        """Agent g's row of the hyper block <- a checkpoint's ``"schedule"`` entry (None: the configured start values; the KL sums empty)."""
+        cfg = self.cfg
+        entry = entry or {}
+        row = [0.0] * HYPER_STRIDE
+        row[HYPER_LR] = float(entry.get("lr", cfg.learning_rate))
+        row[HYPER_ENTROPY] = float(entry.get("entropy_scale", cfg.entropy_loss_scale))
+        row[HYPER_RATIO_CLIP] = float(entry.get("ratio_clip", cfg.ratio_clip))
+        self.hyper[g] = torch.tensor(row, dtype=torch.float32)
+        self.updates_done = int(entry.get("updates", 0))       # one clock per learner: its agents' entries agree
+
+    def schedule_entry(self, g: int) -> dict:
+        """Agent g's current learning rate, entropy scale and ratio clip, and the learner's count of finished updates."""
+        h = self.hyper[g].cpu()
+        return {"lr": float(h[HYPER_LR]), "entropy_scale": float(h[HYPER_ENTROPY]), "ratio_clip": float(h[HYPER_RATIO_CLIP]),
+                "updates": self.updates_done}
+
+    def _schedule(self, mode: int, progress: float = 0.0) -> None:
+        """One launch of the schedule rule on ``hyper`` (eager, between replays of the captured step graphs); on the CPU its restatement."""
+        cfg = self.cfg
+        step = _learn_native.ppo_schedule_step if self.device.type == "cuda" else schedule_step
+        final = lambda x, x0: x0 if x is None else x
+        step(self.hyper, self.sched_active, mode, kl_target=cfg.lr_kl_target, kl_factor=cfg.lr_kl_factor, lr_factor=cfg.lr_factor,
+             lr_min=cfg.lr_min, lr_max=cfg.lr_max, anneal_mask=self.anneal_mask, progress=progress,
+             lr=(cfg.learning_rate, final(cfg.lr_final, cfg.learning_rate)),
+             entropy=(cfg.entropy_loss_scale, final(cfg.entropy_final, cfg.entropy_loss_scale)),
+             ratio_clip=(cfg.ratio_clip, final(cfg.ratio_clip_final, cfg.ratio_clip)))
 
     # ------------------------------------------------------------------ freezing (skrl Model.freeze_parameters)
     def set_frozen(self, role: Optional[str] = None, policy: Optional[bool] = None, value: Optional[bool] = None) -> None:
@@ -371,6 +493,8 @@ class RoleLearner:
         self.col_train.copy_(torch.stack(rows))
         if self.value_norm:     # a frozen critic keeps the scale it was trained under (``_moments_step``)
             self._vn_frozen.copy_(torch.tensor([[self.frozen[r][1]] for r in self.agent_roles]))
+        if self.scheduled:      # a frozen policy has KL exactly 0: the KL rule leaves its learning rate alone
+            self.sched_active.copy_(torch.tensor([0.0 if self.frozen[r][0] else 1.0 for r in self.agent_roles]))
 
     def rows(self, role: str) -> List[int]:
         return [g for g, r in enumerate(self.agent_roles) if r == role]
@@ -388,10 +512,17 @@ class RoleLearner:
         logits, _ = self.policy.forward(b["pin"], (st(self.p0[0]), st(self.p0[1])), keep, select=idx)
         values, _ = self.value.forward(b["vin"], (st(self.v0[0]), st(self.v0[1])), keep, select=idx)
         M = float(logits.shape[1] * logits.shape[2])                                     # samples per agent in the minibatch
+        ratio_clip, entropy_scale = cfg.ratio_clip, cfg.entropy_loss_scale
+        if self.scheduled and not self.native:      # per agent, from the hyper block (fp32, as the kernel takes them)
+            ratio_clip, entropy_scale = self.hyper[:, HYPER_RATIO_CLIP].view(-1, 1, 1), self.hyper[:, HYPER_ENTROPY]
         if self.native:   # loss, statistics and d loss / d (logits, values) in one launch (csrc/cat_ppo.hip)
-            sums, d_logits, d_values = _learn_native.ppo_loss_grad(
-                logits, values, sel(b["act"]), sel(b["logp"]), sel(b["adv"]), sel(b["ret"]), cfg.ratio_clip, cfg.value_loss_scale,
-                cfg.entropy_loss_scale)
+            if self.scheduled:      # ... which reads the ratio clip and the entropy scale from the hyper block
+                sums, d_logits, d_values = _learn_native.ppo_loss_grad_dev(
+                    logits, values, sel(b["act"]), sel(b["logp"]), sel(b["adv"]), sel(b["ret"]), self.hyper, cfg.value_loss_scale)
+            else:
+                sums, d_logits, d_values = _learn_native.ppo_loss_grad(
+                    logits, values, sel(b["act"]), sel(b["logp"]), sel(b["adv"]), sel(b["ret"]), cfg.ratio_clip, cfg.value_loss_scale,
+                    cfg.entropy_loss_scale)
             policy_loss, value_loss, kl = -sums[:, 0] / M, cfg.value_loss_scale * sums[:, 1] / M, sums[:, 3] / M
             _GradsOf.apply(logits, values, d_logits, d_values).backward()
         else:
@@ -402,11 +533,11 @@ class RoleLearner:
             with torch.no_grad():
                 kl = _rowsum((ratio - 1) - (logp - old)) / M                            # [G]
             adv = sel(b["adv"])
-            surr = torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - cfg.ratio_clip, 1 + cfg.ratio_clip))
+            surr = torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - ratio_clip, 1 + ratio_clip))
             policy_loss = -_rowsum(surr) / M
             entropy = -_rowsum((logp_all.exp() * logp_all).sum(-1)) / M
             value_loss = cfg.value_loss_scale * _rowsum((values.float().squeeze(-1) - sel(b["ret"])) ** 2) / M
-            (policy_loss - cfg.entropy_loss_scale * entropy + value_loss).sum().backward()   # agents share no parameter
+            (policy_loss - entropy_scale * entropy + value_loss).sum().backward()   # agents share no parameter
         with torch.no_grad():
             self.ar[:, :-1].copy_(self.fp.grad)
             self.ar[:, -1].copy_(kl)
@@ -416,6 +547,11 @@ class RoleLearner:
     def _step_apply(self) -> None:
         """KL gate, joint policy+value gradient-norm clip per agent, masked Adam, refresh of the compute copy."""
         cfg = self.cfg
+        if self.device.type == "cuda" and self.scheduled:   # the learning rate from the hyper block; the KL sums of the epoch go there
+            _learn_native.ppo_adam_step_dev(self.ar, self.col_train, self.epoch_active, self.m, self.v, self.steps, self.fp.master,
+                                            None if self.fp.lp is self.fp.master else self.fp.lp, self.stat[2], self._norm_scratch,
+                                            self.hyper, self.BETA1, self.BETA2, self.EPS, cfg.grad_norm_clip, cfg.kl_threshold)
+            return
         if self.device.type == "cuda":   # the same step in two launches (csrc/cat_ppo.hip)
             _learn_native.ppo_adam_step(self.ar, self.col_train, self.epoch_active, self.m, self.v, self.steps, self.fp.master,
                                         None if self.fp.lp is self.fp.master else self.fp.lp, self.stat[2], self._norm_scratch,
@@ -423,6 +559,12 @@ class RoleLearner:
             return
         kl = self.ar[:, -1]
         self.stat[2].copy_(kl)
+        lr = cfg.learning_rate
+        if self.scheduled:      # cat_ppo_adam_step_dev: an agent that enters the step active adds its KL to the epoch's sum
+            was = self.epoch_active != 0
+            self.hyper[:, HYPER_KL_SUM].add_(torch.where(was, kl, torch.zeros_like(kl)))
+            self.hyper[:, HYPER_KL_COUNT].add_(was.to(torch.float32))
+            lr = self.hyper[:, HYPER_LR].unsqueeze(1)
         if cfg.kl_threshold:
             self.epoch_active.mul_((kl <= cfg.kl_threshold).to(torch.float32))
         g = self.ar[:, :-1] * self.col_train                                           # frozen parameters: no gradient
@@ -435,7 +577,7 @@ class RoleLearner:
         s = self.steps.clamp_min(1.0)
         bc1, bc2 = 1 - self.BETA1 ** s, 1 - self.BETA2 ** s
         denom = (self.v / bc2).sqrt_().add_(self.EPS)
-        self.fp.master.sub_(gate * cfg.learning_rate * (self.m / bc1) / denom)
+        self.fp.master.sub_(gate * lr * (self.m / bc1) / denom)
         self.fp.refresh()
 
     def minibatch_step(self, use_graph: bool) -> None:
@@ -459,10 +601,13 @@ class RoleLearner:
         """Capture the two halves of the step in HIP graphs (``torch.cuda.CUDAGraph``).  Warm-up runs on a side stream
         first (library workspaces, autograd buffers), as whole-network capture requires; the optimiser state the warm-up
         touched is restored, so capturing does not train.  Returns () if the runtime refuses the capture."""
-        keep = [t.clone() for t in (self.fp.master, self.m, self.v, self.steps, self.epoch_active, self.ar, self.stat)]
+        kept = (self.fp.master, self.m, self.v, self.steps, self.epoch_active, self.ar, self.stat)
+        if self.scheduled:      # the warm-up and the capture add to the KL sums of the hyper block
+            kept += (self.hyper,)
+        keep = [t.clone() for t in kept]
 
         def restore():
-            for dst, src in zip((self.fp.master, self.m, self.v, self.steps, self.epoch_active, self.ar, self.stat), keep):
+            for dst, src in zip(kept, keep):
                 dst.copy_(src)
             self.fp.refresh()
         try:
@@ -559,6 +704,12 @@ class RoleLearner:
         """dones/starts [T, N]; last_values [G, N] (bootstrap, already zeroed where the next tick starts an episode; with ``value_norm``
         a normalised critic output like ``buf["val"]``: the zero is then not a zero return, but ``dones`` of the last tick cuts it off)."""
         cfg, b = self.cfg, self.buf
+        kl_rule = self.scheduled and cfg.lr_schedule == "kl_adaptive"
+        if self.scheduled:
+            if self.anneal_mask:    # the linear anneals: once per update, before its epochs
+                self._schedule(SCHED_ANNEAL, min(1.0, self.updates_done / cfg.schedule_updates))
+            if not kl_rule:         # nothing reads the KL sums the step kernel keeps: empty them, so that they stay small
+                self.hyper[:, HYPER_KL_SUM:HYPER_KL_COUNT + 1].zero_()
         if self.value_norm:
             adv = self._scan_normalised(dones, last_values)
         elif self.native:   # the reverse scan over the T ticks as one launch (csrc/cat_ppo.hip) instead of ~7 small ones per tick
@@ -585,6 +736,10 @@ class RoleLearner:
             for k in range(cfg.mini_batches):
                 self.idx.copy_(perm[k * self.B:(k + 1) * self.B])
                 self.minibatch_step(use_graph)
+            if kl_rule:             # the epoch's mean KL moves every agent's learning rate; the sums start over
+                self._schedule(SCHED_KL)
+        if self.scheduled:
+            self.updates_done += 1
 
 
 class MAPPOTrainer:
@@ -934,6 +1089,11 @@ class MAPPOTrainer:
                 sc = rl.vn_scale.cpu()
                 for g, a in enumerate(rl.agents):
                     out[f"value_mean/{a}"], out[f"value_std/{a}"] = float(sc[g, 0]), float(sc[g, 1])
+            if rl.scheduled:            # what the next minibatch step would train with
+                h = rl.hyper.cpu()
+                for g, a in enumerate(rl.agents):
+                    out[f"lr/{a}"], out[f"entropy_scale/{a}"], out[f"ratio_clip/{a}"] = (float(h[g, HYPER_LR]), float(h[g, HYPER_ENTROPY]),
+                                                                                       float(h[g, HYPER_RATIO_CLIP]))
         ep = self._episode_stats()
         if ep is not None:
             e = ep()
@@ -1046,8 +1206,12 @@ class MAPPOTrainer:
             rl, g = self.learner_of(a)
             if rl.role in self._opponents:           # played by an actor (set_opponent): not this trainer's to save
                 continue
-            out[a] = dict(self.agent_models(a), optimizer=adam_state_dict(rl.fp, g, rl.m, rl.v, rl.steps, rl.cfg.learning_rate,
+            sched = rl.schedule_entry(g) if rl.scheduled else None
+            out[a] = dict(self.agent_models(a), optimizer=adam_state_dict(rl.fp, g, rl.m, rl.v, rl.steps,
+                                                                         sched["lr"] if sched else rl.cfg.learning_rate,
                                                                          (rl.BETA1, rl.BETA2), rl.EPS))
+            if sched:                   # the agent's current learning rate, entropy scale and ratio clip, and the anneals' clock
+                out[a]["schedule"] = sched
             if rl.value_norm:           # the running moments the agent's critic was trained under: (n, mean, M2), f64
                 out[a]["vn_state"] = rl.vn_state[g].detach().cpu().clone()
         out[self.META_KEY] = {"format": "cat-mappo-3", "timestep": self.timestep, "num_rays": self.R, "recurrent": bool(self.tcfg.recurrent)}
@@ -1057,13 +1221,15 @@ class MAPPOTrainer:
         """``roles``: restrict to these roles' models (reference ``copy_role_models``, which copies policy and value
         weights only: pass ``optimizer=False`` for that).  Accepts this class's checkpoints, a checkpoint written by the
         reference (skrl layout, no ``__cat__``; preprocessor entries are ignored, the reference configures none) and
-        round-2 files (``{"format": "cat-mappo-2", "models": ..., "optimizers": ...}``).  With ``TrainerConfig.value_norm`` an agent's
+        round-2 files (``{"format": "cat-mappo-2", "models": ..., "optimizers": ...}``).  A scheduled learner (``RoleConfig.lr_schedule`` ...)
+        takes an agent's ``schedule`` entry (none: it starts from the config); a trainer without schedules ignores them with one warning.  With ``TrainerConfig.value_norm`` an agent's
         ``vn_state`` is restored with its models (an agent entry without one starts a fresh scaler); without the option a checkpoint's
         ``vn_state`` entries are ignored with one warning."""
         if sd.get("format") == "cat-mappo-2":
             sd = dict({a: dict(sd["models"][a], **({"optimizer": sd["optimizers"][a]} if a in sd.get("optimizers", {}) else {}))
                        for a in sd["models"]}, **{self.META_KEY: {"timestep": sd.get("timestep", 0)}})
         ignored: List[str] = []
+        unscheduled: List[str] = []
         for a in self.agents:
             if roles is not None and a.split("_")[0] not in roles:
                 continue
@@ -1077,6 +1243,15 @@ class MAPPOTrainer:
                 rl.set_value_moments(g, sd[a].get("vn_state"))
             elif "vn_state" in sd[a]:
                 ignored.append(a)
+            if not optimizer:           # the schedule goes with the optimiser: a copy of the models alone leaves it as it is
+                pass
+            elif rl.scheduled:          # no entry: the schedule starts from the config
+                rl.set_schedule(g, sd[a].get("schedule"))
+            elif "schedule" in sd[a]:
+                unscheduled.append(a)
+        if unscheduled:
+            warnings.warn(f"the checkpoint holds scheduled hyper-parameters (schedule) of {unscheduled}, which a trainer without schedules ignores: "
+                          "it trains them at its configured learning rate, entropy scale and ratio clip")
         if ignored:
             warnings.warn(f"the checkpoint holds running value moments (vn_state) of {ignored}, which a trainer with value_norm=False ignores: "
                           "their value networks were trained on normalised returns")

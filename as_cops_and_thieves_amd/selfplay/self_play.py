@@ -622,7 +622,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   seed: int = 0, device=None, resume: bool = True, log=print, env_factory=None,
                   query_order: str = "index", tracked_eval: bool = False, episode_stats: bool = False,
                   fused_eval: bool = False, league_eval: bool = False, role_training: bool = False,
-                  fused_collect: bool = False, value_norm: bool = False, position_stats: Optional[int] = None) -> Dict[str, object]:
+                  fused_collect: bool = False, value_norm: bool = False, position_stats: Optional[int] = None,
+                  lr_schedule: str = "constant", lr_final: Optional[float] = None, lr_kl_target: Optional[float] = None,
+                  entropy_final: Optional[float] = None, ratio_clip_final: Optional[float] = None) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -654,6 +656,11 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
 
     ``value_norm``: the critics train on returns normalised by running per-agent moments (``TrainerConfig.value_norm``); the joint
     checkpoints then carry each agent's moments (``vn_state``) beside its value network.
+
+    ``lr_schedule`` ("constant", "linear" with ``lr_final``, "kl_adaptive" with ``lr_kl_target``), ``entropy_final``, ``ratio_clip_final``: the
+    schedules of ``RoleConfig``, put into both roles' configurations.  A role configuration that leaves ``schedule_updates`` at 0 gets the
+    number of updates this call will make for it (``planned_updates``), so that a linear anneal ends with the run.  The schedule runs on
+    through the iterations (``reset_optimizers`` renews Adam, not the schedule); the log line of an iteration shows the learning rates.
 
     ``position_stats=CELL``: the evaluation env is built with ``track_positions=CELL`` and after every iteration's evaluation rank 0 writes
     the heatmaps of that evaluation's rows (``render.write_heatmaps``) into ``positions_iter_{i}/`` of the run directory, then clears the
@@ -746,6 +753,12 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     if position_stats is not None:
         eval_env.position_tracker.clear()
     role_cfg = role_cfg or {"cop": CFG_AGENT, "thief": CFG_AGENT}        # self_play_driver.py passes CFG_AGENT
+    asked = {k: v for k, v in (("lr_schedule", lr_schedule), ("lr_final", lr_final), ("lr_kl_target", lr_kl_target),
+                               ("entropy_final", entropy_final), ("ratio_clip_final", ratio_clip_final)) if v not in (None, "constant")}
+    if asked:
+        role_cfg = {r: dataclasses.replace(c, **asked) for r, c in role_cfg.items()}
+        role_cfg = {r: c if c.schedule_updates else dataclasses.replace(c, schedule_updates=planned_updates(iterations, trainer_cfg, c))
+                    for r, c in role_cfg.items()}
     trainer = MAPPOTrainer(env, role_cfg, trainer_cfg, seed=seed, **({"split_roles": True} if role_training else {}))
     if role_training:  # per role a bank of archived opponents over the training env; one bank over the evaluation env for the booking
         evaluator = None
@@ -822,6 +835,7 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                         archive.add_policy_to_archive(str(ck), arch[role], it, role)
                 log(f"[self-play] iteration {it}: saved {ck.name}; evaluated {len(ev[cop])} thief and {len(ev[thief])} cop opponents"
                     + (f"; {world} ranks x {n_local} envs" if multi else "")
+                    + ("; lr " + " ".join(f"{a}={stats[k]:.3g}" for a in trainer.agents for k in (f"lr/{a}",) if k in stats) if asked else "")
                     + (f"; training episodes{' of rank 0' if multi else ''} {stats['episodes']}, cop win rate {stats['cop_win_rate']:.3f}, mean length "
                        f"{stats['mean_episode_length']:.1f}" if episode_stats else ""))
                 if episode_stats:
@@ -837,6 +851,14 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
             raise chief_error
         history.append({"iteration": it, "evaluations": ev, "stats": stats})
     return finish()
+
+
+def planned_updates(iterations: int, trainer_cfg: TrainerConfig, cfg: RoleConfig) -> int:
+    """The updates ``iterations`` calls of ``MAPPOTrainer.train(trainer_cfg.timesteps)`` make for a role configured by ``cfg``: one after
+    every rollout of ``horizon`` ticks that ends at or beyond the role's ``learning_starts`` (at least 1)."""
+    rollouts = -(-trainer_cfg.timesteps // trainer_cfg.horizon)
+    first = max(1, -(-cfg.learning_starts // trainer_cfg.horizon))
+    return max(1, iterations * max(0, rollouts - first + 1))
 
 
 def launch_ranks(n: int, argv) -> int:
@@ -927,6 +949,13 @@ def main() -> None:
                     "on a grid of CELL x CELL pixels, written to positions_iter_N/ in --out")
     ap.add_argument("--fused-collect", action="store_true", help="collect the training rollouts through the one-launch fused act kernel "
                     "(TrainerConfig.fused_collect: a GPU, bf16, the recurrent pair, 64 or 90 rays)")
+    ap.add_argument("--lr-schedule", choices=("constant", "linear", "kl_adaptive"), default="constant", help="learning-rate schedule of both roles "
+                    "(RoleConfig.lr_schedule): linear to --lr-final over the run's updates, or KL-adaptive per agent (skrl's KLAdaptiveLR rule); "
+                    "constant in the reference")
+    ap.add_argument("--lr-final", type=float, default=None, help="end value of --lr-schedule linear")
+    ap.add_argument("--lr-kl-target", type=float, default=None, help="KL target of --lr-schedule kl_adaptive (RoleConfig default: 0.008)")
+    ap.add_argument("--entropy-final", type=float, default=None, help="anneal the entropy scale linearly to this value over the run's updates")
+    ap.add_argument("--clip-final", type=float, default=None, help="anneal the ratio clip linearly to this value over the run's updates")
     ap.add_argument("--value-norm", action="store_true", help="train the critics on returns normalised by running per-agent moments "
                     "(TrainerConfig.value_norm; off in the reference)")
     args = ap.parse_args()
@@ -958,7 +987,10 @@ def main() -> None:
                         query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval,
                         league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}),
                         **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}),
-                        **({"position_stats": args.position_stats} if args.position_stats is not None else {}))
+                        **({"position_stats": args.position_stats} if args.position_stats is not None else {}),
+                        **{k: v for k, v in (("lr_schedule", args.lr_schedule), ("lr_final", args.lr_final), ("lr_kl_target", args.lr_kl_target),
+                                             ("entropy_final", args.entropy_final), ("ratio_clip_final", args.clip_final))
+                           if v not in (None, "constant")})
     if backend:
         import torch.distributed as dist
         print(f"[self-play] rank {res['rank']}/{res['world']}: {res['envs_local']} envs from global id {res['env_id_offset']}, all-reduce over "

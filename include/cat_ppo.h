@@ -134,6 +134,90 @@ const char *cat_ppo_last_error(void);
 int cat_ppo_loss_grad(const cat_ppo_loss *a, void *stream);
 int cat_ppo_adam_step(const cat_ppo_adam *a, void *stream);
 
+/* ---- Hyper-parameters in device memory (entries added to version 2; nothing above changes).
+ * The two entries above take the learning rate, the entropy scale and the ratio clip BY VALUE: a captured graph bakes them in.  The
+ * _dev entries below read them from a per-agent block in device memory instead, so a replay sees what the block holds at that time:
+ *   float hyper[G][CAT_PPO_HYPER_STRIDE]
+ * Columns 5..7 are reserved: the caller writes 0, no kernel touches them. */
+#define CAT_PPO_HYPER_STRIDE 8
+enum {
+    CAT_PPO_HYPER_LR = 0,               /* learning rate */
+    CAT_PPO_HYPER_ENTROPY = 1,          /* entropy scale */
+    CAT_PPO_HYPER_RATIO_CLIP = 2,       /* ratio clip */
+    CAT_PPO_HYPER_KL_SUM = 3,           /* sum of the minibatch KLs of the current epoch */
+    CAT_PPO_HYPER_KL_COUNT = 4          /* number of minibatches in that sum */
+};
+
+/* cat_ppo_loss with ``hyper``: agent g takes ratio_clip = hyper[g][RATIO_CLIP] and entropy_scale = hyper[g][ENTROPY]; the two by-value
+ * fields are ignored, value_scale stays by value.  One kernel template with cat_ppo_loss_grad: with the block holding the by-value
+ * numbers the result is bit-equal to it. */
+typedef struct cat_ppo_loss_dev {
+    int32_t G, M, chunks, pad;
+    const void *logits;
+    const void *values;
+    const int64_t *actions;
+    const float *old_logp, *adv, *ret;
+    float ratio_clip, value_scale, entropy_scale, pad2;
+    void *d_logits;
+    void *d_values;
+    float *partial;
+    const float *hyper;         /* [G][CAT_PPO_HYPER_STRIDE]; device memory, not NULL */
+} cat_ppo_loss_dev;
+int cat_ppo_loss_grad_dev(const cat_ppo_loss_dev *a, void *stream);
+
+/* cat_ppo_adam with ``hyper``: agent g's learning rate is hyper[g][LR]; the ``lr`` field is ignored.  The same two kernel templates as
+ * cat_ppo_adam_step, bit-equal to it when hyper[g][LR] = lr.  In addition the one thread that rewrites epoch_active[g] reads
+ * was = epoch_active[g] before that store and, when was != 0, does (plain fp32 adds)
+ *   hyper[g][KL_SUM] += kl_g;   hyper[g][KL_COUNT] += 1
+ * so the minibatch that trips the KL early stop still counts and the gated ones after it do not (skrl appends the KL, then breaks). */
+typedef struct cat_ppo_adam_dev {
+    int32_t G, P, chunks, pad;
+    const float *ar;
+    const float *col_train;
+    float *epoch_active;
+    float *m, *v, *steps;
+    float *master;
+    void *lp;
+    float *kl_out;
+    float *norm_partial;
+    float lr, beta1, beta2, eps, grad_norm_clip, kl_threshold;
+    float *hyper;               /* [G][CAT_PPO_HYPER_STRIDE]; device memory, not NULL */
+} cat_ppo_adam_dev;
+int cat_ppo_adam_step_dev(const cat_ppo_adam_dev *a, void *stream);
+
+/* The schedule rule on the block: one workgroup, thread g = agent g (G <= CAT_ROLLOUT_MAX_AGENTS = 8), no atomics, capturable.  Every
+ * operation below is ONE rounded fp32 operation (no contraction of a product into a sum; the divides are the correctly rounded ones).
+ * ``mode`` is a set of the two bits; with both the anneal runs first.
+ *
+ * CAT_PPO_SCHED_ANNEAL (start of an update), for every agent and each field chosen by ``anneal_mask``
+ * (CAT_PPO_ANNEAL_LR: lr0, lr1 -> LR; CAT_PPO_ANNEAL_ENTROPY: ent0, ent1 -> ENTROPY; CAT_PPO_ANNEAL_RATIO_CLIP: clip0, clip1 -> RATIO_CLIP):
+ *   d = x1 - x0;  p = d * progress;  x = x0 + p                    (0 <= progress <= 1)
+ *
+ * CAT_PPO_SCHED_KL (end of an epoch; skrl's KLAdaptiveLR [SKRL-RECALL], per agent):
+ *   hi = kl_target * kl_factor;  lo = kl_target / kl_factor
+ *   if (hyper[g][KL_COUNT] > 0 && sched_active[g] != 0) {
+ *       kl = hyper[g][KL_SUM] / hyper[g][KL_COUNT];  lr = hyper[g][LR]
+ *       if      (kl > hi) lr = fmaxf(lr / lr_factor, lr_min)
+ *       else if (kl < lo) lr = fminf(lr * lr_factor, lr_max)
+ *       hyper[g][LR] = lr
+ *   }
+ *   hyper[g][KL_SUM] = hyper[g][KL_COUNT] = 0                      (always)
+ * sched_active[g] = 1 iff agent g's policy is being trained: a frozen policy has KL exactly 0, and without the gate its learning rate
+ * would climb to lr_max under the critic that still trains.
+ * CAT_PPO_ERR_BAD_ARG, whatever the mode: NULL hyper or sched_active, G outside 1..8, mode outside 1..3, progress outside [0, 1],
+ * lr_factor < 1, kl_factor < 1, lr_min > lr_max (a NaN fails each of these too). */
+enum { CAT_PPO_SCHED_KL = 1, CAT_PPO_SCHED_ANNEAL = 2 };
+enum { CAT_PPO_ANNEAL_LR = 1, CAT_PPO_ANNEAL_ENTROPY = 2, CAT_PPO_ANNEAL_RATIO_CLIP = 4 };
+typedef struct cat_ppo_schedule {
+    int32_t G, mode, anneal_mask, pad;
+    float *hyper;                       /* [G][CAT_PPO_HYPER_STRIDE] */
+    const float *sched_active;          /* [G] */
+    float kl_target, kl_factor, lr_factor, lr_min, lr_max;
+    float progress;
+    float lr0, lr1, ent0, ent1, clip0, clip1;
+} cat_ppo_schedule;
+int cat_ppo_schedule_step(const cat_ppo_schedule *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
