@@ -5,9 +5,16 @@
  * checker for the HIP library (libcat_sim.so) and as bench.py's "cpu_baseline" leg.  Nothing
  * in the product package may include, link or call this.
  *
- * PARITY UNPINNED: the arithmetic of this path lives in Pymunk/Chipmunk2D, a third-party
- * dependency that is NOT under /root/reference (requirements.txt:4, unpinned) and is not
- * installable here.  The Chipmunk side is restated from its published algorithm
+ * PARITY WITH PYMUNK: the arithmetic of this path lives in Pymunk/Chipmunk2D, a third-party
+ * dependency that is NOT under /root/reference (requirements.txt:4, no version) and is not
+ * installable here, so no test runs it.  PINNED WITHOUT IT: the sensor's geometry (the first
+ * contact of a ray's swept disc with the rounded hulls and the agents' discs, the reported point
+ * and its float16 distance), the capture predicate and the spawn rule, against an independent
+ * float64 ground truth written from the geometry (tests/ray_truth.py, tests/test_ray_truth_host.py;
+ * the HIP kernels against the same truth in tests/test_gpu_ray_truth.py).  STILL ONLY RESTATED:
+ * Chipmunk's conventions -- the thin-segment bounding-box gate, the segment end as the point of a
+ * hit at alpha 0, the visiting order on rays whose result depends on it -- and Space.step, which
+ * that truth does not cover.  The Chipmunk side is restated from its published algorithm
  * (marked [CHIPMUNK-RECALL]); the reference's own Python side
  * (src/environments/base_env.py, src/agents/{entity,cop,thief}.py, src/environments/observation_spaces.py)
  * is restated line by line with file:line citations in cat_oracle.c.  What IS pinned: the

@@ -1,7 +1,8 @@
 """ctypes wrapper around oracle/_build/libcat_oracle.so — TEST INFRASTRUCTURE ONLY.
 
-PARITY UNPINNED (see cat_oracle.h): this checks the HIP library against a CPU restatement of
-the reference + Chipmunk2D's published algorithm, not against a running Pymunk.
+Parity with Pymunk (see cat_oracle.h): this checks the HIP library against a CPU restatement of
+the reference + Chipmunk2D's published algorithm, not against a running Pymunk; its sensor geometry,
+capture predicate and spawn rule are pinned to a geometric ground truth (tests/ray_truth.py).
 """
 from __future__ import annotations
 

@@ -5,42 +5,9 @@ import numpy as np
 import pytest
 
 import tests.test_oracle_known_answers as ka
-from tests.util import to_np
+from tests.gpu_sim import GpuSim  # noqa: F401  (the adapter lives in tests/gpu_sim.py; importing it from here keeps working)
 
 pytestmark = pytest.mark.gpu
-
-
-class GpuSim:
-    """The OracleSim surface the cases use, on top of CatSim (ctypes -> libcat_sim.so)."""
-
-    def __init__(self, cfg, cmaps):
-        import torch
-        from as_cops_and_thieves_amd.sim import CatSim
-        self.torch, self.cfg = torch, cfg
-        self.sim = CatSim(cfg, cmaps, device="cuda:0", debug_hit_shape=True)
-
-    def _out(self):
-        self.torch.cuda.synchronize()
-        return to_np(self.sim.out)
-
-    def reset(self, mask=None, positions=None):
-        t = self.torch
-        self.sim.reset(mask=None if mask is None else t.as_tensor(np.ascontiguousarray(mask, np.uint8)),
-                       positions=None if positions is None else t.as_tensor(np.ascontiguousarray(positions, np.float64)))
-        return self._out()
-
-    def step(self, actions):
-        self.sim.step(self.torch.as_tensor(np.ascontiguousarray(actions, np.int32)))
-        return self._out()
-
-    def random_actions(self, tick):
-        return self.sim.random_actions(tick).cpu().numpy()
-
-    def get_state(self):
-        return to_np(self.sim.get_state())
-
-    def set_state(self, **arrays):
-        self.sim.set_state(**arrays)
 
 
 @pytest.fixture(autouse=True)
