@@ -38,7 +38,7 @@ MODULES = {
                                                          C.c_int32, C.c_void_p]),
                       "cat_dense_wgrad_splits": (C.c_int, [C.c_int32] * 4), "cat_dense_wgrad": _ENTRY, "cat_dense_forward": _ENTRY,
                       "cat_dense_dgrad": _ENTRY, "cat_dense_sum_chunks2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])}),
-    "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY}),
+    "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY, "cat_rollout_scripted": _ENTRY}),
     "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]), "cat_render_positions_update": _ENTRY,
                         "cat_render_positions_ends_update": _ENTRY}),
     "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
@@ -995,6 +995,66 @@ def positions_ends_update(final_positions, terminated, truncated, group, quota, 
 def positions_ends_launch(a: PositionsEndsArgs) -> None:
     """One launch of ``cat_render_positions_ends_update`` with an argument block ``positions_ends_update`` has checked."""
     _check(lib().cat_render_positions_ends_update(C.byref(a), _stream()), "cat_render_positions_ends_update")
+
+
+# ---------------------------------------------------------------------------------------------- scripted opponents
+SCRIPT_CHASE, SCRIPT_EVADE = 0, 1   # CAT_ROLLOUT_CHASE / CAT_ROLLOUT_EVADE; -1: not scripted in that segment
+SCRIPTED_MAX_SEGMENTS = 32          # CAT_ROLLOUT_MAX_SEGMENTS (= ACT_MAX_SEGMENTS)
+SCRIPTED_MIN_RAYS, SCRIPTED_MAX_RAYS = 8, 1024
+
+
+class ScriptedArgs(C.Structure):
+    """include/cat_rollout.h cat_rollout_scripted_args."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("R", C.c_int32), ("G", C.c_int32), ("agent", C.c_int32 * 8), ("target", C.c_int32 * 8),
+                ("memory_ticks", C.c_int32), ("clear_min", C.c_float), ("turn_prob", C.c_float), ("S", C.c_int32),
+                ("seg_start", C.c_int32 * (SCRIPTED_MAX_SEGMENTS + 1)), ("seg_script", (C.c_int32 * SCRIPTED_MAX_SEGMENTS) * 8),
+                ("obs_distance", C.c_void_p), ("obs_type", C.c_void_p), ("uniform", C.c_void_p), ("keep", C.c_void_p),
+                ("state", C.c_void_p), ("actions", C.c_void_p)]
+
+
+class ScriptedTable:
+    """A checked segment table of ``cat_rollout_scripted_args`` in the C struct's own arrays (``scripted_table`` makes it)."""
+
+    def __init__(self, S: int, start, rows):
+        self.S, self.start, self.rows = S, start, rows
+        self.seg_start = (C.c_int32 * (SCRIPTED_MAX_SEGMENTS + 1))(*start)
+        self.seg_script = ((C.c_int32 * SCRIPTED_MAX_SEGMENTS) * 8)(*[(C.c_int32 * SCRIPTED_MAX_SEGMENTS)(*row) for row in rows])
+
+
+def scripted_table(N: int, G: int, bounds, rows) -> ScriptedTable:
+    """The segment table of ``cat_rollout_scripted_args`` checked by the C entry's rules: ``bounds`` S + 1 row bounds (``_check_bounds``),
+    ``rows`` [G][S] scripts in {-1, SCRIPT_CHASE, SCRIPT_EVADE}.  Raises ValueError."""
+    start = [int(v) for v in bounds]
+    _check_bounds(N, start, SCRIPTED_MAX_SEGMENTS)
+    S = len(start) - 1
+    table = [[int(v) for v in row] for row in rows]
+    if not 1 <= G <= 8 or len(table) != G or any(len(row) != S for row in table):
+        raise ValueError(f"the scripts must be [{G}][{S}] with 1 <= G <= 8")
+    if any(v not in (-1, SCRIPT_CHASE, SCRIPT_EVADE) for row in table for v in row):
+        raise ValueError("a script outside {-1, 0, 1}")
+    return ScriptedTable(S, start, table)
+
+
+def rollout_scripted(raw, agent_indices, targets, table, uniform, keep, state, actions, memory_ticks: int = 30, clear_min: float = 12.0,
+                     turn_prob: float = 0.02) -> None:
+    """One tick of the scripted opponents in one launch (include/cat_rollout.h, ``cat_rollout_scripted``).  raw = the env core's output
+    buffers (obs_distance f16 / obs_type u8 [N, A, R]); ``targets[g]``: the type code policy g looks for; ``table``: a ``ScriptedTable``
+    for these N and G; uniform fp32 [G, N]; keep fp32 [N] or None; state int32 [G, N, 4] updated in place; actions int32 [N, A]: column
+    ``agent_indices[g]`` receives policy g's action where its script is not -1."""
+    import torch
+    od, ot = raw["obs_distance"], raw["obs_type"]
+    N, A, R = od.shape
+    G = len(agent_indices)
+    assert od.dtype == torch.float16 and ot.dtype == torch.uint8 and od.is_contiguous() and ot.is_contiguous() and ot.shape == od.shape
+    assert isinstance(table, ScriptedTable) and table.start[-1] == N and len(table.rows) == G == len(targets)
+    assert uniform.dtype == torch.float32 and uniform.shape == (G, N) and uniform.is_contiguous()
+    assert keep is None or (keep.dtype == torch.float32 and keep.numel() == N and keep.is_contiguous())
+    assert state.dtype == torch.int32 and state.shape == (G, N, 4) and state.is_contiguous()
+    assert actions.dtype == torch.int32 and actions.shape == (N, A) and actions.is_contiguous()
+    a = ScriptedArgs(N, A, R, G, (C.c_int32 * 8)(*agent_indices), (C.c_int32 * 8)(*targets), int(memory_ticks), float(clear_min), float(turn_prob),
+                     table.S, table.seg_start, table.seg_script, od.data_ptr(), ot.data_ptr(), uniform.data_ptr(), _ptr(keep), state.data_ptr(),
+                     actions.data_ptr())
+    _check(lib().cat_rollout_scripted(C.byref(a), _stream()), "cat_rollout_scripted")
 
 
 # ---------------------------------------------------------------------------------------------- the fused act tick

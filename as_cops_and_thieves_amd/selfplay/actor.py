@@ -25,6 +25,7 @@ import torch
 
 from .. import _learn_native, packing
 from .mappo import MAPPOTrainer, _sample
+from .scripted import SCRIPTS, ScriptedParams, scripted_step, target_of
 from .stacked import HIDDEN, StackedNet, _module_for, _net_shapes, load_agent_state_dict
 
 META_KEY = MAPPOTrainer.META_KEY
@@ -246,6 +247,11 @@ class LeagueActor(PolicyActor):
         actor.set_matchups([(0, 8, {"cop_0": 0, "cop_1": 0, "thief_0": 2}), (8, 16, {"cop_0": 1, "cop_1": 1, "thief_0": "random"})])
         actions = actor.act(env, starts)
 
+    An agent may also follow a script of ``selfplay.scripted`` in a segment (``"chase"`` / ``"evade"``): fused, the league kernel is told
+    "random" for it and a second launch, ``cat_rollout_scripted`` with the same uniform numbers and segment bounds, writes its action
+    column there; unfused, it draws its own ``torch.rand(stop - start)`` after the segment's other draws.  Match-ups without a scripted
+    name run exactly the single launch / the generator sequence described below.
+
     fused: per tick one ``torch.rand(G, N)`` -- the draw a ``PolicyActor`` makes -- and ONE ``cat_act_league_step`` (include/cat_act.h).
     unfused: per segment the ``StackedNet`` chain over the G parameter rows the segment names, on that segment's rows of the inputs and of
     the state, then ``first_max_index`` / ``mappo._sample``; "random" draws ``torch.randint(0, 4, ...)`` and leaves its state rows alone."""
@@ -257,6 +263,10 @@ class LeagueActor(PolicyActor):
         self.table = None                              # _learn_native.LeagueTable of the current match-ups
         self._bank_params = None
         self._nets = {}                                # unfused: (set index per agent) -> StackedNet over a copy of those bank rows
+        self.script_params = ScriptedParams()
+        self.script_table = None                       # _learn_native.ScriptedTable while a segment names a script, else None
+        self.script_state = None                       # int32 [G, N, 4] (scripted.py), allocated with the first scripted match-up
+        self._targets = [target_of(a) for a in self.agents]
 
     @classmethod
     def from_env(cls, env, sets: int, fused: Union[str, bool] = "auto", compute_bf16: bool = True, normalize_inputs: bool = False,
@@ -309,13 +319,15 @@ class LeagueActor(PolicyActor):
         self._nets.clear()
 
     def set_matchups(self, segments) -> None:
-        """``segments``: [(start, stop, {agent: set index | "random"}), ...] -- contiguous row ranges that cover 0 .. N in order, at most
-        ``_learn_native.ACT_MAX_SEGMENTS`` of them, every agent named in each.  The rules of ``cat_act_league_step``; ValueError otherwise."""
+        """``segments``: [(start, stop, {agent: set index | "random" | "chase" | "evade"}), ...] -- contiguous row ranges that cover 0 .. N
+        in order, at most ``_learn_native.ACT_MAX_SEGMENTS`` of them, every agent named in each.  The rules of ``cat_act_league_step``;
+        ValueError otherwise."""
         segments = list(segments)
         if not segments:
             raise ValueError("no segments")
         bounds = [segments[0][0]]
         rows = [[] for _ in self.agents]
+        scripts = [[] for _ in self.agents]
         for lo, hi, who in segments:
             if lo != bounds[-1]:
                 raise ValueError(f"segment ({lo}, {hi}) does not begin where the one before it ends ({bounds[-1]})")
@@ -324,10 +336,43 @@ class LeagueActor(PolicyActor):
                 raise ValueError(f"segment ({lo}, {hi}) must name exactly the agents {self.agents}: {sorted(who)}")
             for g, a in enumerate(self.agents):
                 v = who[a]
-                if not (v == "random" or (isinstance(v, int) and not isinstance(v, bool) and v >= 0)):
-                    raise ValueError(f"segment ({lo}, {hi}), {a}: {v!r} is neither a set index nor \"random\"")
-                rows[g].append(-1 if v == "random" else v)
-        self.table = _learn_native.league_table(self.N, len(self.agents), self.sets, bounds, rows)
+                scripted = isinstance(v, str) and v in SCRIPTS
+                if not (v == "random" or scripted or (isinstance(v, int) and not isinstance(v, bool) and v >= 0)):
+                    raise ValueError(f"segment ({lo}, {hi}), {a}: {v!r} is neither a set index nor \"random\" nor one of {sorted(SCRIPTS)}")
+                rows[g].append(-1 if v == "random" or scripted else v)
+                scripts[g].append(SCRIPTS[v] if scripted else -1)
+        table = _learn_native.league_table(self.N, len(self.agents), self.sets, bounds, rows)
+        if any(v >= 0 for row in scripts for v in row):
+            script_table = _learn_native.scripted_table(self.N, len(self.agents), bounds, scripts)
+            if self.script_state is None:
+                self.script_state = torch.zeros(len(self.agents), self.N, 4, dtype=torch.int32, device=self.device)
+        else:
+            script_table = None
+        self.table, self.script_table = table, script_table
+
+    @torch.no_grad()
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        super().reset(mask)
+        if self.script_state is not None:
+            if mask is None:
+                self.script_state.zero_()
+            else:
+                self.script_state.masked_fill_(mask.view(1, -1, 1), 0)
+
+    def get_state(self, out=None):
+        """``PolicyActor.get_state``, with the scripted agents' rows under ``"scripted"`` while there are any."""
+        out = super().get_state(out)
+        if self.script_state is not None:
+            if "scripted" in out:
+                out["scripted"].copy_(self.script_state)
+            else:
+                out["scripted"] = self.script_state.clone()
+        return out
+
+    def set_state(self, state) -> None:
+        super().set_state(state)
+        if self.script_state is not None and "scripted" in state:
+            self.script_state.copy_(state["scripted"])
 
     @property
     def segments(self) -> List[Tuple[int, int]]:
@@ -376,6 +421,10 @@ class LeagueActor(PolicyActor):
             u = torch.rand(g.G, N, device=self.device)
             _learn_native.act_league_step(raw, g.indices, self._bank_params, self.sets, self.table, None, h[0], c[0], keep, u, actions,
                                           self._scales[0], self._scales[1], greedy, logits_out, logp_out, self.row_tile)
+            if self.script_table is not None:          # the scripted agents' columns in their segments, over the league kernel's "random"
+                sp = self.script_params
+                _learn_native.rollout_scripted(raw, g.indices, self._targets, self.script_table, u, keep, self.script_state, actions,
+                                               sp.memory_ticks, sp.clear_min, sp.turn_prob)
             return actions
         if obs is None:
             obs = env.observations() if hasattr(env, "observations") else env._obs()
@@ -391,9 +440,18 @@ class LeagueActor(PolicyActor):
             else:
                 act = _sample(torch.log_softmax(logits[:, 0].float(), dim=-1))
             net = [i for i, k in enumerate(sets) if k >= 0]
-            if len(net) < g.G:
-                rows = torch.tensor([k < 0 for k in sets], device=self.device).view(g.G, 1)
+            scripted = [] if self.script_table is None else [i for i, row in enumerate(self.script_table.rows) if row[s] >= 0]
+            if len(net) + len(scripted) < g.G:
+                rows = torch.tensor([k < 0 and i not in scripted for i, k in enumerate(sets)], device=self.device).view(g.G, 1)
                 act = torch.where(rows, torch.randint(0, 4, (g.G, hi - lo), device=self.device), act)
+            for i in scripted:                         # after the segment's other draws: one torch.rand(hi - lo) per scripted agent
+                a = g.agents[i]
+                st = self.script_state[i, lo:hi]
+                a_s, new = scripted_step(obs[a]["distance"][lo:hi], obs[a]["object_type"][lo:hi], torch.rand(hi - lo, device=self.device), st,
+                                         None if starts is None else ~starts[lo:hi], self.script_table.rows[i][s], self._targets[i],
+                                         self.script_params)
+                st.copy_(new)
+                act[i] = a_s.to(act.dtype)
             if logits_out is not None:                 # [G, N, 4]: the rows of the agents that evaluated a network, as the kernel
                 logits_out[net, lo:hi] = logits[net, 0].to(logits_out.dtype)
             if hn.shape[0]:                            # the recurrent pair: the rows of the agents that evaluated a network move

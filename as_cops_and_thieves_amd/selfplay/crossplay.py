@@ -6,8 +6,10 @@
 A cell (cop file i, thief file j) is one segment of ``--episodes`` env slots of a ``LeagueActor`` (``actor.py``): the cops of file i and
 the thieves of file j play the first episode of each slot (``self_play.evaluate_league``).  At most ``ACT_MAX_SEGMENTS`` = 32 cells share a
 pass, so a K x K table takes ceil(K^2 / 32) passes instead of K^2.  ``--random-column`` adds a last column: thieves acting uniformly at
-random, a fixed yardstick.  ``payoff.json`` holds the file lists and the matrices ``cop_win_rate``, ``cop_wins``, ``thief_wins``,
-``timeouts`` (the three counts add up to the episodes of a cell) and ``mean_length`` (ticks of the counted episodes), rows = cop files.
+random, a fixed yardstick; ``--scripted`` adds the scripted opponents of ``scripted.py``: a last row ``chase`` (cops that head for the
+thief they see) and a last column ``evade`` (thieves that run from the cops they see).  ``payoff.json`` holds the file lists and the
+matrices ``cop_win_rate``, ``cop_wins``, ``thief_wins``, ``timeouts`` (the three counts add up to the episodes of a cell) and
+``mean_length`` (ticks of the counted episodes), rows = cop files.
 ``--heatmaps DIR [--cell C]``: position statistics of the counted episodes, one group per cell of the table -- occupancy, exposure, hidden
 and spawn maps per agent under ``DIR/{cop file}__{thief file}/`` and the raw counts in ``DIR/positions.npz`` (``positions.py``).
 """
@@ -26,6 +28,7 @@ from .actor import LeagueActor
 from .self_play import evaluate_league
 
 RANDOM = "random"
+CHASE, EVADE = "chase", "evade"                 # scripted.SCRIPTS: the row of scripted cops, the column of scripted thieves
 
 
 def policy_files(directory, role: str) -> List[Path]:
@@ -38,9 +41,10 @@ def policy_files(directory, role: str) -> List[Path]:
 def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool = False, greedy: bool = False, num_rays: int = 64,
               n_cops: Optional[int] = None, n_thieves: Optional[int] = None, max_step_count: int = 2000, seed: int = 0, device=None,
               fused: Union[str, bool] = "kernel", normalize_inputs: bool = False, env_factory=None, log=None,
-              frame_skip: int = 1, heatmaps=None, cell: int = 8) -> Dict[str, object]:
+              frame_skip: int = 1, heatmaps=None, cell: int = 8, scripted: bool = False) -> Dict[str, object]:
     """``cops`` / ``thieves``: an archive directory or a list of checkpoint files.  ``episodes`` slots per cell; sampled actions, or the
-    largest logit with ``greedy``.  ``env_factory(num_envs, seed)``: build the env some other way (``map_name`` etc. are then unused).
+    largest logit with ``greedy``.  ``scripted``: a last row of "chase" cops and a last column of "evade" thieves (after "random").
+    ``env_factory(num_envs, seed)``: build the env some other way (``map_name`` etc. are then unused).
     ``frame_skip``: env ticks per decision (``evaluate_league``); ``mean_length`` stays in env ticks.
     ``heatmaps``: a directory -- the env is built with ``track_positions=cell`` and one group per cell of a pass, and every pass writes its
     cells' heatmaps there (``render.write_heatmaps``; ``positions.npz`` holds the first pass, ``positions_pass{p}.npz`` the later ones).  An
@@ -52,8 +56,9 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
         raise ValueError(f"cross-play needs at least one file per role: {len(cop_files)} cop and {len(thief_files)} thief files")
     if episodes < 1:
         raise ValueError("episodes must be at least 1")
-    columns = list(range(len(thief_files))) + ([RANDOM] if random_column else [])
-    cells = [(i, j) for i in range(len(cop_files)) for j in columns]
+    rows = list(range(len(cop_files))) + ([CHASE] if scripted else [])
+    columns = list(range(len(thief_files))) + ([RANDOM] if random_column else []) + ([EVADE] if scripted else [])
+    cells = [(i, j) for i in rows for j in columns]
     per_pass = min(_learn_native.ACT_MAX_SEGMENTS, len(cells))
     N = per_pass * episodes
     if env_factory is None:
@@ -74,7 +79,7 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
         def act(self, env_, starts=None, obs=None):
             return actor.act(env_, starts, greedy=True, obs=obs)
     player = _Greedy() if greedy else actor
-    shape = (len(cop_files), len(columns))
+    shape = (len(rows), len(columns))
     mats = {k: [[0] * shape[1] for _ in range(shape[0])] for k in ("cop_wins", "thief_wins", "timeouts")}
     mean_length = [[0.0] * shape[1] for _ in range(shape[0])]
     loaded: Dict[Path, dict] = {}
@@ -91,7 +96,8 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
                 actor.load_set(sets[(path, agent)], loaded[path], agent)
             return sets[(path, agent)]
         for s, (i, j) in enumerate(chunk):
-            who = {a: (set_of(cop_files[i], a) if a.startswith("cop") else RANDOM if j == RANDOM else set_of(thief_files[j], a)) for a in agents}
+            who = {a: ((i if i == CHASE else set_of(cop_files[i], a)) if a.startswith("cop") else j if j in (RANDOM, EVADE) else set_of(thief_files[j], a))
+                   for a in agents}
             segments.append((s * episodes, (s + 1) * episodes, who))
             quota.append(episodes)
         if len(chunk) < per_pass:                       # the last pass: the remaining slots fill the env and count nothing
@@ -103,20 +109,21 @@ def crossplay(cops, thieves, map_name: str, episodes: int, random_column: bool =
         if heatmaps is not None:
             from ..render import write_heatmaps
             tracker = env.position_tracker
-            names = [f"{cop_files[i].stem}__{RANDOM if j == RANDOM else thief_files[j].stem}" for i, j in chunk]
+            names = [f"{i if i == CHASE else cop_files[i].stem}__{j if j in (RANDOM, EVADE) else thief_files[j].stem}" for i, j in chunk]
             write_heatmaps(heatmaps, tracker, env.maps, group_names=names + [None] * (tracker.G - len(names)),
                            npz_name="positions.npz" if passes == 0 else f"positions_pass{passes}.npz")
         length = res["length"].cpu()
         for s, (i, j) in enumerate(chunk):
-            col = columns.index(j)
+            row, col = rows.index(i), columns.index(j)
             for k in mats:
-                mats[k][i][col] = res[k][s]
-            mean_length[i][col] = float(length[s * episodes:(s + 1) * episodes].float().mean())
+                mats[k][row][col] = res[k][s]
+            mean_length[row][col] = float(length[s * episodes:(s + 1) * episodes].float().mean())
         passes += 1
         if log:
             log(f"[cross-play] pass {passes}: {len(chunk)} cells, {res['ticks']} ticks")
     env.close()
-    return {"cops": [f.name for f in cop_files], "thieves": [f.name for f in thief_files] + ([RANDOM] if random_column else []),
+    return {"cops": [f.name for f in cop_files] + ([CHASE] if scripted else []),
+            "thieves": [f.name for f in thief_files] + ([RANDOM] if random_column else []) + ([EVADE] if scripted else []),
             "episodes": episodes, "greedy": bool(greedy), "passes": passes,
             "cop_win_rate": [[w / episodes for w in row] for row in mats["cop_wins"]], **mats, "mean_length": mean_length}
 
@@ -128,6 +135,7 @@ def main() -> None:
     ap.add_argument("--map", default="squarinth")
     ap.add_argument("--episodes", type=int, default=32, help="env slots (first episodes) per cell")
     ap.add_argument("--random-column", action="store_true", help="a last column of thieves acting uniformly at random")
+    ap.add_argument("--scripted", action="store_true", help="a last row of scripted \"chase\" cops and a last column of scripted \"evade\" thieves")
     ap.add_argument("--greedy", action="store_true", help="the largest logit instead of a draw")
     ap.add_argument("--rays", type=int, default=64)
     ap.add_argument("--n-cops", type=int, default=None)
@@ -141,7 +149,7 @@ def main() -> None:
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     res = crossplay(args.cops, args.thieves, args.map, args.episodes, args.random_column, args.greedy, args.rays, args.n_cops, args.n_thieves,
-                    args.max_step_count, args.seed, log=print, frame_skip=args.frame_skip, heatmaps=args.heatmaps, cell=args.cell)
+                    args.max_step_count, args.seed, log=print, frame_skip=args.frame_skip, heatmaps=args.heatmaps, cell=args.cell, scripted=args.scripted)
     args.out.write_text(json.dumps(res, indent=1))
     print(f"[cross-play] {len(res['cops'])} x {len(res['thieves'])} cells in {res['passes']} pass(es) -> {args.out}")
 

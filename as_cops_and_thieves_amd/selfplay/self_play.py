@@ -308,7 +308,7 @@ def evaluate_agent(eval_env, evaluator: MAPPOTrainer, learned: MAPPOTrainer, lea
 
 
 @torch.no_grad()
-def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1, positions: bool = False) -> Dict[str, object]:
+def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1, positions: bool = False, greedy: bool = False) -> Dict[str, object]:
     """``evaluate_agents``' loop -- the first episode of every slot, one poll per tick -- under the match-ups of a ``LeagueActor``: all its
     segments play at once.  ``episodes_per_segment``: an int or one int per segment -- only the first that many slots of a segment count
     (None: all of them; 0 for a segment that merely fills the env).  Returns per segment (lists in segment order) ``cop_wins`` (winner 0),
@@ -318,7 +318,8 @@ def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1, 
     ``length`` stays in env ticks (the sum of the slot's ``infos["ticks"]``), ``ticks`` counts decisions.
     ``positions``: the env's ``position_tracker`` (``VecCopsEnv(track_positions=CELL, position_groups >= segments)``) is cleared and set up
     like the accounting here -- one group per segment, a quota of the first episode of every counted slot, none of the others -- so that
-    afterwards it holds the maps of exactly the counted episodes; ``out["positions"]`` is its ``summary()``."""
+    afterwards it holds the maps of exactly the counted episodes; ``out["positions"]`` is its ``summary()``.
+    ``greedy``: the networks take their largest logit instead of a draw (``LeagueActor.act(greedy=True)``)."""
     N = env.num_envs
     assert N == actor.N and actor.table is not None
     tracker = env.position_tracker if positions else None      # (an env without one raises here, before anything is played)
@@ -350,7 +351,7 @@ def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1, 
     for _ in range(env.max_step_count + 2):
         if not bool(counted.any()):
             break
-        actions = actor.act(env, starts, obs=obs)
+        actions = actor.act(env, starts, obs=obs, **({"greedy": True} if greedy else {}))
         obs, _, terms, truncs, infos = env.step(actions, **skip)
         ticks += 1
         done = terms[actor.agents[0]]
@@ -375,6 +376,38 @@ def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1, 
     if tracker is not None:
         out["positions"] = tracker.summary()
     return out
+
+
+BASELINE_SEGMENTS = ("cops_vs_evade", "cops_vs_random", "chase_vs_thieves", "random_vs_thieves")
+
+
+def evaluate_against_scripts(eval_env, source, episodes: int, greedy: bool = False, frame_skip: int = 1, fused="kernel", actor=None) -> Dict[str, object]:
+    """Learned policies against the fixed yardstick opponents of ``selfplay.scripted`` in ONE ``evaluate_league`` pass over four segments of
+    ``episodes`` slots each (``eval_env.num_envs == 4 * episodes``), in the order of ``BASELINE_SEGMENTS``: the learned cops against
+    "evade" thieves and against "random" thieves, then "chase" cops and "random" cops against the learned thieves.  ``source``: a
+    ``MAPPOTrainer`` (its current policies) or anything ``LeagueActor.load_set`` reads (a checkpoint file or its dict) holding every agent.
+    ``actor``: a ``LeagueActor`` over ``eval_env`` with at least one set per agent to reuse (else one is built: ``fused`` as in
+    ``LeagueActor.from_env``).  Returns {"segments": names, "episodes", "cop_wins", "thief_wins", "timeouts", "mean_length" (lists in
+    segment order), "cop_win_rate", "ticks"}."""
+    from .actor import LeagueActor
+    agents = list(eval_env.possible_agents)
+    if eval_env.num_envs != 4 * episodes or episodes < 1:
+        raise ValueError(f"evaluate_against_scripts plays 4 segments of {episodes} episodes: the env must have {4 * episodes} slots, not {eval_env.num_envs}")
+    if actor is None:
+        actor = LeagueActor.from_env(eval_env, len(agents), fused=fused)
+    if actor.sets < len(agents) or list(actor.agents) != agents:
+        raise ValueError(f"the actor must cover {agents} with at least {len(agents)} sets")
+    for g, a in enumerate(agents):
+        actor.load_set(g, {a: source.agent_models(a)} if isinstance(source, MAPPOTrainer) else source, a)
+    own = {a: g for g, a in enumerate(agents)}
+    cop = lambda a: a.startswith("cop")
+    who = [{a: own[a] if cop(a) else "evade" for a in agents}, {a: own[a] if cop(a) else "random" for a in agents},
+           {a: "chase" if cop(a) else own[a] for a in agents}, {a: "random" if cop(a) else own[a] for a in agents}]
+    actor.set_matchups([(s * episodes, (s + 1) * episodes, w) for s, w in enumerate(who)])
+    res = evaluate_league(eval_env, actor, frame_skip=frame_skip, greedy=greedy)
+    length = res["length"].float().view(4, episodes).mean(dim=1).tolist()
+    return {"segments": list(BASELINE_SEGMENTS), "episodes": res["episodes"], "cop_wins": res["cop_wins"], "thief_wins": res["thief_wins"],
+            "timeouts": res["timeouts"], "mean_length": length, "cop_win_rate": [c / episodes for c in res["cop_wins"]], "ticks": res["ticks"]}
 
 
 def evaluate_agent_league(eval_env, actor, learned: MAPPOTrainer, archives: Dict[str, Path], tc: TrainingConfig, rng: random.Random, log=print,
@@ -624,7 +657,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   fused_eval: bool = False, league_eval: bool = False, role_training: bool = False,
                   fused_collect: bool = False, value_norm: bool = False, position_stats: Optional[int] = None,
                   lr_schedule: str = "constant", lr_final: Optional[float] = None, lr_kl_target: Optional[float] = None,
-                  entropy_final: Optional[float] = None, ratio_clip_final: Optional[float] = None) -> Dict[str, object]:
+                  entropy_final: Optional[float] = None, ratio_clip_final: Optional[float] = None,
+                  baseline_eval: bool = False, baseline_episodes: int = 64) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -665,6 +699,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     ``position_stats=CELL``: the evaluation env is built with ``track_positions=CELL`` and after every iteration's evaluation rank 0 writes
     the heatmaps of that evaluation's rows (``render.write_heatmaps``) into ``positions_iter_{i}/`` of the run directory, then clears the
     maps.  The simultaneous mode only (ValueError with ``role_training``); envs of an ``env_factory`` must bring their own ``position_tracker``.
+    ``baseline_eval``: after every iteration's evaluation rank 0 plays the trained policies against the fixed yardsticks -- the scripted
+    "chase" / "evade" opponents of ``scripted.py`` and "random" -- in one ``evaluate_against_scripts`` pass on an env of its own with
+    ``4 * baseline_episodes`` slots, and appends the result to ``baselines.json`` of the run directory.  The simultaneous mode only.  Off,
+    nothing of it is built and no random number is drawn for it.
 
     With an initialised ``torch.distributed`` group of W > 1 ranks this is ONE data-parallel job: ``num_envs`` is the TOTAL,
     rank r simulates ``shard_envs(num_envs, r, W)``; the trainer all-reduces its gradient | KL buffer every optimiser step (all
@@ -673,6 +711,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     from ..sharding import shard_envs
     if league_eval and tracked_eval:
         raise ValueError("league_eval plays through evaluate_league (one poll per tick): it cannot be combined with tracked_eval")
+    if baseline_eval and (role_training or baseline_episodes < 1):
+        raise ValueError("baseline_eval belongs to the simultaneous loop (not role_training) and needs baseline_episodes >= 1")
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     chief = rank == 0
@@ -777,6 +817,14 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     else:
         evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False, fused_collect=False),
                                  seed=seed + 1)
+    baseline_env = baseline_actor = None
+    baseline_log = []
+    if baseline_eval and chief:    # the fixed yardsticks (scripted.py): four segments of baseline_episodes slots, one pass per iteration
+        from .actor import LeagueActor
+        baseline_env = eval_factory(4 * baseline_episodes, seed + 7927)
+        baseline_actor = LeagueActor.from_env(baseline_env, len(baseline_env.possible_agents), fused="kernel", compute_bf16=trainer_cfg.compute_bf16,
+                                              normalize_inputs=trainer_cfg.normalize_inputs, recurrent=trainer_cfg.recurrent, seed=seed + 3,
+                                              device=trainer.device)
     rng = random.Random(seed)
     start = 0
     if resume:
@@ -790,11 +838,16 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     stats_file = out_dir / "episode_stats.json"
     if episode_stats and chief and start > 0 and stats_file.exists():
         episode_log = json.loads(stats_file.read_text())
+    baselines_file = out_dir / "baselines.json"
+    if baseline_env is not None and start > 0 and baselines_file.exists():
+        baseline_log = json.loads(baselines_file.read_text())
 
     def finish():
         digest = trainer.param_digest()
         env.close()
         eval_env.close()
+        if baseline_env is not None:
+            baseline_env.close()
         return {"iterations": history, "param_digest": digest, "archives": {r: str(p) for r, p in arch.items()}, "rank": rank, "world": world,
                 "envs_local": n_local, "env_id_offset": offset}
 
@@ -827,6 +880,11 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                     from ..render import write_heatmaps
                     write_heatmaps(out_dir / f"positions_iter_{it}", eval_env.position_tracker, getattr(eval_env, "maps", None) or load_preset(map_name, n_cops, n_thieves))
                     eval_env.position_tracker.clear()
+                if baseline_env is not None:   # the trained policies against the scripted and the random opponents: absolute progress
+                    b = evaluate_against_scripts(baseline_env, trainer, baseline_episodes, frame_skip=trainer_cfg.frame_skip, actor=baseline_actor)
+                    baseline_log.append(dict({"iteration": it}, **b))
+                    baselines_file.write_text(json.dumps(baseline_log, indent=1))
+                    log("[self-play] baselines, cop win rate: " + ", ".join(f"{n} {r:.2f}" for n, r in zip(b["segments"], b["cop_win_rate"])))
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -937,6 +995,9 @@ def main() -> None:
                     "instead of a second trainer")
     ap.add_argument("--league-eval", action="store_true", help="evaluate both roles against all their drawn opponents in one pass through a LeagueActor "
                     "(one act launch per tick for every match-up); not with --tracked-eval")
+    ap.add_argument("--baseline-eval", action="store_true", help="after every iteration play the trained policies against the scripted chase / evade "
+                    "opponents and against random ones in one pass (selfplay/scripted.py) and append the result to baselines.json")
+    ap.add_argument("--baseline-episodes", type=int, default=64, help="--baseline-eval: episodes per match-up (four match-ups share one env)")
     ap.add_argument("--episode-stats", action="store_true", help="account the training episodes on the device: win rate and mean length in "
                     "every iteration's log line, episode_stats.json in --out (with --gpus N: of rank 0's shard)")
     ap.add_argument("--role-training", action="store_true", help="the reference's role-training mode (fictitious play): per iteration a cop phase, then a "
@@ -988,6 +1049,7 @@ def main() -> None:
                         league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}),
                         **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}),
                         **({"position_stats": args.position_stats} if args.position_stats is not None else {}),
+                        **({"baseline_eval": True, "baseline_episodes": args.baseline_episodes} if args.baseline_eval else {}),
                         **{k: v for k, v in (("lr_schedule", args.lr_schedule), ("lr_final", args.lr_final), ("lr_kl_target", args.lr_kl_target),
                                              ("entropy_final", args.entropy_final), ("ratio_clip_final", args.clip_final))
                            if v not in (None, "constant")})

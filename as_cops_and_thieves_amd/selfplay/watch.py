@@ -38,8 +38,11 @@ def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_st
 @torch.no_grad()
 def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, ticks: int = 2000, rays: bool = False, seed: int = 0,
           num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None, n_thieves: Optional[int] = None, device=None,
-          log=print, fused_act: bool = False, greedy: bool = False, frame_skip: int = 1, heatmap: Optional[int] = None) -> Dict[str, object]:
-    """``heatmap=CELL``: a ``positions.PositionTracker`` on a grid of CELL x CELL pixels is fed every decision's rows of the slots still
+          log=print, fused_act: bool = False, greedy: bool = False, frame_skip: int = 1, heatmap: Optional[int] = None,
+          scripts: Optional[Dict[str, str]] = None) -> Dict[str, object]:
+    """``scripts``: {"cop": "chase"} and / or {"thief": "evade"} -- that role's agents follow the scripted opponent of ``scripted.py``
+    instead of their policies (their action columns are written over the policies' every tick).
+    ``heatmap=CELL``: a ``positions.PositionTracker`` on a grid of CELL x CELL pixels is fed every decision's rows of the slots still
     playing (this env does not auto-reset, so the terminal row holds the episode's last position and counts as occupancy, and there is no
     spawn map), and ``heatmaps/`` next to the clips receives the pictures and ``positions.npz`` (``render.write_heatmaps``).  The env is
     built with ``final_positions=True``, so the capture / timeout maps of the episodes played are among them.
@@ -61,6 +64,12 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
         runner = MAPPOTrainer(env, {"cop": CFG_AGENT, "thief": CFG_AGENT}, TrainerConfig(graph_rollout=False, graph_update=False), seed=seed)
         if checkpoint:
             runner.load_state_dict(torch.load(checkpoint, map_location=runner.device, weights_only=True), optimizer=False)
+    scripted = None
+    if scripts:
+        from .scripted import ScriptedActor
+        if any(r not in ("cop", "thief") for r in scripts):
+            raise ValueError(f"scripts names roles: cop and / or thief, not {sorted(scripts)}")
+        scripted = ScriptedActor(env, {a: scripts[a.split("_")[0]] for a in env.possible_agents if a.split("_")[0] in scripts})
     N = env.num_envs
     W, H = (int(v) for v in env.maps[0].window_dimensions)
     slots = list(range(N))
@@ -93,6 +102,8 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
             actions = actor.act(env, starts, greedy=greedy, obs=obs)
         else:
             _trainer_actions(runner, obs, state, starts, actions, ())     # self_play.evaluate_agents' action selection
+        if scripted is not None:
+            scripted.act(env, starts, obs=obs, actions=actions)
         obs, _, terms, _, infos = env.step(actions, **skip)
         starts = torch.zeros_like(starts)
         save(t, open_host)
@@ -117,6 +128,7 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
     frames_of = [(length[k] + 1) if ended[k] and not skip else (t + 1) for k in slots]
     result = {"map": map_name, "envs": N, "ticks": ticks, "checkpoint": checkpoint, "seed": seed, "rays": bool(rays),
               **({"fused_act": True, "greedy": bool(greedy)} if fused_act else {}), **({"frame_skip": frame_skip} if skip else {}),
+              **({"scripts": dict(scripts)} if scripts else {}),
               "slots": [{"env": k, "winner": winner[k], "length": length[k], "terminated": ended[k], "frames": frames_of[k]} for k in slots]}
     (out_dir / "episode.json").write_text(json.dumps(result, indent=1))
     if tracker is not None:
@@ -145,7 +157,15 @@ def main(argv=None) -> int:
     ap.add_argument("--frame-skip", type=int, default=1, help="env ticks per decision (action repeat); one frame per decision, --ticks counts decisions")
     ap.add_argument("--heatmap", type=int, default=None, metavar="CELL", help="also write occupancy / exposure heatmaps of the episodes played, on a "
                     "grid of CELL x CELL pixels, into heatmaps/ next to the clips")
+    ap.add_argument("--script", action="append", default=[], metavar="ROLE=NAME", help="cop=chase or thief=evade: that role follows the scripted "
+                    "opponent instead of its policy (may be given once per role)")
     args = ap.parse_args(argv)
+    scripts = {}
+    for item in args.script:
+        role, _, name = item.partition("=")
+        if role not in ("cop", "thief") or name not in ("chase", "evade"):
+            ap.error(f"--script takes cop=chase, cop=evade, thief=chase or thief=evade, not {item!r}")
+        scripts[role] = name
     if args.heatmap is not None and args.heatmap < 1:
         ap.error("--heatmap must be >= 1")
     if args.envs < 1 or args.ticks < 1 or args.frame_skip < 1:
@@ -153,7 +173,7 @@ def main(argv=None) -> int:
     if args.greedy and not args.fused_act:
         ap.error("--greedy needs --fused-act")
     watch(args.map, args.envs, args.out, args.checkpoint, args.ticks, args.rays, args.seed, args.num_rays, args.max_steps,
-          fused_act=args.fused_act, greedy=args.greedy, frame_skip=args.frame_skip, heatmap=args.heatmap)
+          fused_act=args.fused_act, greedy=args.greedy, frame_skip=args.frame_skip, heatmap=args.heatmap, scripts=scripts or None)
     return 0
 
 

@@ -11,6 +11,8 @@
  *  - cat_rollout_sample: one categorical draw per (agent, env) from the policy logits by inverse CDF on a supplied
  *    uniform number, with the log-probability of the drawn action, written where the rollout keeps them, and the action
  *    into the env's [N][A] action matrix.
+ *  - cat_rollout_scripted: the same place for agents that follow a fixed rule instead of a network: the env core's observation
+ *    buffers -> the action matrix, for the scripted chase / evade opponents.
  *
  * Conventions as in cat_sim.h.
  */
@@ -72,6 +74,40 @@ typedef struct cat_rollout_post_args {
     float *keep_out;                            /* [N] */
 } cat_rollout_post_args;
 int cat_rollout_post(const cat_rollout_post_args *a, void *stream);
+
+/* Scripted opponents: a deterministic, parameter-free rule from an agent's own ray fan to its action, one launch for all (policy g,
+   env n) rows, where cat_rollout_sample / cat_act_step sit.  Script CAT_ROLLOUT_CHASE heads for the nearest ray of type target[g] (a
+   cop's: THIEF = 2) and for where it last saw one for memory_ticks more ticks; CAT_ROLLOUT_EVADE runs from it (a thief's target:
+   COP = 1).  Both keep clear of what their ray fan shows closer than clear_min in the cone of the direction they take, and wander
+   (hold the heading, turn with probability turn_prob) when they have no bearing.  All integer arithmetic but the two fp32
+   comparisons free >= clear_min and uniform < turn_prob; as_cops_and_thieves_amd/selfplay/scripted.py states the rule in full and
+   the kernel equals it bit for bit.
+   Rows seg_start[s] .. seg_start[s + 1] - 1 of policy g follow seg_script[g][s]; -1: neither the action column nor the state row of
+   those rows is touched.  S = 1 is the plain form.  state rows are (valid, heading, mem_ray, ttl); keep as in cat_act_step: 0 takes
+   the row's state as all zero before the tick, NULL carries every state.  No atomics, no allocation, no synchronisation. */
+#define CAT_ROLLOUT_MAX_SEGMENTS 32
+#define CAT_ROLLOUT_MIN_RAYS 8
+#define CAT_ROLLOUT_MAX_RAYS 1024
+enum { CAT_ROLLOUT_CHASE = 0, CAT_ROLLOUT_EVADE = 1 };
+
+typedef struct cat_rollout_scripted_args {
+    int32_t N, A, R, G;                         /* envs, agents in the env, rays (8 .. 1024), scripted policies (<= 8) */
+    int32_t agent[CAT_ROLLOUT_MAX_AGENTS];      /* env agent index of policy g: its observation row and its action column */
+    int32_t target[CAT_ROLLOUT_MAX_AGENTS];     /* the type code policy g looks for: 1 (cop) or 2 (thief) */
+    int32_t memory_ticks;                       /* >= 0: ticks a lost bearing is still followed */
+    float clear_min;                            /* >= 0: a cone is free when nothing but the target is closer than this */
+    float turn_prob;                            /* in [0, 1]: chance per tick of a turn while wandering */
+    int32_t S;                                  /* segments, 1 .. CAT_ROLLOUT_MAX_SEGMENTS */
+    int32_t seg_start[CAT_ROLLOUT_MAX_SEGMENTS + 1];                        /* 0 first, N last, strictly increasing */
+    int32_t seg_script[CAT_ROLLOUT_MAX_AGENTS][CAT_ROLLOUT_MAX_SEGMENTS];   /* [g][s]: CAT_ROLLOUT_CHASE / _EVADE / -1 */
+    const void *obs_distance;                   /* f16 [N][A][R], non-negative and finite */
+    const void *obs_type;                       /* u8  [N][A][R] */
+    const float *uniform;                       /* [G][N] in [0, 1) */
+    const float *keep;                          /* [N] or NULL */
+    int32_t *state;                             /* [G][N][4], 16-byte aligned, updated in place */
+    int32_t *actions;                           /* [N][A] */
+} cat_rollout_scripted_args;
+int cat_rollout_scripted(const cat_rollout_scripted_args *a, void *stream);
 
 int cat_rollout_abi_version(void);
 const char *cat_rollout_last_error(void);
