@@ -61,10 +61,13 @@ def _onto_wall(cpu, e, p, d, rc):
 
 
 class Trace:
-    def __init__(self, name):
-        c = CASES[name]
+    """``case`` / ``cmap``: a case record and a compiled map of the caller's (tests/step_truth_cases.py: maps that are no preset, other scripts);
+    by default the case of that name above on its preset.  A subclass may place the bodies (``_place``) and script them (``_action``) differently."""
+
+    def __init__(self, name, case=None, cmap=None):
+        c = CASES[name] if case is None else case
         self.name, self.case = name, c
-        self.cmap = load_preset(c["map"], c["cops"], c["thieves"]).compile()
+        self.cmap = load_preset(c["map"], c["cops"], c["thieves"]).compile() if cmap is None else cmap
         self.cfg = SimConfig(n_envs=c["n"], n_cops=c["cops"], n_thieves=c["thieves"], n_rays=c["rays"], max_step_count=10 ** 6, seed=11)
         cpu = OracleSim(self.cfg, [self.cmap])
         N, A, T = cpu.N, cpu.A, c["ticks"]
@@ -73,14 +76,7 @@ class Trace:
         self.reset_out = {k: np.array(v, copy=True) for k, v in cpu.reset(positions=self.start).items() if k in OBS_KEYS}
         # envs 1 and 3 of every five stand still for the whole run (contact-free slots beside contact slots); in the others, every third body starts ON a wall
         self.calm = np.array([e % 5 in (1, 3) for e in range(N)])
-        pos = cpu.get_state()["pos"].copy()
-        for e in range(N):
-            for i in range(A):
-                if not self.calm[e] and (e + i) % 3 == 0:
-                    pos[e, i] = _onto_wall(cpu, e, pos[e, i], int(rng.integers(4)), self.cfg.agent_radius)
-        for e, i, x, y in c.get("three_walls", ()):
-            pos[e, i] = (x, y)
-        self.placed = pos
+        self.placed = pos = self._place(cpu, rng, cpu.get_state()["pos"].copy())
         cpu.set_state(pos=pos)
         self.actions = np.zeros((T, N, A), np.int32)
         self.outs, self.states = [], []
@@ -89,29 +85,40 @@ class Trace:
             st = cpu.get_state() if t == 0 else self.states[-1]
             for e in range(N):
                 for i in range(A):
-                    if self.calm[e]:
-                        self.actions[t, e, i] = STILL[t % 4]
-                        continue
-                    if mode[e, i, 2] <= 0:
-                        mode[e, i] = (rng.choice(4, p=(0.3, 0.25, 0.3, 0.15)), rng.integers(4), rng.integers(10, 35))
-                        if mode[e, i, 0] == 2:
-                            mode[e, i, 1] = (i + 1 + rng.integers(A - 1)) % A
-                    kind, arg = mode[e, i, 0], mode[e, i, 1]
-                    mode[e, i, 2] -= 1
-                    if kind == 0:      # push one way (into a wall, or away from the one behind)
-                        a = arg
-                    elif kind == 1:    # into a corner: two neighbouring directions in turn
-                        a = (arg + t % 2) % 4
-                    elif kind == 2:    # chase body `arg`
-                        a = _towards(st["pos"][e, arg] - st["pos"][e, i])
-                    else:
-                        a = STILL[t % 4]
-                    self.actions[t, e, i] = a
+                    self.actions[t, e, i] = self._action(rng, t, e, i, st, mode)
             out = cpu.step(self.actions[t])
             self.outs.append({k: np.array(v, copy=True) for k, v in out.items()})
             self.states.append({k: np.array(v, copy=True) for k, v in cpu.get_state().items()})
         self.coverage = coverage(self.states)
         self.min_over_bound = c.get("over_bound", 0)
+
+    def _place(self, cpu, rng, pos):
+        """in the envs that are not calm, every third body starts ON a wall; the case's bodies where three walls overlap"""
+        for e in range(cpu.N):
+            for i in range(cpu.A):
+                if not self.calm[e] and (e + i) % 3 == 0:
+                    pos[e, i] = _onto_wall(cpu, e, pos[e, i], int(rng.integers(4)), self.cfg.agent_radius)
+        for e, i, x, y in self.case.get("three_walls", ()):
+            pos[e, i] = (x, y)
+        return pos
+
+    def _action(self, rng, t, e, i, st, mode):
+        if self.calm[e]:
+            return STILL[t % 4]
+        A = mode.shape[1]
+        if mode[e, i, 2] <= 0:
+            mode[e, i] = (rng.choice(4, p=(0.3, 0.25, 0.3, 0.15)), rng.integers(4), rng.integers(10, 35))
+            if mode[e, i, 0] == 2:
+                mode[e, i, 1] = (i + 1 + rng.integers(A - 1)) % A
+        kind, arg = mode[e, i, 0], mode[e, i, 1]
+        mode[e, i, 2] -= 1
+        if kind == 0:      # push one way (into a wall, or away from the one behind)
+            return arg
+        if kind == 1:      # into a corner: two neighbouring directions in turn
+            return (arg + t % 2) % 4
+        if kind == 2:      # chase body `arg`
+            return _towards(st["pos"][e, arg] - st["pos"][e, i])
+        return STILL[t % 4]
 
 
 @functools.lru_cache(maxsize=None)
