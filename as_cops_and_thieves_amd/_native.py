@@ -136,7 +136,10 @@ def lib() -> C.CDLL:
     if hasattr(L, "cat_bbtree_host"):
         L.cat_bbtree_host.argtypes = [vp, C.c_size_t, vp, vp, i32, vp, vp]
         L.cat_bbtree_host.restype = i32
-    if hasattr(L, "cat_debug_tree_counts"):      # diagnostic builds only (-DCAT_TREE_COUNTS)
+    if hasattr(L, "cat_plan_describe_host"):     # absent from diagnostic builds of earlier sources
+        L.cat_plan_describe_host.argtypes = [vp, vp, vp, vp, i32, vp, C.c_char_p, C.c_size_t]   # cfg, tables, blobs, sizes, n_maps, slot_map_ids, buf, cap
+        L.cat_plan_describe_host.restype = i32
+    if hasattr(L, "cat_debug_tree_counts"):     # diagnostic builds only (-DCAT_TREE_COUNTS)
         L.cat_debug_tree_counts.argtypes = [vp, i32]
         L.cat_debug_tree_counts.restype = i32
     if hasattr(L, "cat_reward_arith_host"):      # absent from diagnostic builds of earlier sources
@@ -157,4 +160,5 @@ EXPORTED_SYMBOLS = ("cat_abi_version", "cat_one_tick_kernel", "cat_rollout_kerne
                     "cat_reset_done", "cat_step", "cat_step_fused", "cat_rollout_fused", "cat_step_repeat", "cat_get_state", "cat_set_state", "cat_random_actions",
                     "cat_set_seed", "cat_device_errors", "cat_arm_kernel_timing", "cat_num_agents", "cat_num_shapes", "cat_selftest_arith", "cat_debug_grid_lookup",
                     "cat_grid_build_host", "cat_grid_lookup_host", "cat_grid_bytes_host", "cat_grid_free_host", "cat_map_wall_bb_depth_host",
-                    "cat_bbtree_host", "cat_reward_arith_host", "cat_reward_arith_max", "cat_debug_reward_table", "cat_bind_final_positions")
+                    "cat_bbtree_host", "cat_reward_arith_host", "cat_reward_arith_max", "cat_debug_reward_table", "cat_bind_final_positions",
+                    "cat_plan_describe_host")

@@ -20,13 +20,16 @@
 //   physics_env              pymunk Space.step -> [CP cpSpaceStep]  (call site base_env.py:392)
 //   termination_captured     BaseEnv._termination_criterion       src/environments/base_env.py:521-554
 //
-// One translation unit: this file includes cat_sim_{common,reward,geometry,fan,physics,scheduler}.h inside its anonymous namespace, then cat_sim_host.h.
+// One translation unit: this file includes cat_sim_{common,reward,geometry,fan,physics,scheduler}.h inside its anonymous namespace, then the host side:
+// cat_sim_grid.h (knobs, map blobs, candidate tables, static tree: no device needed), cat_sim_plan.h (plan_sim: every decision and table of a sim, no
+// device needed) and cat_sim_host.h (cat_create = plan + upload, the launches).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
 #include <cfloat>
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -50,4 +53,6 @@ namespace {
 #include "cat_sim_scheduler.h"
 }  // namespace
 
+#include "cat_sim_grid.h"
+#include "cat_sim_plan.h"
 #include "cat_sim_host.h"

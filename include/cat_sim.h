@@ -279,6 +279,12 @@ int cat_map_wall_bb_depth_host(const void *map_blob, size_t blob_size, double ag
    or an error code.  Any output pointer may be NULL. */
 int cat_bbtree_host(const void *map_blob, size_t blob_size, double *bb_out, int *link_out, int max_nodes, int *root, int *depth);
 
+/* Host-only: the text cat_create prints under CAT_VERBOSE for these arguments (every decision it takes and a hash of
+   every table it would upload), without a device.  Lines of key=value; at most cap - 1 characters and a NUL are written
+   to buf (which may be NULL).  Returns the length of the whole text, or a CAT_ERR_* with cat_last_error(NULL) set. */
+int cat_plan_describe_host(const cat_config *cfg, const cat_tables *tables, const void *const *map_blobs, const size_t *blob_sizes,
+                           int n_maps, const int32_t *slot_map_ids, char *buf, size_t cap);
+
 /* Device arithmetic self-test used by tests: out[i] = op(in_a[i], in_b[i]) evaluated on the GPU
    with the same primitives the kernels use (op 0 sqrt(a), 1 a/b, 2 f64->f16 bits of a,
    3 obs-distance f16 bits of (a,b) relative to the origin (0,0)).  DEVICE pointers. */
