@@ -142,6 +142,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "cat_debug_tree_counts"):     # diagnostic builds only (-DCAT_TREE_COUNTS)
         L.cat_debug_tree_counts.argtypes = [vp, i32]
         L.cat_debug_tree_counts.restype = i32
+    if hasattr(L, "cat_radius_thresholds_host"):   # absent from diagnostic builds of earlier sources
+        L.cat_radius_thresholds_host.argtypes = [C.c_double, C.c_double, C.c_double, vp]
+        L.cat_radius_thresholds_host.restype = i32
     if hasattr(L, "cat_reward_arith_host"):      # absent from diagnostic builds of earlier sources
         L.cat_reward_arith_host.argtypes = [vp, vp, vp]
         L.cat_reward_arith_host.restype = i32
@@ -161,4 +164,4 @@ EXPORTED_SYMBOLS = ("cat_abi_version", "cat_one_tick_kernel", "cat_rollout_kerne
                     "cat_set_seed", "cat_device_errors", "cat_arm_kernel_timing", "cat_num_agents", "cat_num_shapes", "cat_selftest_arith", "cat_debug_grid_lookup",
                     "cat_grid_build_host", "cat_grid_lookup_host", "cat_grid_bytes_host", "cat_grid_free_host", "cat_map_wall_bb_depth_host",
                     "cat_bbtree_host", "cat_reward_arith_host", "cat_reward_arith_max", "cat_debug_reward_table", "cat_bind_final_positions",
-                    "cat_plan_describe_host")
+                    "cat_plan_describe_host", "cat_radius_thresholds_host")

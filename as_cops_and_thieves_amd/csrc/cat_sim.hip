@@ -21,7 +21,7 @@
 //   termination_captured     BaseEnv._termination_criterion       src/environments/base_env.py:521-554
 //
 // One translation unit: this file includes cat_sim_{common,reward,geometry,fan,physics,scheduler}.h inside its anonymous namespace, then the host side:
-// cat_sim_grid.h (knobs, map blobs, candidate tables, static tree: no device needed), cat_sim_plan.h (plan_sim: every decision and table of a sim, no
+// cat_sim_grid.h (knobs, map blobs, candidate tables, static tree: no device needed), cat_sim_radius.h (the radius tests' thresholds), cat_sim_plan.h (plan_sim: every decision and table of a sim, no
 // device needed) and cat_sim_host.h (cat_create = plan + upload, the launches).
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared
 #include <hip/hip_runtime.h>
@@ -54,5 +54,6 @@ namespace {
 }  // namespace
 
 #include "cat_sim_grid.h"
+#include "cat_sim_radius.h"
 #include "cat_sim_plan.h"
 #include "cat_sim_host.h"

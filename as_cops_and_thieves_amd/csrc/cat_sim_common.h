@@ -48,6 +48,7 @@ struct Params {
     long long env_id_offset;
     unsigned long long seed;
     double dt, bias_coef, slop, ray_length, ray_radius, rc, mass, impulse, max_speed, term_radius, wall_r;
+    double term_d2, near_d2;   // the two radius tests on squared distances: sqrt(x) < term_radius <=> x < term_d2, sqrt(x) - rc <= ray_radius <=> x <= near_d2 (cat_sim_radius.h)
     const double *ray_dx, *ray_dy;
     const float *cop_lut, *thief_lut;
     const MapDesc *maps;
@@ -86,6 +87,7 @@ struct Params {
     const int *tree_link;
     const int *tree_root;
     int lds_racc_off;       // cat_step_repeat: byte offset, in a slot's env area, of its [A] f32 reward accumulators (lds_sizes)
+    int lds_o16_off;        // byte offset, in a slot's env area, of the [A] float16 tick-start origins (Lds::o16; lds_sizes)
 };
 
 // Problem dimensions as seen by the device code: either read from the parameter block (DynDims) or compile-time
@@ -304,6 +306,16 @@ __device__ __forceinline__ unsigned obs_distance_f16(double px, double py, doubl
     return f32_to_f16(hyp);
 }
 
+// ... with the origin's two float16 values already converted (Lds::o16: x | y << 16)
+__device__ __forceinline__ unsigned obs_distance_f16(double px, double py, unsigned o16)
+{
+    float dx32 = f16_to_f32(f64_to_f16(px)) - f16_to_f32(o16 & 0xFFFFu);
+    float dy32 = f16_to_f32(f64_to_f16(py)) - f16_to_f32(o16 >> 16);
+    float dx = f16_to_f32(f32_to_f16(dx32)), dy = f16_to_f32(f32_to_f16(dy32));
+    float hyp = (float)sqrt((double)dx * (double)dx + (double)dy * (double)dy);
+    return f32_to_f16(hyp);
+}
+
 __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
                                            unsigned k0, unsigned k1, unsigned out[4])
 {
@@ -352,6 +364,7 @@ struct Lds {
     double *pos, *vel, *vb, *tc, *leaf;  // [A][2] x4, [A][4]
     const double *fpos, *ftc, *fleaf;    // what the ray fan reads: the tick-start snapshot of pos / tc / leaf
     unsigned *dmin;   // [A] minimum wanted-class distance (f16 bits), 0x10000 = none seen
+    unsigned *o16;    // [A] float16 bits of the tick-start origin fpos, x | y << 16 (agent_setup): the origin's side of obs_distance_f16, once per agent instead of per ray
     int *flags;       // step, captured, timeout, -
     int *ctrl;        // workgroup: [wpb][4] = chunks claimed, chunks done, published, env id
     double *wjn, *pjn;

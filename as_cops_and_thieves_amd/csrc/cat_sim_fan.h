@@ -284,7 +284,7 @@ __device__ __forceinline__ void agent_setup(const Lds &L, const Params &p, const
             else { l = tcx - p.rc; b = tcy - p.rc; r = tcx + p.rc; t = tcy + p.rc; }
             if ((l <= ax + reach) && (ax - reach <= r) && (b <= ay + reach) && (ay - reach <= t)) {
                 const double ex = ax - tcx, ey = ay - tcy;
-                near = sqrt(ex * ex + ey * ey) - p.rc <= r2;  // [CP cpCircleShapePointQuery]
+                near = ex * ex + ey * ey <= p.near_d2;  // [CP cpCircleShapePointQuery] sqrt(e2) - rc <= r2, by its threshold on e2
                 ray_cone(p, ax, ay, l - cone_m, b - cone_m, r + cone_m, t + cone_m, R, k0, cnt);
             }
         }
@@ -295,6 +295,8 @@ __device__ __forceinline__ void agent_setup(const Lds &L, const Params &p, const
         if (lane < A) L.adn[lane] = (int)((nearbits >> (lane * A)) & ((1ull << A) - 1ull));
     }
     if (lane < A) { L.acell[lane] = my_cell; L.anear[2 * lane] = my_near0; L.anear[2 * lane + 1] = my_near1; L.dmin[lane] = 0x10000u; }
+    if constexpr (D::kFan == 1)   // np.float16 of the origin (entity.py:208), for the pooled rounds alone: only a sim with a ring runs them
+        if (p.lds_pool_off != 0 && lane < A) L.o16[lane] = f64_to_f16(L.fpos[2 * lane]) | (f64_to_f16(L.fpos[2 * lane + 1]) << 16);
     if (lane < A * A) { L.dk0[lane] = my_dk0; L.dcnt[lane] = my_dcnt; }
     wave_sync();
 }
@@ -1059,7 +1061,8 @@ __device__ __forceinline__ void rewards_and_positions(const Lds &L, const Params
 // observations, which the lookup's round trip then overlaps.)
 __device__ __forceinline__ void await_reward(LateOut &late) { asm volatile("" : "+v"(late.reward)); }
 
-// LDS -> HBM copy of n bytes with the widest store both sides allow (LDS side is 16-byte aligned)
+// LDS -> HBM copy of n bytes with the widest store both sides allow (LDS side is 16-byte aligned).  INVARIANT: reads exactly the n bytes of the array, never the
+// padding up to its 16-byte alignment -- lds_sizes() keeps the float16 origins (Lds::o16) in such a gap behind a staging array.
 __device__ __forceinline__ void wide_store(void *gdst, const void *lsrc, int n, int lane)
 {
     const unsigned long long ga = (unsigned long long)gdst;
@@ -1121,7 +1124,7 @@ __device__ __forceinline__ int termination_captured(const Lds &L, const Params &
     if (lane < npairs) {
         const int t = nc + lane / nc, c = lane % nc;
         const double ddx = L.pos[2 * t] - L.pos[2 * c], ddy = L.pos[2 * t + 1] - L.pos[2 * c + 1];  // Vec2d.get_distance
-        within = sqrt(ddx * ddx + ddy * ddy) < p.term_radius;
+        within = ddx * ddx + ddy * ddy < p.term_d2;   // sqrt(d2) < term_radius, by its threshold on d2 (cat_sim_radius.h)
     }
     unsigned long long cand = __ballot(within);
     while (cand) {   // in pair order; the first pair with a clear line of sight captures

@@ -431,6 +431,14 @@ extern "C" int cat_selftest_arith(int op, const double *a, const double *b, doub
     return hipGetLastError() == hipSuccess ? CAT_OK : CAT_ERR_HIP;
 }
 
+extern "C" int cat_radius_thresholds_host(double term_radius, double agent_radius, double ray_radius, double *out2)
+{
+    if (!out2) return CAT_ERR_BAD_ARG;
+    out2[0] = radius_lt_threshold(term_radius);
+    out2[1] = radius_le_threshold(agent_radius, ray_radius);
+    return CAT_OK;
+}
+
 extern "C" int cat_reward_arith_host(const float *cop_lut, const float *thief_lut, float *out)
 {
     if (out)

@@ -32,6 +32,7 @@ struct RecLayout {
 struct LdsSizes {
     int map, env, uni;
     int racc;   // offset in an env area of the [A] f32 reward accumulators of cat_step_repeat
+    int o16;    // ... of the [A] float16 origins (Lds::o16)
     size_t total(int wpb) const { return (size_t)map + (size_t)ctrl_bytes(wpb) + (size_t)wpb * ((size_t)env + (size_t)uni); }
 };
 constexpr size_t kLdsBytes = 160 * 1024;   // of a CU (gfx950)
@@ -50,8 +51,24 @@ static LdsSizes lds_sizes(int A, int R, int maxS, int maxP, int maxPP, bool grou
     // (2v1: 12 of 12, 1v1: 8 of 8), else the end of the area -- which the padding below absorbs for 3v2: the carve of every instantiated shape keeps its size
     const int gap = up(eb, 16) - eb;
     z.racc = gap >= 4 * A ? eb : -1;
+    const int stage0 = eb;
     eb = up(eb, 16) + up(A * R * 2, 16) + up(A * R, 16) + up(2 * R * 2, 16) + up(2 * R, 16);   // output staging
     if (z.racc < 0) { z.racc = eb; eb += up(4 * A, 16); }
+    // The float16 origins ([A] words) go where the area has room already: the first gap that the 16-byte alignment leaves behind a staging array (the arrays are
+    // written and stored element by element up to their own length: wide_store), else the end -- where the padding below absorbs them for 2v1 at 64 rays, 3v2 and
+    // 2v2: none of the instantiated and recorded shapes' areas grows by them.  A roster / ray count with neither a gap nor pad slack grows by 16 bytes per
+    // slot, and a ring that only just fitted such a shape drops to the next attempt (exact capacity, smaller group arrays, or no ring).
+    z.o16 = -1;
+    {
+        const int sz[4] = {A * R * 2, A * R, 2 * R * 2, 2 * R};
+        int off = up(stage0, 16);
+        for (int q = 0; q < 4; q++) {
+            const int a4 = up(off + sz[q], 4), next = up(off + sz[q], 16);
+            if (z.o16 < 0 && next - a4 >= 4 * A) z.o16 = a4;
+            off = next;
+        }
+    }
+    if (z.o16 < 0) { z.o16 = eb; eb += 4 * A; }
     z.env = up(eb, 16);
     // The pooled rounds address env areas PER LANE (a round's rays come from several slots: origin, cached circles, "inside" walls, output staging of the
     // lane's slot).  An area of a multiple of 256 bytes -- 2v1 at 64 rays: exactly 2048 -- puts the same field of every slot on the same LDS banks; with
@@ -551,6 +568,7 @@ static int plan_part(const cat_config *cfg, SimPlan &plan, PartPlan &pt, std::ve
     p.maxE = maxS + A;
     p.lds_map_bytes = ls.map; p.lds_env_bytes = ls.env; p.lds_union_bytes = ls.uni; p.wpb = wpb;
     p.lds_racc_off = ls.racc;
+    p.lds_o16_off = ls.o16;
     p.grp_rays = grp_rays;
     p.item_cap = item_cap;
     p.lds_pool_off = pool_cap ? (int)((ls.total(wpb) + 15) / 16 * 16) : 0;
@@ -597,6 +615,7 @@ static int plan_sim(const cat_config *cfg, const cat_tables *tab, const void *co
     base.dt = cfg->dt; base.bias_coef = cfg->bias_coef; base.slop = cfg->slop; base.ray_length = cfg->ray_length;
     base.ray_radius = cfg->ray_radius; base.rc = cfg->agent_radius; base.mass = cfg->agent_mass; base.impulse = cfg->impulse;
     base.max_speed = cfg->max_speed; base.term_radius = cfg->termination_radius; base.wall_r = cfg->wall_radius;
+    base.term_d2 = radius_lt_threshold(base.term_radius); base.near_d2 = radius_le_threshold(base.rc, base.ray_radius);
     base.hot_bytes = RecLayout(A).hot_bytes();
     base.rec_bytes = RecLayout(A).rec_bytes();
     if (base.hot_bytes > kLanes * 16) PLAN_FAIL(CAT_ERR_BAD_CONFIG, "state record of %d bytes exceeds the kernels' register staging", base.hot_bytes);   // StateRegs

@@ -44,6 +44,7 @@ __device__ __forceinline__ Lds carve(const Params &p, char *smem, const MapDesc 
         L.sd = reinterpret_cast<unsigned short *>(o); o += align_up(2 * R * 2, 16);
         L.st = reinterpret_cast<unsigned char *>(o);
     }
+    L.o16 = reinterpret_cast<unsigned *>(w + p.lds_o16_off);
     // union: contact arrays (physics) / ray-fan scratch
     char *u = smem + p.lds_map_bytes + ctrl_bytes(W) + W * p.lds_env_bytes + wave * p.lds_union_bytes;
     L.conf = reinterpret_cast<double *>(u);
@@ -848,6 +849,14 @@ __device__ __forceinline__ int pool_sort(const Lds &L, const Params &p, const La
                 wrow[q] = ((GAS const unsigned *)G(p.grid_rows))[gd.row_base + r];
             }
         }
+        // One reservation for the (up to four) chunks of the group: every chunk's active rays are counted first, then one fetch-add, one broadcast and
+        // one wait cover them all -- per chunk these were three LDS round trips each on the front's serial chain.  The group's entries are consecutive in the ring.
+        unsigned dyn[4] = {0u, 0u, 0u, 0u}, actbits = 0u;   // bit q of actbits: this lane's ray of chunk c0 + q becomes an entry
+        int pos[4] = {0, 0, 0, 0};   // the entry's place among the group's, then its position in the ring
+        int n_grp = 0;
+#ifdef CAT_FAULT_INJECT
+        bool inject = false;
+#endif
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             if (c0 + q < nch) {
@@ -863,33 +872,51 @@ __device__ __forceinline__ int pool_sort(const Lds &L, const Params &p, const La
                         int rel = k - dk; if (rel < 0) rel += R;
                         if (rel < dc) dynmask |= 1u << j;
                     }
-                bool act = rowv != 0u || dynmask != 0u;
+                wrow[q] = rowv; dyn[q] = dynmask;
+                const bool act = rowv != 0u || dynmask != 0u;
                 const unsigned long long m = __ballot(act);
-                const int n = __popcll(m);
-                int base = 0;
-                if (n) {
-                    if (lane == 0) base = __hip_atomic_fetch_add(&pctl[1], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    base = uni(base);
-                }
-                unsigned long long *const e = &pool[act ? ring_pos<kExact>(p, (unsigned)(base + __popcll(m & lt_mask))) : 0];
-#ifdef CAT_FAULT_INJECT   // diagnostic build only (tests/test_gpu_fault_injection.py): the first entry of slot 0 is reserved and never written
-                if (slot == 0 && c0 + q == 0 && n && lane == (int)__builtin_ctzll(m)) act = false;
-#endif
-                // The ring holds at most wpb * A * R entries that are not yet counted, but an entry counts as read only once the wave that claimed its
-                // round has loaded it: the position must read 0 (cleared by that reader) before a new entry goes there.  True at the first look in every
-                // run observed; the wait makes it an invariant instead of a matter of timing (bounded like every wait of the scheduler).
-                for (int spins = 0; __ballot(act && __hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0ull) != 0ull;)
-                    if (++spins >= kSpinLimit) { if (lane == 0) atomicOr(p.err_word, CAT_DEVERR_SCHEDULER); break; }
-                if (act) {
-                    const unsigned meta = kPoolValid | ((unsigned)slot << 24) | ((unsigned)i << 16) | (dynmask << 8) | (unsigned)k;
-                    __hip_atomic_store(e, ((unsigned long long)meta << 32) | rowv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                } else if (in && (rowv == 0u && dynmask == 0u)) {   // nothing along this ray: its observation is final
+                pos[q] = n_grp + __popcll(m & lt_mask);
+                n_grp += __popcll(m);
+                if (act) actbits |= 1u << q;
+                else if (in) {   // nothing along this ray: its observation is final
                     const int o = i * R + k;
                     L.od[o] = (unsigned short)d_empty;
                     L.ot[o] = (unsigned char)CAT_EMPTY;
                     if (la.out.hit_shape && (!kRowGate || env >= 0)) la.out.hit_shape[(size_t)env * A * R + o] = -1;  // parity/debug only
                 }
-                n_res += __popcll(__ballot(in && (rowv == 0u && dynmask == 0u)));
+#ifdef CAT_FAULT_INJECT   // diagnostic build only (tests/test_gpu_fault_injection.py): the first entry of slot 0 is reserved and never written
+                if (slot == 0 && c0 + q == 0 && m && lane == (int)__builtin_ctzll(m)) inject = true;
+#endif
+                n_res += __popcll(__ballot(in && !act));
+            }
+        }
+        if (n_grp == 0) continue;
+        int base = 0;
+        if (lane == 0) base = __hip_atomic_fetch_add(&pctl[1], n_grp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        base = uni(base);
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (c0 + q < nch) pos[q] = ((actbits >> q) & 1u) ? ring_pos<kExact>(p, (unsigned)(base + pos[q])) : 0;
+#ifdef CAT_FAULT_INJECT
+        if (inject) actbits &= ~1u;
+#endif
+        // The ring holds at most wpb * A * R entries that are not yet counted, but an entry counts as read only once the wave that claimed its
+        // round has loaded it: a position must read 0 (cleared by that reader) before a new entry goes there.  True at the first look in every
+        // run observed; the wait makes it an invariant instead of a matter of timing (bounded like every wait of the scheduler).
+        for (int spins = 0;;) {
+            bool busy = false;
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                if (c0 + q < nch && ((actbits >> q) & 1u)) busy |= __hip_atomic_load(&pool[pos[q]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0ull;
+            if (__ballot(busy) == 0ull) break;
+            if (++spins >= kSpinLimit) { if (lane == 0) atomicOr(p.err_word, CAT_DEVERR_SCHEDULER); break; }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (c0 + q < nch && ((actbits >> q) & 1u)) {
+                const int i = (c0 + q) / cpa, k = ((c0 + q) - i * cpa) * kLanes + lane;
+                const unsigned meta = kPoolValid | ((unsigned)slot << 24) | ((unsigned)i << 16) | (dyn[q] << 8) | (unsigned)k;
+                __hip_atomic_store(&pool[pos[q]], ((unsigned long long)meta << 32) | wrow[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
     }
@@ -1041,7 +1068,7 @@ __device__ __forceinline__ unsigned pool_round(const Lds &L0, const Params &p, c
                 circle_hit_point(v.x, v.y, ax, ay, bx, by, t, r2, px, py);
             }
         }
-        d16 = obs_distance_f16(px, py, ax, ay);
+        d16 = obs_distance_f16(px, py, slot_ptr(L0.o16, s, envb)[i]);
         ty = (best < S) ? CAT_WALL : ((best - S) >= n_cops ? CAT_THIEF : CAT_COP);
     }
     if (on) {  // observations go to the slot's staging in LDS; one coalesced burst to HBM at its write-back
@@ -1446,6 +1473,9 @@ __global__ void selftest_kernel(int op, const double *a, const double *b, double
     else if (op == 1) r = a[i] / b[i];
     else if (op == 2) r = (double)f64_to_f16(a[i]);
     else if (op == 3) r = (double)obs_distance_f16(a[i], b[i], 0.0, 0.0);
+    // the radius tests on a squared distance a[i], with the square root (bit 0) and by the host's threshold (bit 1; cat_sim_radius.h): b = {radius, threshold} ...
+    else if (op == 4) r = (double)((sqrt(a[i]) < b[0] ? 1 : 0) | (a[i] < b[1] ? 2 : 0));
+    else if (op == 5) r = (double)((sqrt(a[i]) - b[0] <= b[1] ? 1 : 0) | (a[i] <= b[2] ? 2 : 0));   // ... b = {rc, ray radius, threshold}
     out[i] = r;
 }
 

@@ -287,9 +287,16 @@ int cat_plan_describe_host(const cat_config *cfg, const cat_tables *tables, cons
 
 /* Device arithmetic self-test used by tests: out[i] = op(in_a[i], in_b[i]) evaluated on the GPU
    with the same primitives the kernels use (op 0 sqrt(a), 1 a/b, 2 f64->f16 bits of a,
-   3 obs-distance f16 bits of (a,b) relative to the origin (0,0)).  DEVICE pointers. */
+   3 obs-distance f16 bits of (a,b) relative to the origin (0,0); 4 and 5: a radius test on the squared distance a with the
+   square root (bit 0 of the result) and by its threshold (bit 1) -- 4: sqrt(a) < b[0] | a < b[1]; 5: sqrt(a) - b[0] <= b[1] |
+   a <= b[2]; in_b then holds those two or three values, not n).  DEVICE pointers. */
 int cat_selftest_arith(int op, const double *in_a, const double *in_b, double *out, int n, int device,
                        void *stream);
+
+/* Host-only: the thresholds by which the kernels run their two radius tests on SQUARED distances (csrc/cat_sim_radius.h):
+   out2[0] = the double X with sqrt(x) < term_radius <=> x < X, out2[1] = the double E with sqrt(x) - agent_radius <= ray_radius
+   <=> x <= E, for every x >= 0 (-1: no such x). */
+int cat_radius_thresholds_host(double term_radius, double agent_radius, double ray_radius, double *out2);
 
 /* The non-terminal rewards as arithmetic (csrc/cat_sim_reward.h), a bit-exact restatement of the two reward tables that the kernels do not use (measured
    slower than the table load: DESIGN 4.9) and the tests keep exact.  cat_reward_arith_host (host only, no device): writes the HOST build's value for every
