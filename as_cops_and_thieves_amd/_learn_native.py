@@ -16,7 +16,8 @@ if os.environ.get("CAT_LEARN_LIB"):         # diagnostic builds (A/B of kernel v
     LIB_PATH = Path(os.environ["CAT_LEARN_LIB"]).resolve()
 SOURCES = tuple(PKG / "csrc" / f"cat_{n}.hip" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes", "act"))
 HEADERS = tuple(ROOT / "include" / f"cat_{n}.h" for n in ("lstm", "trunk", "ppo", "dense", "rollout", "render", "episodes", "act"))
-INTERNAL_HEADERS = (PKG / "csrc" / "cat_learn_common.h",)   # what the sources share; not part of the C ABI, but an input of the build
+# what the sources share, and the navigation kernels of cat_render.hip; not part of the C ABI, but inputs of the build
+INTERNAL_HEADERS = (PKG / "csrc" / "cat_learn_common.h", PKG / "csrc" / "cat_render_nav.h")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared"]
 HIDDEN = 128
 
@@ -40,7 +41,7 @@ MODULES = {
                       "cat_dense_dgrad": _ENTRY, "cat_dense_sum_chunks2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])}),
     "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY, "cat_rollout_scripted": _ENTRY}),
     "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]), "cat_render_positions_update": _ENTRY,
-                        "cat_render_positions_ends_update": _ENTRY}),
+                        "cat_render_positions_ends_update": _ENTRY, "cat_render_nav_build": _ENTRY, "cat_render_nav_step": _ENTRY}),
     "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
                          "cat_episodes_segment_summary": _ENTRY}),
     "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_collect_step": _ENTRY, "cat_act_league_step": _ENTRY}),
@@ -995,6 +996,90 @@ def positions_ends_update(final_positions, terminated, truncated, group, quota, 
 def positions_ends_launch(a: PositionsEndsArgs) -> None:
     """One launch of ``cat_render_positions_ends_update`` with an argument block ``positions_ends_update`` has checked."""
     _check(lib().cat_render_positions_ends_update(C.byref(a), _stream()), "cat_render_positions_ends_update")
+
+
+# ---------------------------------------------------------------------------------------------- navigation (pursue / flee)
+NAV_MAX_CELLS, NAV_MAX_MAPS, NAV_NONE = 4096, 16, 0xFFFF        # CAT_NAV_MAX_CELLS / _MAX_MAPS / _NONE
+NAV_MAX_NAVIGATORS, NAV_MAX_SEGMENTS = 8, 32                    # CAT_NAV_MAX_NAVIGATORS / _MAX_SEGMENTS
+NAV_PURSUE, NAV_FLEE = 0, 1                                     # CAT_NAV_PURSUE / CAT_NAV_FLEE; -1: leaves the column alone
+
+
+class NavBuildArgs(C.Structure):
+    """include/cat_render.h cat_render_nav_build_args."""
+    _fields_ = [("n_maps", C.c_int32), ("pad", C.c_int32), ("grid_host", C.c_void_p), ("grid", C.c_void_p), ("free", C.c_void_p), ("hops", C.c_void_p)]
+
+
+class NavStepArgs(C.Structure):
+    """include/cat_render.h cat_render_nav_step_args."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("G", C.c_int32), ("S", C.c_int32), ("n_maps", C.c_int32), ("cell", C.c_int32),
+                ("agent", C.c_int32 * NAV_MAX_NAVIGATORS), ("opp_mask", C.c_uint32 * NAV_MAX_NAVIGATORS),
+                ("seg_start", C.c_int32 * (NAV_MAX_SEGMENTS + 1)), ("pad", C.c_int32),
+                ("seg_script", (C.c_int32 * NAV_MAX_SEGMENTS) * NAV_MAX_NAVIGATORS),
+                ("grid", C.c_void_p), ("free", C.c_void_p), ("snap", C.c_void_p), ("hops", C.c_void_p), ("slot_map", C.c_void_p),
+                ("team_positions", C.c_void_p), ("uniform", C.c_void_p), ("actions", C.c_void_p), ("nav_hops", C.c_void_p)]
+
+
+def nav_build(grid_host, grid, free, hops) -> None:
+    """The all-pairs hop table of a batch of map grids in one launch (``cat_render_nav_build``): ``grid_host`` int32 [M, 4] NumPy (Wc, Hc,
+    cell_off, hops_off), ``grid`` the same on the device, ``free`` uint8 [sum C], ``hops`` uint16 / int16 [sum C^2] (written)."""
+    import numpy as np
+    import torch
+    M = grid_host.shape[0]
+    assert grid_host.dtype == np.int32 and grid_host.shape == (M, 4) and grid_host.flags.c_contiguous
+    assert grid.dtype == torch.int32 and tuple(grid.shape) == (M, 4) and grid.is_contiguous()
+    cells = int((grid_host[:, 0].astype(np.int64) * grid_host[:, 1]).sum())
+    entries = int(((grid_host[:, 0].astype(np.int64) * grid_host[:, 1]) ** 2).sum())
+    assert free.dtype == torch.uint8 and free.numel() == cells and free.is_contiguous()
+    assert hops.element_size() == 2 and hops.numel() == entries and hops.is_contiguous()
+    assert grid.device == free.device == hops.device
+    a = NavBuildArgs(M, 0, grid_host.ctypes.data, grid.data_ptr(), free.data_ptr(), hops.data_ptr())
+    _check(lib().cat_render_nav_build(C.byref(a), _stream()), "cat_render_nav_build")
+
+
+class NavTable:
+    """A checked segment table of ``cat_render_nav_step_args`` in the C struct's own arrays (``nav_table`` makes it)."""
+
+    def __init__(self, S: int, start, rows):
+        self.S, self.start, self.rows = S, start, rows
+        self.seg_start = (C.c_int32 * (NAV_MAX_SEGMENTS + 1))(*start)
+        self.seg_script = ((C.c_int32 * NAV_MAX_SEGMENTS) * NAV_MAX_NAVIGATORS)(*[(C.c_int32 * NAV_MAX_SEGMENTS)(*row) for row in rows])
+
+
+def nav_table(N: int, G: int, bounds, rows) -> NavTable:
+    """The segment table of ``cat_render_nav_step_args`` checked by the C entry's rules: ``bounds`` S + 1 row bounds (``_check_bounds``),
+    ``rows`` [G][S] scripts in {-1, NAV_PURSUE, NAV_FLEE}.  Raises ValueError."""
+    start = [int(v) for v in bounds]
+    _check_bounds(N, start, NAV_MAX_SEGMENTS)
+    S = len(start) - 1
+    table = [[int(v) for v in row] for row in rows]
+    if not 1 <= G <= NAV_MAX_NAVIGATORS or len(table) != G or any(len(row) != S for row in table):
+        raise ValueError(f"the scripts must be [{G}][{S}] with 1 <= G <= {NAV_MAX_NAVIGATORS}")
+    if any(v not in (-1, NAV_PURSUE, NAV_FLEE) for row in table for v in row):
+        raise ValueError("a script outside {-1, 0, 1}")
+    return NavTable(S, start, table)
+
+
+def nav_step(team_positions, uniform, field, agent_indices, opp_masks, table, actions, nav_hops=None) -> None:
+    """One tick of the navigators in one launch (``cat_render_nav_step``): team_positions f16 [N, A, 2], uniform fp32 [G, N], ``field`` with
+    the device tensors grid / free / snap / hops / slot_map of ``navigation.NavField`` and its ``cell``, ``table`` a ``NavTable`` for these N
+    and G; actions int32 [N, A]: column ``agent_indices[g]`` receives navigator g's action where its script is not -1; nav_hops int32
+    [G, N] or None."""
+    import torch
+    N, A, _ = team_positions.shape
+    G = len(agent_indices)
+    assert team_positions.dtype == torch.float16 and team_positions.shape == (N, A, 2) and team_positions.is_contiguous()
+    assert isinstance(table, NavTable) and table.start[-1] == N and len(table.rows) == G == len(opp_masks)
+    assert uniform.dtype == torch.float32 and uniform.shape == (G, N) and uniform.is_contiguous()
+    assert actions.dtype == torch.int32 and actions.shape == (N, A) and actions.is_contiguous()
+    assert nav_hops is None or (nav_hops.dtype == torch.int32 and nav_hops.shape == (G, N) and nav_hops.is_contiguous())
+    assert field.slot_map.dtype == torch.int32 and field.slot_map.shape == (N,) and field.slot_map.is_contiguous()
+    assert all(t.device == actions.device for t in (team_positions, uniform, field.grid, field.free, field.snap, field.hops, field.slot_map))
+    pad = [0] * (NAV_MAX_NAVIGATORS - G)
+    a = NavStepArgs(N, A, G, table.S, field.grid.shape[0], int(field.cell), (C.c_int32 * NAV_MAX_NAVIGATORS)(*agent_indices, *pad),
+                    (C.c_uint32 * NAV_MAX_NAVIGATORS)(*opp_masks, *pad), table.seg_start, 0, table.seg_script,
+                    field.grid.data_ptr(), field.free.data_ptr(), field.snap.data_ptr(), field.hops.data_ptr(), field.slot_map.data_ptr(),
+                    team_positions.data_ptr(), uniform.data_ptr(), actions.data_ptr(), _ptr(nav_hops))
+    _check(lib().cat_render_nav_step(C.byref(a), _stream()), "cat_render_nav_step")
 
 
 # ---------------------------------------------------------------------------------------------- scripted opponents

@@ -16,6 +16,7 @@
 
 #include "cat_learn_common.h"
 #include "cat_render.h"
+#include "cat_render_nav.h"
 
 namespace {
 
@@ -488,6 +489,54 @@ extern "C" int cat_render_positions_ends_update(const cat_render_positions_ends_
     const long blocks = ((long)a->N + spw - 1) / spw;
     hipLaunchKernelGGL(positions_ends_kernel, dim3((unsigned)blocks), dim3(PBLOCK), 0, (hipStream_t)stream, *a, spw);
     return launched("cat_render_positions_ends_update");
+}
+
+// ---- navigation (include/cat_render.h; the kernels are in cat_render_nav.h)
+extern "C" int cat_render_nav_build(const cat_render_nav_build_args *a, void *stream)
+{
+    if (!a) return nbfail("NULL arguments");
+    if (a->n_maps < 1 || a->n_maps > CAT_NAV_MAX_MAPS) return nbfail("n_maps must lie in 1 .. 16");
+    if (!a->grid_host || !a->grid) return nbfail("the grid table is NULL (host or device)");
+    if (!a->free || !a->hops) return nbfail("a required buffer is NULL");
+    if ((uintptr_t)a->hops & 1) return nbfail("hops must be 2-byte aligned");
+    long cells = 0, entries = 0;
+    for (int m = 0; m < a->n_maps; ++m) {
+        const int32_t *g = a->grid_host + 4 * m;
+        if (g[0] < 1 || g[1] < 1) return nbfail("a grid needs Wc >= 1 and Hc >= 1");
+        const long C = (long)g[0] * g[1];
+        if (C > CAT_NAV_MAX_CELLS) return nbfail("a grid has more than 4096 cells");
+        if (g[2] != cells || g[3] != entries) return nbfail("the offsets must be those of the maps concatenated in order");
+        cells += C;
+        entries += C * C;
+    }
+    hipLaunchKernelGGL(nav_build_kernel, dim3((unsigned)cells), dim3(NAV_BLOCK), 0, (hipStream_t)stream, *a);
+    return launched("cat_render_nav_build");
+}
+
+extern "C" int cat_render_nav_step(const cat_render_nav_step_args *a, void *stream)
+{
+    if (!a) return nsfail("NULL arguments");
+    if (a->N <= 0 || a->A <= 0 || a->A > CAT_RENDER_MAX_AGENTS) return nsfail("bad dimensions");
+    if (a->G < 1 || a->G > CAT_NAV_MAX_NAVIGATORS) return nsfail("G must lie in 1 .. 8");
+    if (a->S < 1 || a->S > CAT_NAV_MAX_SEGMENTS) return nsfail("S must lie in 1 .. 32");
+    if (a->n_maps < 1 || a->n_maps > CAT_NAV_MAX_MAPS) return nsfail("n_maps must lie in 1 .. 16");
+    if (a->cell < 1) return nsfail("cell must be >= 1");
+    if (!agents_ok(a->agent, a->G, a->A)) return nsfail("an agent index outside [0, A)");
+    for (int g = 0; g < a->G; ++g)
+        if ((a->A < 32 && (a->opp_mask[g] >> a->A)) || ((a->opp_mask[g] >> a->agent[g]) & 1u))
+            return nsfail("opp_mask names an agent outside [0, A) or the navigator itself");
+    if (a->seg_start[0] != 0) return nsfail("the segments must begin at 0");
+    if (a->seg_start[a->S] != a->N) return nsfail("the segments must end at N");
+    for (int s = 0; s < a->S; ++s)
+        if (a->seg_start[s + 1] <= a->seg_start[s]) return nsfail("segment bounds must be strictly increasing");
+    for (int g = 0; g < a->G; ++g)
+        for (int s = 0; s < a->S; ++s)
+            if (a->seg_script[g][s] < -1 || a->seg_script[g][s] > CAT_NAV_FLEE) return nsfail("a script outside {-1, 0, 1}");
+    if (!a->grid || !a->free || !a->snap || !a->hops) return nsfail("a table of the field is NULL");
+    if (!a->team_positions || !a->uniform || !a->actions) return nsfail("a required buffer is NULL");
+    if ((uintptr_t)a->team_positions & 3) return nsfail("team_positions must be 4-byte aligned");
+    hipLaunchKernelGGL(nav_step_kernel, dim3((unsigned)((a->N + NAV_BLOCK - 1) / NAV_BLOCK), (unsigned)a->G), dim3(NAV_BLOCK), 0, (hipStream_t)stream, *a);
+    return launched("cat_render_nav_step");
 }
 
 extern "C" int cat_render_abi_version(void) { return CAT_RENDER_ABI_VERSION; }

@@ -1,0 +1,329 @@
+"""Shortest paths around the walls: a grid over each map, the all-pairs hop table on it, and the rule by which the PRIVILEGED yardstick
+opponents ``"pursue"`` and ``"flee"`` (``selfplay/navigators.py``) move.  Privileged: they read ``team_positions`` and the map, which no
+policy observes; they measure how far a cop or a thief is from one that knows the maze, and are no training target to imitate.
+
+    field = NavField.from_env(env)                  # host tables per compiled map; on a GPU one launch of cat_render_nav_build
+    action, hops = navigate_step(env.raw_outputs()["team_positions"], u, field, [0, 1], [0, 0], [0b100, 0b100])
+
+This module IS the definition: ``free_cells`` / ``snap_cells`` / ``hops_reference`` (NumPy) of the tables and ``navigate_step`` (torch, any
+device) of the tick.  ``cat_render_nav_build`` and ``cat_render_nav_step`` (include/cat_render.h) equal them exactly: every value is an
+integer.
+
+The grid of a map with window W x H: ``Wc = ceil(W / cell)``, ``Hc = ceil(H / cell)`` cells, cell (ix, iy) at index ``k = ix * Hc + iy``
+(x-major, like ``positions.PositionTracker``), ``C = Wc * Hc <= MAX_CELLS``.
+
+* ``free[k]``: the cell's centre ((ix + .5) cell, (iy + .5) cell) lies at least ``clearance`` inside the window on all four sides, outside
+  every hull, and farther than ``clearance`` from every hull's boundary.  With ``clearance = agent_radius + wall_radius`` an agent's centre
+  can stand there.
+* ``snap[k]``: k for a free cell; for a blocked one the free cell with the smallest squared centre distance within Chebyshev distance 2
+  (the lowest index on ties), ``NONE`` if there is none -- an agent in contact with a wall can stand in a cell whose centre is blocked.
+* ``hops[goal][k]``: 4-connected steps over free cells, ``NONE`` where either is blocked or no path exists.
+
+The tick, per row = (navigator g, env n) -- actions 0 = -x, 1 = +y, 2 = +x, 3 = -y as in ``selfplay/scripted.py``:
+
+* the cell of a position (x, y) (f16): both finite, x >= 0, y >= 0, ix = int(floor(x)) // cell < Wc, iy = int(floor(y)) // cell < Hc, then
+  ``snap[ix * Hc + iy]``; ``NONE`` is no cell.  a = the row's own cell, b_j the cells of its opponents j.
+* target: among the opponents with a cell and ``hops[b_j][a] != NONE`` the smallest key ``(hops[b_j][a] << 8) | j``; d its hop count.
+* fallback: no own cell, no target, or none of a's four neighbours usable (on the grid and free): ``min(3, int(4 u))``, ``nav_hops = -1``.
+* pref: D = target position - own position (fp32); the x axis if |D.x| >= |D.y| else y; on x 2 if D.x >= 0 else 0, on y 1 if D.y >= 0 else 3.
+* pursue: d == 0 -> pref.  Otherwise the usable neighbours with the smallest ``hops[b][nb_i]`` (one has d - 1): pref if it is one of them,
+  else the lowest action.
+* flee: per usable neighbour m_i = min and t_i = sum over ALL opponents with a cell of ``hops[b_j][nb_i]`` (``NONE`` counts as 65535: an
+  unreachable threat is none): the largest m_i, then the largest t_i, then the lowest action.
+* ``nav_hops`` = d: the geodesic separation of the row from its nearest opponent.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+MAX_CELLS = 4096        # CAT_NAV_MAX_CELLS
+MAX_MAPS = 16           # CAT_NAV_MAX_MAPS
+NONE = 0xFFFF           # CAT_NAV_NONE
+PURSUE, FLEE = 0, 1     # CAT_NAV_PURSUE / CAT_NAV_FLEE
+
+
+def grid_shape(window, cell: int) -> Tuple[int, int]:
+    """(Wc, Hc) of a window (W, H) at ``cell`` pixels per cell; ValueError above ``MAX_CELLS`` cells."""
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or cell < 1:
+        raise ValueError(f"cell is the cell size in pixels, an integer >= 1, got {cell!r}")
+    Wc, Hc = max(1, math.ceil(float(window[0]) / cell)), max(1, math.ceil(float(window[1]) / cell))
+    if Wc * Hc > MAX_CELLS:
+        raise ValueError(f"a {Wc} x {Hc} grid has more than {MAX_CELLS} cells: choose a larger cell than {cell}")
+    return Wc, Hc
+
+
+def hull_distance(cmap, points: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """For points float64 [P, 2]: (inside [P] -- inside or on some hull, by its planes; dist [P] -- the smallest Euclidean distance to any
+    hull's boundary, +inf for a map without walls).  Hull vertices are ``planes[:, 2:4]``; edge i of a hull runs from vertex i - 1 to i."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    inside = np.zeros(len(pts), bool)
+    dist = np.full(len(pts), np.inf)
+    for first, count in zip(cmap.shape_first, cmap.shape_count):
+        pl = cmap.planes[first:first + count]
+        inside |= ((pts[:, 0:1] * pl[None, :, 0] + pts[:, 1:2] * pl[None, :, 1] - pl[None, :, 4]) <= 0.0).all(axis=1)
+        b = pl[:, 2:4]
+        a = np.roll(b, 1, axis=0)
+        e = b - a                                                             # [k, 2]
+        w = pts[:, None, :] - a[None]                                         # [P, k, 2]
+        t = np.clip((w * e[None]).sum(-1) / (e * e).sum(-1)[None], 0.0, 1.0)
+        q = w - t[..., None] * e[None]
+        dist = np.minimum(dist, np.sqrt((q * q).sum(-1)).min(axis=1))
+    return inside, dist
+
+
+def free_cells(cmap, cell: int, clearance: float) -> Tuple[np.ndarray, int, int]:
+    """(free uint8 [C], Wc, Hc) of one ``CompiledMap``: the rule of the module docstring."""
+    W, H = float(cmap.window[0]), float(cmap.window[1])
+    Wc, Hc = grid_shape((W, H), cell)
+    cx = (np.repeat(np.arange(Wc), Hc) + 0.5) * cell
+    cy = (np.tile(np.arange(Hc), Wc) + 0.5) * cell
+    inside, dist = hull_distance(cmap, np.stack([cx, cy], axis=1))
+    in_window = (cx >= clearance) & (cx <= W - clearance) & (cy >= clearance) & (cy <= H - clearance)
+    return (in_window & ~inside & (dist > clearance)).astype(np.uint8), Wc, Hc
+
+
+def snap_cells(free: np.ndarray, Wc: int, Hc: int) -> np.ndarray:
+    """snap uint16 [C]: the rule of the module docstring."""
+    f = np.asarray(free).reshape(Wc, Hc) != 0
+    index = np.arange(Wc * Hc, dtype=np.int64).reshape(Wc, Hc)
+    snap = np.where(f, index, NONE)
+    todo = ~f
+    # nearest first; among equally near cells the lowest index = the smallest dx, then the smallest dy
+    offsets = sorted(((dx * dx + dy * dy, dx, dy) for dx in range(-2, 3) for dy in range(-2, 3) if (dx, dy) != (0, 0)))
+    ix, iy = np.meshgrid(np.arange(Wc), np.arange(Hc), indexing="ij")
+    for _, dx, dy in offsets:
+        jx, jy = ix + dx, iy + dy
+        ok = (jx >= 0) & (jx < Wc) & (jy >= 0) & (jy < Hc)
+        hit = todo & ok & f[np.clip(jx, 0, Wc - 1), np.clip(jy, 0, Hc - 1)]
+        snap[hit] = (jx * Hc + jy)[hit]
+        todo &= ~hit
+    return snap.reshape(-1).astype(np.uint16)
+
+
+def hops_reference(free: np.ndarray, Wc: int, Hc: int, goals: Optional[Sequence[int]] = None) -> np.ndarray:
+    """The all-pairs table uint16 [C, C] (or the rows ``goals``): ``hops[goal][k]`` = 4-connected breadth-first steps over free cells,
+    ``NONE`` where goal or k is blocked or unreachable.
+
+    Level-synchronous over boolean arrays, every goal at once: the booleans of one cell over all goals are packed eight to a byte (goal
+    j = bit j % 8 of byte j // 8), so a level is a handful of byte-wise operations on [Wc, Hc, ceil(goals / 8)] arrays.  In level L every
+    unvisited free cell with a 4-neighbour in the frontier takes L + 1, which is written bit by bit into 16 packed planes."""
+    C = Wc * Hc
+    f = np.asarray(free).reshape(Wc, Hc) != 0
+    goals = np.arange(C) if goals is None else np.asarray(goals, dtype=np.int64).reshape(-1)
+    n = len(goals)
+    B = (n + 7) // 8
+    front = np.zeros((Wc, Hc, B), np.uint8)
+    j = np.arange(n)
+    ok = f.reshape(-1)[goals]                                                 # a blocked goal reaches nothing: its row stays NONE
+    np.bitwise_or.at(front, (goals[ok] // Hc, goals[ok] % Hc, j[ok] // 8), (1 << (j[ok] % 8)).astype(np.uint8))
+    open_ = np.where(f, 0xFF, 0).astype(np.uint8)[:, :, None]
+    visited = front.copy()
+    planes = np.zeros((16, Wc, Hc, B), np.uint8)
+    for level in range(1, C + 1):
+        reach = np.zeros_like(front)
+        reach[1:] |= front[:-1]
+        reach[:-1] |= front[1:]
+        reach[:, 1:] |= front[:, :-1]
+        reach[:, :-1] |= front[:, 1:]
+        front = reach & open_ & ~visited
+        if not front.any():
+            break
+        visited |= front
+        for p in range(16):
+            if (level >> p) & 1:
+                planes[p] |= front
+    out = np.zeros((C, n), np.uint16)                                          # [cell, goal]
+    for p in range(16):
+        if planes[p].any():
+            out |= np.unpackbits(planes[p].reshape(C, B), axis=1, bitorder="little")[:, :n].astype(np.uint16) << p
+    out[np.unpackbits(visited.reshape(C, B), axis=1, bitorder="little")[:, :n] == 0] = NONE
+    return np.ascontiguousarray(out.T)
+
+
+def component_sizes(free: np.ndarray, Wc: int, Hc: int) -> List[int]:
+    """Sizes of the 4-connected components of the free cells, largest first."""
+    f = np.asarray(free).reshape(Wc, Hc) != 0
+    label = np.where(f, np.arange(Wc * Hc).reshape(Wc, Hc), -1)
+    while True:                                                                # every free cell takes the largest label it touches
+        big = label.copy()
+        big[1:] = np.maximum(big[1:], label[:-1]); big[:-1] = np.maximum(big[:-1], label[1:])
+        big[:, 1:] = np.maximum(big[:, 1:], label[:, :-1]); big[:, :-1] = np.maximum(big[:, :-1], label[:, 1:])
+        big = np.where(f, big, -1)
+        if np.array_equal(big, label):
+            break
+        label = big
+    return sorted((int(c) for c in np.bincount(label[f]) if c), reverse=True)
+
+
+class NavField:
+    """The tables of a batch of maps, on ``device``.
+
+    ``cell``; ``grid_host`` int32 NumPy [M, 4] = (Wc, Hc, cell_off, hops_off): map m's first element in ``free`` / ``snap`` and in
+    ``hops``; ``grid`` the same as a tensor; ``free`` uint8 [sum C]; ``snap`` and ``hops`` [sum C] / [sum C^2] hold uint16 values in
+    int16 tensors (``& 0xFFFF`` after widening; ``NONE`` reads -1); ``slot_map`` int32 [N].  ``free_of`` / ``snap_of`` / ``hops_of`` give
+    one map's tables as NumPy arrays in their own types."""
+
+    def __init__(self, cell: int, masks: Sequence[Tuple[np.ndarray, int, int]], slot_map, device="cpu"):
+        """``masks``: per map (free uint8 [C], Wc, Hc).  On a GPU the hop table is built there by ``cat_render_nav_build`` (a missing
+        kernel is an error), elsewhere by ``hops_reference``."""
+        if not 1 <= len(masks) <= MAX_MAPS:
+            raise ValueError(f"a field has 1 .. {MAX_MAPS} maps, not {len(masks)}")
+        if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or cell < 1:
+            raise ValueError(f"cell is the cell size in pixels, an integer >= 1, got {cell!r}")
+        self.cell, self.device = int(cell), torch.device(device)
+        rows, cells, entries = [], 0, 0
+        for free, Wc, Hc in masks:
+            C = int(Wc) * int(Hc)
+            if Wc < 1 or Hc < 1 or C > MAX_CELLS or np.asarray(free).size != C:
+                raise ValueError(f"a grid of {Wc} x {Hc} cells with a mask of {np.asarray(free).size}: 1 .. {MAX_CELLS} cells, one mask entry each")
+            rows.append((Wc, Hc, cells, entries))
+            cells, entries = cells + C, entries + C * C
+        self.grid_host = np.array(rows, dtype=np.int32).reshape(len(masks), 4)
+        free_all = np.concatenate([(np.asarray(f).reshape(-1) != 0).astype(np.uint8) for f, _, _ in masks])
+        snap_all = np.concatenate([snap_cells(f, Wc, Hc) for f, Wc, Hc in masks])
+        slot_map = np.asarray(slot_map, dtype=np.int32).reshape(-1)
+        if slot_map.size and (slot_map.min() < 0 or slot_map.max() >= len(masks)):
+            raise ValueError(f"slot_map names a map outside [0, {len(masks)})")
+        self.grid = torch.from_numpy(self.grid_host.copy()).to(self.device)
+        self.free = torch.from_numpy(free_all).to(self.device)
+        self.snap = torch.from_numpy(snap_all.view(np.int16).copy()).to(self.device)
+        self.slot_map = torch.from_numpy(slot_map.copy()).to(self.device)
+        if self.device.type == "cuda":
+            from . import _learn_native
+            self.hops = torch.empty(entries, dtype=torch.int16, device=self.device)
+            with torch.cuda.device(self.device):
+                _learn_native.nav_build(self.grid_host, self.grid, self.free, self.hops)
+        else:
+            self.hops = torch.from_numpy(np.concatenate([hops_reference(f, Wc, Hc).reshape(-1) for f, Wc, Hc in masks]).view(np.int16).copy())
+
+    @classmethod
+    def from_maps(cls, compiled, slot_map, cell: int = 16, clearance: float = 6.0, device="cpu") -> "NavField":
+        """The field of ``CompiledMap``s (``free_cells`` of each)."""
+        return cls(cell, [free_cells(cm, cell, clearance) for cm in compiled], slot_map, device)
+
+    @classmethod
+    def from_env(cls, env, cell: int = 16, clearance: Optional[float] = None) -> "NavField":
+        """The field of ``env``'s compiled maps and slots; ``clearance`` defaults to the env's agent_radius + wall_radius (6.0 with the
+        default physics)."""
+        cfg = env._cfg
+        if clearance is None:
+            clearance = float(cfg.agent_radius) + float(cfg.wall_radius)
+        slot_map = getattr(env, "slot_map_ids", None)
+        if slot_map is None:
+            slot_map = np.zeros(env.num_envs, dtype=np.int32)
+        return cls.from_maps(env._compiled, slot_map, cell, float(clearance), env.device)
+
+    @property
+    def n_maps(self) -> int:
+        return self.grid_host.shape[0]
+
+    def _cells(self, m: int) -> Tuple[int, int, int, int]:
+        Wc, Hc, off, hoff = (int(v) for v in self.grid_host[m])
+        return Wc * Hc, off, hoff, Hc
+
+    def free_of(self, m: int) -> np.ndarray:
+        C, off, _, _ = self._cells(m)
+        return self.free[off:off + C].cpu().numpy()
+
+    def snap_of(self, m: int) -> np.ndarray:
+        C, off, _, _ = self._cells(m)
+        return self.snap[off:off + C].cpu().numpy().view(np.uint16)
+
+    def hops_of(self, m: int) -> np.ndarray:
+        C, _, hoff, _ = self._cells(m)
+        return self.hops[hoff:hoff + C * C].cpu().numpy().view(np.uint16).reshape(C, C)
+
+    def component_sizes(self) -> List[List[int]]:
+        """Per map the sizes of the connected components of its free cells, largest first."""
+        return [component_sizes(self.free_of(m), int(self.grid_host[m, 0]), int(self.grid_host[m, 1])) for m in range(self.n_maps)]
+
+
+@torch.no_grad()
+def navigate_step(team_positions: torch.Tensor, uniform: torch.Tensor, field: NavField, agent_index: Sequence[int], script,
+                  opponent_mask: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The rule of the module docstring: team_positions f16 [N, A, 2], uniform fp32 [G, N], per navigator g its env agent index, its
+    script (an int or an integer tensor [N] per navigator, or one tensor [G, N]: PURSUE, FLEE or -1) and the bitmask of its opponents'
+    agent indices.  Returns (action int32 [G, N], nav_hops int32 [G, N]); both are -1 where the script is -1, and nav_hops is -1 after
+    the fallback.  Nothing is modified."""
+    N, A, _ = team_positions.shape
+    G = len(agent_index)
+    assert team_positions.dtype == torch.float16 and uniform.dtype == torch.float32 and tuple(uniform.shape) == (G, N)
+    dev, i64 = team_positions.device, torch.int64
+    cell, M = field.cell, field.n_maps
+    pos = team_positions.float()                                               # f16 -> fp32 is exact
+    bits = team_positions.view(torch.int16).to(i64) & 0xFFFF
+    finite = ((bits & 0x7C00) != 0x7C00).all(-1)
+    m = field.slot_map.to(dev).to(i64)
+    map_ok = (m >= 0) & (m < M)
+    row = field.grid.to(dev).to(i64)[m.clamp(0, M - 1)]                        # [N, 4]
+    Wc, Hc, coff, hoff = (row[:, c].unsqueeze(1) for c in range(4))            # [N, 1]
+    C = Wc * Hc
+    free, snap, hops = field.free.to(dev), field.snap.to(dev), field.hops.to(dev)
+
+    valid = finite & (pos[..., 0] >= 0) & (pos[..., 1] >= 0) & map_ok.unsqueeze(1)
+    safe = torch.where(valid.unsqueeze(-1), pos, torch.zeros_like(pos))
+    ix, iy = safe[..., 0].floor().to(i64) // cell, safe[..., 1].floor().to(i64) // cell
+    valid = valid & (ix < Wc) & (iy < Hc)
+    s = snap[coff + torch.where(valid, ix * Hc + iy, torch.zeros_like(ix))].to(i64) & 0xFFFF
+    cells = torch.where(valid & (s < C), s, torch.full_like(s, -1))            # [N, A]: the cell of every agent, -1 = none
+
+    def H(b, k):                                                               # hops[b][k] where both are cells, NONE elsewhere
+        ok = (b >= 0) & (k >= 0)
+        per_row = (N,) + (1,) * (ok.dim() - 1)
+        v = hops[hoff.view(per_row) + torch.where(ok, b * C.view(per_row) + k, torch.zeros_like(b + k))].to(i64) & 0xFFFF
+        return torch.where(ok, v, torch.full_like(v, NONE))
+
+    script_t = torch.stack([torch.as_tensor(sc, device=dev).to(i64).expand(N) for sc in script]) if not torch.is_tensor(script) else \
+        script.to(dev).to(i64).expand(G, N)
+    actions, nav = [], []
+    four = torch.arange(4, device=dev)
+    big = 1 << 40
+    for g in range(G):
+        me, opp = int(agent_index[g]), [j for j in range(A) if (int(opponent_mask[g]) >> j) & 1]
+        a = cells[:, me:me + 1]                                                # [N, 1]
+        u = uniform[g]
+        fallback = (4.0 * u).to(i64).clamp(max=3)
+        if not opp:
+            actions.append(fallback); nav.append(torch.full_like(fallback, -1))
+            continue
+        opp_t = torch.tensor(opp, device=dev)
+        b = cells[:, opp_t]                                                    # [N, J]
+        ha = H(b, a)
+        key = torch.where(ha != NONE, (ha << 8) | opp_t, torch.full_like(ha, big))
+        best, arg = key.min(dim=1)                                             # (keys are distinct: the first minimum is the only one)
+        has = best < big
+        d = best >> 8
+        bt = torch.where(has, b.gather(1, arg.unsqueeze(1)).squeeze(1), torch.full_like(d, -1)).unsqueeze(1)
+        delta = pos[:, opp_t].gather(1, arg.view(N, 1, 1).expand(N, 1, 2)).squeeze(1) - pos[:, me]
+        dx, dy = delta[:, 0], delta[:, 1]
+        pref = torch.where(dx.abs() >= dy.abs(), torch.where(dx >= 0, 2, 0), torch.where(dy >= 0, 1, 3))
+        # the four neighbours by action
+        a0 = a.clamp(min=0)
+        aix, aiy = a0 // Hc, a0 % Hc
+        nb = torch.cat([a0 - Hc, a0 + 1, a0 + Hc, a0 - 1], dim=1)               # [N, 4]
+        on = torch.cat([aix > 0, aiy + 1 < Hc, aix + 1 < Wc, aiy > 0], dim=1) & (a >= 0)
+        use = on & (free[coff + torch.where(on, nb, torch.zeros_like(nb))] != 0)
+        nbu = torch.where(use, nb, torch.full_like(nb, -1))
+        # pursue
+        v = torch.where(use, H(bt.expand(N, 4), nbu), torch.full_like(nb, big))
+        at_min = v == v.min(dim=1, keepdim=True).values
+        lowest = torch.where(at_min, four, 4).min(dim=1).values
+        chase = torch.where(at_min.gather(1, pref.unsqueeze(1)).squeeze(1), pref, lowest)
+        chase = torch.where(d == 0, pref, chase)
+        # flee
+        h = H(b.unsqueeze(2).expand(N, len(opp), 4), nbu.unsqueeze(1).expand(N, len(opp), 4))        # [N, J, 4]; NONE where b has no cell
+        has_cell = (b >= 0).unsqueeze(2)
+        lo = h.min(dim=1).values
+        total = torch.where(has_cell, h, torch.zeros_like(h)).sum(dim=1)
+        score = torch.where(use, (lo << 32) | total, torch.full_like(lo, -1))
+        away = torch.where(score == score.max(dim=1, keepdim=True).values, four, 4).min(dim=1).values
+        ok = (a.squeeze(1) >= 0) & has & use.any(dim=1)
+        sc = script_t[g]
+        act = torch.where(ok, torch.where(sc == FLEE, away, chase), fallback)
+        actions.append(torch.where(sc >= 0, act, torch.full_like(act, -1)))
+        nav.append(torch.where((sc >= 0) & ok, d, torch.full_like(d, -1)))
+    return torch.stack(actions).to(torch.int32), torch.stack(nav).to(torch.int32)

@@ -410,6 +410,98 @@ def evaluate_against_scripts(eval_env, source, episodes: int, greedy: bool = Fal
             "timeouts": res["timeouts"], "mean_length": length, "cop_win_rate": [c / episodes for c in res["cop_wins"]], "ticks": res["ticks"]}
 
 
+NAVIGATOR_MATCHUPS = ("cops_vs_flee", "pursue_vs_thieves", "pursue_vs_flee", "pursue_vs_random", "random_vs_flee", "chase_vs_flee", "pursue_vs_evade")
+
+
+@torch.no_grad()
+def evaluate_against_navigators(eval_env, source, episodes: int, greedy: bool = False, frame_skip: int = 1, fused="kernel", actor=None,
+                                cell: int = 16) -> Dict[str, object]:
+    """The PRIVILEGED yardsticks of ``selfplay.navigators`` -- "pursue" cops and "flee" thieves, which read every agent's true position and
+    the map -- against the learned policies, against each other, against "random" and against the scripted "chase" / "evade", in the order
+    of ``NAVIGATOR_MATCHUPS``.  The match-ups are played one after another on ``eval_env`` (``num_envs == episodes``), the first episode of
+    every slot each, by ``evaluate_league``'s rule.  ``source`` as in ``evaluate_against_scripts``; None skips the two learned rows.
+    ``actor``: a ``LeagueActor`` over ``eval_env`` to reuse for the columns that are no navigator's (it needs a set per agent when
+    ``source`` is given).  Returns {"segments": names, "episodes", "cop_wins", "thief_wins", "timeouts", "cop_win_rate", "mean_length",
+    "mean_hops" (lists in match-up order), "ticks"}; ``mean_hops``: the mean of the navigators' ``nav_hops`` -- the hop count of the
+    shortest path to the nearest opponent -- over their rows of the counted ticks that did not fall back (None without such a row)."""
+    from .actor import LeagueActor
+    from .navigators import NavigatorActor
+    from ..navigation import NavField
+    agents = list(eval_env.possible_agents)
+    N = eval_env.num_envs
+    if N != episodes or episodes < 1:
+        raise ValueError(f"evaluate_against_navigators plays {episodes} episodes per match-up: the env must have {episodes} slots, not {N}")
+    sets = len(agents) if source is not None else 1
+    if actor is None:
+        actor = LeagueActor.from_env(eval_env, sets, fused=fused)
+    if actor.sets < sets or list(actor.agents) != agents:
+        raise ValueError(f"the actor must cover {agents} with at least {sets} sets")
+    own = {a: "random" for a in agents}
+    if source is not None:
+        for g, a in enumerate(agents):
+            actor.load_set(g, {a: source.agent_models(a)} if isinstance(source, MAPPOTrainer) else source, a)
+        own = {a: g for g, a in enumerate(agents)}
+    cop = lambda a: a.startswith("cop")
+    sides = {"cops": own, "thieves": own, "random": {a: "random" for a in agents}, "chase": {a: "chase" for a in agents},
+             "evade": {a: "evade" for a in agents}}
+    field = NavField.from_env(eval_env, cell)
+    skip = _skip_kw(frame_skip)
+    dev = actor.device
+    out = {"segments": [], "episodes": [], "cop_wins": [], "thief_wins": [], "timeouts": [], "cop_win_rate": [], "mean_length": [], "mean_hops": [],
+           "ticks": 0}
+    for name in NAVIGATOR_MATCHUPS:
+        cops, thieves = name.split("_vs_")
+        if source is None and (cops == "cops" or thieves == "thieves"):       # the learned rows
+            continue
+        nav = {a: (cops if cop(a) else thieves) for a in agents}
+        nav = {a: v for a, v in nav.items() if v in ("pursue", "flee")}
+        # the league actor plays every column (a navigator's as "random"); the navigators then overwrite theirs
+        actor.set_matchups([(0, N, {a: "random" if a in nav else sides[cops if cop(a) else thieves][a] for a in agents})])
+        navigator = NavigatorActor(eval_env, nav, field=field)
+        obs, _ = eval_env.reset()
+        actor.reset()
+        starts = torch.ones(N, dtype=torch.bool, device=dev)
+        open_ = torch.ones(N, dtype=torch.bool, device=dev)
+        winner = torch.full((N,), -1, dtype=torch.int8, device=dev)
+        timeout = torch.zeros(N, dtype=torch.bool, device=dev)
+        length = torch.zeros(N, dtype=torch.int32, device=dev)
+        played = torch.zeros(N, dtype=torch.int32, device=dev)
+        hop_sum = torch.zeros((), dtype=torch.int64, device=dev)
+        hop_rows = torch.zeros((), dtype=torch.int64, device=dev)
+        ticks = 0
+        for _ in range(eval_env.max_step_count + 2):
+            actions = actor.act(eval_env, starts, obs=obs, **({"greedy": True} if greedy else {}))
+            navigator.act(eval_env, starts, actions=actions)
+            counted = open_.view(1, N) & (navigator.nav_hops >= 0)
+            hop_sum += torch.where(counted, navigator.nav_hops, torch.zeros_like(navigator.nav_hops)).sum()
+            hop_rows += counted.sum()
+            obs, _, terms, truncs, infos = eval_env.step(actions, **skip)
+            ticks += 1
+            done = terms[agents[0]]
+            first = open_ & done
+            winner = torch.where(first, infos["winner"].to(torch.int8), winner)
+            timeout = torch.where(first, truncs[agents[0]], timeout)
+            if skip:
+                played = played + infos["ticks"]
+            length = torch.where(first, played if skip else torch.full_like(length, ticks), length)
+            open_ = open_ & ~done
+            starts = done.clone()
+            if not bool(open_.any()):                   # one host sync per tick, as evaluate_league
+                break
+        w, t = winner.cpu(), timeout.cpu()
+        rows = int(hop_rows)
+        out["segments"].append(name)
+        out["episodes"].append(N)
+        out["cop_wins"].append(int((w == 0).sum()))
+        out["thief_wins"].append(int(((w == 1) & ~t).sum()))
+        out["timeouts"].append(int(((w != 0) & t).sum()))
+        out["cop_win_rate"].append(out["cop_wins"][-1] / N)
+        out["mean_length"].append(float(length.float().mean()))
+        out["mean_hops"].append(int(hop_sum) / rows if rows else None)
+        out["ticks"] += ticks
+    return out
+
+
 def evaluate_agent_league(eval_env, actor, learned: MAPPOTrainer, archives: Dict[str, Path], tc: TrainingConfig, rng: random.Random, log=print,
                           learned_roles: Optional[Tuple[str, ...]] = None, frame_skip: int = 1) -> Dict[str, Dict[str, bool]]:
     """``evaluate_agent`` for the roles in ``learned_roles`` (default: cops, then thieves) in ONE pass of ``evaluate_league``: every newly
@@ -658,7 +750,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   fused_collect: bool = False, value_norm: bool = False, position_stats: Optional[int] = None,
                   lr_schedule: str = "constant", lr_final: Optional[float] = None, lr_kl_target: Optional[float] = None,
                   entropy_final: Optional[float] = None, ratio_clip_final: Optional[float] = None,
-                  baseline_eval: bool = False, baseline_episodes: int = 64) -> Dict[str, object]:
+                  baseline_eval: bool = False, baseline_episodes: int = 64, navigator_eval: bool = False,
+                  navigator_episodes: int = 64) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -703,6 +796,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     "chase" / "evade" opponents of ``scripted.py`` and "random" -- in one ``evaluate_against_scripts`` pass on an env of its own with
     ``4 * baseline_episodes`` slots, and appends the result to ``baselines.json`` of the run directory.  The simultaneous mode only.  Off,
     nothing of it is built and no random number is drawn for it.
+    ``navigator_eval``: the same for the PRIVILEGED navigator yardsticks (``navigators.py``: "pursue" / "flee" read true positions and the
+    map): after every iteration rank 0 runs ``evaluate_against_navigators`` on an env of its own with ``navigator_episodes`` slots and appends
+    the result to ``navigators.json``.  The simultaneous mode only.  Off, nothing of it is built and no random number is drawn for it.
 
     With an initialised ``torch.distributed`` group of W > 1 ranks this is ONE data-parallel job: ``num_envs`` is the TOTAL,
     rank r simulates ``shard_envs(num_envs, r, W)``; the trainer all-reduces its gradient | KL buffer every optimiser step (all
@@ -713,6 +809,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         raise ValueError("league_eval plays through evaluate_league (one poll per tick): it cannot be combined with tracked_eval")
     if baseline_eval and (role_training or baseline_episodes < 1):
         raise ValueError("baseline_eval belongs to the simultaneous loop (not role_training) and needs baseline_episodes >= 1")
+    if navigator_eval and (role_training or navigator_episodes < 1):
+        raise ValueError("navigator_eval belongs to the simultaneous loop (not role_training) and needs navigator_episodes >= 1")
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     chief = rank == 0
@@ -825,6 +923,14 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         baseline_actor = LeagueActor.from_env(baseline_env, len(baseline_env.possible_agents), fused="kernel", compute_bf16=trainer_cfg.compute_bf16,
                                               normalize_inputs=trainer_cfg.normalize_inputs, recurrent=trainer_cfg.recurrent, seed=seed + 3,
                                               device=trainer.device)
+    navigator_env = navigator_actor = None
+    navigator_log = []
+    if navigator_eval and chief:   # the privileged yardsticks (navigators.py): the match-ups one after another on navigator_episodes slots
+        from .actor import LeagueActor
+        navigator_env = eval_factory(navigator_episodes, seed + 7933)
+        navigator_actor = LeagueActor.from_env(navigator_env, len(navigator_env.possible_agents), fused="kernel", compute_bf16=trainer_cfg.compute_bf16,
+                                               normalize_inputs=trainer_cfg.normalize_inputs, recurrent=trainer_cfg.recurrent, seed=seed + 5,
+                                               device=trainer.device)
     rng = random.Random(seed)
     start = 0
     if resume:
@@ -841,6 +947,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     baselines_file = out_dir / "baselines.json"
     if baseline_env is not None and start > 0 and baselines_file.exists():
         baseline_log = json.loads(baselines_file.read_text())
+    navigators_file = out_dir / "navigators.json"
+    if navigator_env is not None and start > 0 and navigators_file.exists():
+        navigator_log = json.loads(navigators_file.read_text())
 
     def finish():
         digest = trainer.param_digest()
@@ -848,6 +957,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         eval_env.close()
         if baseline_env is not None:
             baseline_env.close()
+        if navigator_env is not None:
+            navigator_env.close()
         return {"iterations": history, "param_digest": digest, "archives": {r: str(p) for r, p in arch.items()}, "rank": rank, "world": world,
                 "envs_local": n_local, "env_id_offset": offset}
 
@@ -885,6 +996,11 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                     baseline_log.append(dict({"iteration": it}, **b))
                     baselines_file.write_text(json.dumps(baseline_log, indent=1))
                     log("[self-play] baselines, cop win rate: " + ", ".join(f"{n} {r:.2f}" for n, r in zip(b["segments"], b["cop_win_rate"])))
+                if navigator_env is not None:  # ... and against the privileged pursue / flee navigators: the distance to a map-aware opponent
+                    b = evaluate_against_navigators(navigator_env, trainer, navigator_episodes, frame_skip=trainer_cfg.frame_skip, actor=navigator_actor)
+                    navigator_log.append(dict({"iteration": it}, **b))
+                    navigators_file.write_text(json.dumps(navigator_log, indent=1))
+                    log("[self-play] navigators (privileged), cop win rate: " + ", ".join(f"{n} {r:.2f}" for n, r in zip(b["segments"], b["cop_win_rate"])))
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -998,6 +1114,9 @@ def main() -> None:
     ap.add_argument("--baseline-eval", action="store_true", help="after every iteration play the trained policies against the scripted chase / evade "
                     "opponents and against random ones in one pass (selfplay/scripted.py) and append the result to baselines.json")
     ap.add_argument("--baseline-episodes", type=int, default=64, help="--baseline-eval: episodes per match-up (four match-ups share one env)")
+    ap.add_argument("--navigator-eval", action="store_true", help="after every iteration play the trained policies against the PRIVILEGED pursue / flee "
+                    "navigators (selfplay/navigators.py: they read true positions and the map) and append the result to navigators.json")
+    ap.add_argument("--navigator-episodes", type=int, default=64, help="--navigator-eval: episodes per match-up (the match-ups run one after another)")
     ap.add_argument("--episode-stats", action="store_true", help="account the training episodes on the device: win rate and mean length in "
                     "every iteration's log line, episode_stats.json in --out (with --gpus N: of rank 0's shard)")
     ap.add_argument("--role-training", action="store_true", help="the reference's role-training mode (fictitious play): per iteration a cop phase, then a "
@@ -1050,6 +1169,7 @@ def main() -> None:
                         **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}),
                         **({"position_stats": args.position_stats} if args.position_stats is not None else {}),
                         **({"baseline_eval": True, "baseline_episodes": args.baseline_episodes} if args.baseline_eval else {}),
+                        **({"navigator_eval": True, "navigator_episodes": args.navigator_episodes} if args.navigator_eval else {}),
                         **{k: v for k, v in (("lr_schedule", args.lr_schedule), ("lr_final", args.lr_final), ("lr_kl_target", args.lr_kl_target),
                                              ("entropy_final", args.entropy_final), ("ratio_clip_final", args.clip_final))
                            if v not in (None, "constant")})

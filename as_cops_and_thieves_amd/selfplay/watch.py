@@ -39,8 +39,11 @@ def make_env(map_name: str, envs: int, seed: int = 0, num_rays: int = 64, max_st
 def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, ticks: int = 2000, rays: bool = False, seed: int = 0,
           num_rays: int = 64, max_step_count: int = 2000, n_cops: Optional[int] = None, n_thieves: Optional[int] = None, device=None,
           log=print, fused_act: bool = False, greedy: bool = False, frame_skip: int = 1, heatmap: Optional[int] = None,
-          scripts: Optional[Dict[str, str]] = None) -> Dict[str, object]:
-    """``scripts``: {"cop": "chase"} and / or {"thief": "evade"} -- that role's agents follow the scripted opponent of ``scripted.py``
+          scripts: Optional[Dict[str, str]] = None, navigators: Optional[Dict[str, str]] = None) -> Dict[str, object]:
+    """``navigators``: {"cop": "pursue"} and / or {"thief": "flee"} -- that role's agents follow the PRIVILEGED navigator of
+    ``navigators.py`` (it reads every agent's true position and the map, which no policy sees) instead of their policies; a role takes a
+    script or a navigator, not both.
+    ``scripts``: {"cop": "chase"} and / or {"thief": "evade"} -- that role's agents follow the scripted opponent of ``scripted.py``
     instead of their policies (their action columns are written over the policies' every tick).
     ``heatmap=CELL``: a ``positions.PositionTracker`` on a grid of CELL x CELL pixels is fed every decision's rows of the slots still
     playing (this env does not auto-reset, so the terminal row holds the episode's last position and counts as occupancy, and there is no
@@ -70,6 +73,12 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
         if any(r not in ("cop", "thief") for r in scripts):
             raise ValueError(f"scripts names roles: cop and / or thief, not {sorted(scripts)}")
         scripted = ScriptedActor(env, {a: scripts[a.split("_")[0]] for a in env.possible_agents if a.split("_")[0] in scripts})
+    navigator = None
+    if navigators:
+        from .navigators import NavigatorActor
+        if any(r not in ("cop", "thief") for r in navigators) or any(r in (scripts or {}) for r in navigators):
+            raise ValueError(f"navigators names roles (cop and / or thief) that follow no script, not {sorted(navigators)}")
+        navigator = NavigatorActor(env, {a: navigators[a.split("_")[0]] for a in env.possible_agents if a.split("_")[0] in navigators})
     N = env.num_envs
     W, H = (int(v) for v in env.maps[0].window_dimensions)
     slots = list(range(N))
@@ -104,6 +113,8 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
             _trainer_actions(runner, obs, state, starts, actions, ())     # self_play.evaluate_agents' action selection
         if scripted is not None:
             scripted.act(env, starts, obs=obs, actions=actions)
+        if navigator is not None:
+            navigator.act(env, starts, actions=actions)
         obs, _, terms, _, infos = env.step(actions, **skip)
         starts = torch.zeros_like(starts)
         save(t, open_host)
@@ -128,7 +139,7 @@ def watch(map_name: str, envs: int, out_dir, checkpoint: Optional[str] = None, t
     frames_of = [(length[k] + 1) if ended[k] and not skip else (t + 1) for k in slots]
     result = {"map": map_name, "envs": N, "ticks": ticks, "checkpoint": checkpoint, "seed": seed, "rays": bool(rays),
               **({"fused_act": True, "greedy": bool(greedy)} if fused_act else {}), **({"frame_skip": frame_skip} if skip else {}),
-              **({"scripts": dict(scripts)} if scripts else {}),
+              **({"scripts": dict(scripts)} if scripts else {}), **({"navigators": dict(navigators)} if navigators else {}),
               "slots": [{"env": k, "winner": winner[k], "length": length[k], "terminated": ended[k], "frames": frames_of[k]} for k in slots]}
     (out_dir / "episode.json").write_text(json.dumps(result, indent=1))
     if tracker is not None:
@@ -159,13 +170,23 @@ def main(argv=None) -> int:
                     "grid of CELL x CELL pixels, into heatmaps/ next to the clips")
     ap.add_argument("--script", action="append", default=[], metavar="ROLE=NAME", help="cop=chase or thief=evade: that role follows the scripted "
                     "opponent instead of its policy (may be given once per role)")
+    ap.add_argument("--navigator", action="append", default=[], metavar="ROLE=NAME", help="cop=pursue or thief=flee: that role follows the PRIVILEGED "
+                    "shortest-path navigator (it reads true positions and the map) instead of its policy (may be given once per role)")
     args = ap.parse_args(argv)
+    navigators = {}
+    for item in args.navigator:
+        role, _, name = item.partition("=")
+        if (role, name) not in (("cop", "pursue"), ("thief", "flee")):
+            ap.error(f"--navigator takes cop=pursue or thief=flee, not {item!r}")
+        navigators[role] = name
     scripts = {}
     for item in args.script:
         role, _, name = item.partition("=")
         if role not in ("cop", "thief") or name not in ("chase", "evade"):
             ap.error(f"--script takes cop=chase, cop=evade, thief=chase or thief=evade, not {item!r}")
         scripts[role] = name
+    if set(scripts) & set(navigators):
+        ap.error("a role follows a --script or a --navigator, not both")
     if args.heatmap is not None and args.heatmap < 1:
         ap.error("--heatmap must be >= 1")
     if args.envs < 1 or args.ticks < 1 or args.frame_skip < 1:
@@ -173,7 +194,7 @@ def main(argv=None) -> int:
     if args.greedy and not args.fused_act:
         ap.error("--greedy needs --fused-act")
     watch(args.map, args.envs, args.out, args.checkpoint, args.ticks, args.rays, args.seed, args.num_rays, args.max_steps,
-          fused_act=args.fused_act, greedy=args.greedy, frame_skip=args.frame_skip, heatmap=args.heatmap, scripts=scripts or None)
+          fused_act=args.fused_act, greedy=args.greedy, frame_skip=args.frame_skip, heatmap=args.heatmap, scripts=scripts or None, navigators=navigators or None)
     return 0
 
 

@@ -154,6 +154,83 @@ typedef struct cat_render_positions_ends_args {
 /* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
 int cat_render_positions_ends_update(const cat_render_positions_ends_args *a, void *stream);
 
+/*
+ * Navigation: shortest paths around the walls, for the PRIVILEGED yardstick opponents "pursue" and "flee" (selfplay/navigators.py), which
+ * read team_positions and the map -- information no policy sees -- and for geodesic separation as a metric.  navigation.py (NumPy / torch)
+ * defines every number: hops_reference the table, navigate_step the tick.
+ *
+ * The field of a batch of M <= CAT_NAV_MAX_MAPS maps.  Map m has a grid of Wc x Hc cells of cell x cell pixels, C = Wc * Hc <=
+ * CAT_NAV_MAX_CELLS, cell (ix, iy) at index k = ix * Hc + iy (x-major, like the position statistics).
+ *   grid [M][4] int32: Wc, Hc, cell_off, hops_off -- map m's first element in the per-cell arrays (free, snap) and in hops.  hops_off is
+ *     the plain ELEMENT offset: M * C^2 <= 16 * 4096^2 = 2^28 fits an int32, so no scaled offset and no 64-bit table beside it is needed.
+ *   free [sum C] uint8: 1 = an agent's centre may stand on the cell's centre.
+ *   snap [sum C] uint16: a free cell is its own; a blocked one names the nearest free cell within two rings, or CAT_NAV_NONE.
+ *   hops [sum C^2] uint16: hops[hops_off + goal * C + k] = 4-connected steps over free cells from k to goal; CAT_NAV_NONE where goal or k
+ *     is blocked or no path exists.  Symmetric.
+ *
+ * cat_render_nav_build fills hops from free: one workgroup of 256 threads per (map, goal), the goal's row in LDS (C uint16 <= 8 KiB),
+ * level-synchronous sweeps (in level L every unvisited free cell with a 4-neighbour at distance L takes L + 1) until a level changes
+ * nothing, then the row goes out in coalesced 16-bit stores.  No global atomics, no waiting between workgroups, no allocation: capturable.
+ */
+#define CAT_NAV_MAX_CELLS 4096
+#define CAT_NAV_MAX_MAPS 16
+#define CAT_NAV_NONE 0xFFFF
+#define CAT_NAV_MAX_NAVIGATORS 8
+#define CAT_NAV_MAX_SEGMENTS 32      /* = CAT_ROLLOUT_MAX_SEGMENTS */
+#define CAT_NAV_PURSUE 0
+#define CAT_NAV_FLEE 1
+
+typedef struct cat_render_nav_build_args {
+    int32_t n_maps, pad;            /* 1 .. CAT_NAV_MAX_MAPS */
+    const int32_t *grid_host;       /* HOST [n_maps][4] (argument checks and the launch size) */
+    const int32_t *grid;            /* [n_maps][4] the same values on the device */
+    const uint8_t *free;            /* [sum C] */
+    uint16_t *hops;                 /* [sum C^2], 2-byte aligned */
+} cat_render_nav_build_args;
+
+/* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
+int cat_render_nav_build(const cat_render_nav_build_args *a, void *stream);
+
+/*
+ * One tick of G <= CAT_NAV_MAX_NAVIGATORS navigators over N slots in ONE launch: a thread per row (navigator g, slot n), workgroups of 256,
+ * no LDS, no atomics, no allocation (capturable).  Actions as in cat_rollout_scripted: 0 = -x, 1 = +y, 2 = +x, 3 = -y.
+ *
+ *   script = seg_script[g][s] for the segment s with seg_start[s] <= n < seg_start[s + 1]; -1: the row touches nothing.
+ *   Map m = slot_map[n] (0 where slot_map is NULL).  The cell of a position (x, y), the two f16 values of team_positions[n][j]: both
+ *   finite, x >= 0, y >= 0, ix = (int)floor(x) / cell < Wc, iy = (int)floor(y) / cell < Hc, then snap[ix * Hc + iy]; CAT_NAV_NONE is no cell.
+ *   a = the cell of agent[g]; the opponents j are the bits of opp_mask[g], b_j their cells; H(b, k) = hops[b][k].
+ *   Target: among the opponents with a cell and H(b_j, a) != CAT_NAV_NONE the smallest key (H(b_j, a) << 8) | j; d = its H, b = its cell.
+ *   Fallback: no a, no target, or none of a's four neighbours usable (on the grid and free): action = min(3, (int)(4 u)), nav_hops = -1.
+ *   pref: with D = target position - own position in fp32, the x axis if |D.x| >= |D.y| else y; on x: 2 if D.x >= 0 else 0, on y: 1 if
+ *   D.y >= 0 else 3.
+ *   Pursue: d == 0 (one cell): pref.  Otherwise, over the usable neighbours nb_i (i = the action that leads there) the minimum of
+ *   H(b, nb_i); among those that reach it pref if it is one of them, else the lowest i.
+ *   Flee: m_i = min and t_i = sum (int32) over ALL opponents with a cell of H(b_j, nb_i), CAT_NAV_NONE counting as 65535; the largest m_i,
+ *   then the largest t_i, then the lowest i.
+ *   actions[n][agent[g]] = the action; nav_hops[g][n] (where given) = d, or -1 after the fallback.
+ */
+typedef struct cat_render_nav_step_args {
+    int32_t N, A, G, S;             /* slots, agents (<= CAT_RENDER_MAX_AGENTS), navigators, segments (1 .. CAT_NAV_MAX_SEGMENTS) */
+    int32_t n_maps, cell;           /* maps of the field (1 .. CAT_NAV_MAX_MAPS), cell size in pixels (>= 1) */
+    int32_t agent[CAT_NAV_MAX_NAVIGATORS];       /* navigator g's column of team_positions / actions */
+    uint32_t opp_mask[CAT_NAV_MAX_NAVIGATORS];   /* bit j: agent j is an opponent of navigator g (not agent[g] itself, j < A) */
+    int32_t seg_start[CAT_NAV_MAX_SEGMENTS + 1]; /* seg_start[0] = 0 < ... < seg_start[S] = N */
+    int32_t pad;
+    int32_t seg_script[CAT_NAV_MAX_NAVIGATORS][CAT_NAV_MAX_SEGMENTS];   /* CAT_NAV_PURSUE, CAT_NAV_FLEE or -1 */
+    const int32_t *grid;            /* [n_maps][4] */
+    const uint8_t *free;            /* [sum C] */
+    const uint16_t *snap;           /* [sum C] */
+    const uint16_t *hops;           /* [sum C^2] */
+    const int32_t *slot_map;        /* [N] map of slot n, or NULL = map 0 */
+    const uint16_t *team_positions; /* [N][A][2] float16 bits (cat_outputs.team_positions), 4-byte aligned */
+    const float *uniform;           /* [G][N] in [0, 1) */
+    int32_t *actions;               /* [N][A]; only column agent[g] of rows with a script is written */
+    int32_t *nav_hops;              /* [G][N] or NULL; rows of -1 segments are not written */
+} cat_render_nav_step_args;
+
+/* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
+int cat_render_nav_step(const cat_render_nav_step_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
