@@ -1,6 +1,8 @@
 """Exact known-answer data for the learner kernels (csrc/cat_{dense,trunk,ppo,rollout}.hip): operand generators, fp64
 references, the exactness premises and the comparison helpers.  Used by tests/test_gpu_learner_exact.py (on the GPU) and
-tests/test_learner_exact_host.py (the premises and the helpers' teeth, on the CPU).
+tests/test_learner_exact_host.py (the premises and the helpers' teeth, on the CPU).  The LSTM window kernels (csrc/cat_lstm.hip)
+have their exact cases in tests/lstm_exact.py (a saturating network forward, fabricated saved buffers backward), the fused act tick
+(csrc/cat_act.hip) in tests/act_exact.py; ``lstm_reference`` and ``row_k`` below serve the bounded per-row test of long chains.
 
 The idea: with small integer operands every bf16 product is exact, every fp32 partial sum is an integer below 2^24 (so
 exact in ANY summation order and split), and every intermediate a kernel rounds to bf16 is an integer of magnitude

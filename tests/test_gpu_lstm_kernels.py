@@ -169,13 +169,19 @@ LSTM_K = {"out": 2.5, "d_xproj": 8.0, "d_h0": 6.0, "d_c0": 6.0}
 
 
 @pytest.mark.parametrize("B", [1, 17, 8192])
-def test_per_row_errors_stay_within_k_bf16_ulps_of_the_row_scale(B):
+def test_per_row_errors_stay_within_k_bf16_ulps_of_the_row_scale(B, monkeypatch):
     """out, d_xproj, d_h0 and d_c0 against the fp64 recurrence from the same bf16 inputs, ROW by row ((g, t, b) or (g, b)):
     max |err| of a row <= k 2^-8 max |row of the reference| + 2^-12 max |tensor| (tests/learner_exact.row_k).  A per-tensor
     relative error hides a single wrong (t, b); this does not (tests/test_learner_exact_host.py shows it on the CPU).
     G = 3, T = 16; B = 1, 17 and the trainer's 8192 cover both fold paths.  Keep: every other sequence restarts at t = 0,
-    every sequence at t = 9, and 20 % at random.  Calibrated k: LSTM_K (observed worst case beside it)."""
+    every sequence at t = 9, and 20 % at random.  Calibrated k: LSTM_K (observed worst case beside it).
+
+    The bias-sum identity, on the same run: a bias is passed, so backward also leaves the per-block fp32 sums ``part`` of the bias
+    gradient.  part[g, blk] must equal the sum over t and the block's valid rows of the kernel's OWN bf16 d_xproj, to the fp32
+    accumulation bound of its 16 T addends, 16 T 2^-24 sum |addends| -- derived, not calibrated.  At B = 8192 one row left out of
+    the sum is one among 131 072: no per-tensor tolerance sees it, this does."""
     import torch
+    from as_cops_and_thieves_amd import _learn_native
     from as_cops_and_thieves_amd.selfplay.stacked import _LSTMSeq
     from tests import learner_exact as lx
     G, T = 3, 16
@@ -185,11 +191,20 @@ def test_per_row_errors_stay_within_k_bf16_ulps_of_the_row_scale(B):
     gen = torch.Generator(device="cuda").manual_seed(B)
     r_out = torch.randn(G, T, B, H, generator=gen, device="cuda")
     r_h, r_c = torch.randn(G, B, H, generator=gen, device="cuda"), torch.randn(G, B, H, generator=gen, device="cuda")
+    bias = (0.3 * torch.randn(G, 4 * H, generator=gen, device="cuda")).to(torch.bfloat16)
     leaves = [t.detach().clone().requires_grad_(True) for t in (xproj, w_hh, h0, c0)]
-    out, hT, cT = _LSTMSeq.apply(leaves[0], leaves[1], None, None, leaves[2], leaves[3], keep)
+    b_leaf = bias.detach().clone().requires_grad_(True)
+    parts, native_backward = [], _learn_native.seq_backward
+
+    def recording_backward(*args, **kwargs):
+        res = native_backward(*args, **kwargs)
+        parts.append(res)
+        return res
+    monkeypatch.setattr(_learn_native, "seq_backward", recording_backward)
+    out, hT, cT = _LSTMSeq.apply(leaves[0], leaves[1], b_leaf, None, leaves[2], leaves[3], keep)
     ((out.float() * r_out).sum() + (hT.float() * r_h).sum() + (cT.float() * r_c).sum()).backward()
     ref = [t.detach().double().clone().requires_grad_(True) for t in (xproj, w_hh, h0, c0)]
-    ro, rh, rc = lx.lstm_reference(*ref, keep.double())
+    ro, rh, rc = lx.lstm_reference(ref[0] + bias.double().view(G, 1, 1, -1), *ref[1:], keep.double())
     ((ro * r_out.double()).sum() + (rh * r_h.double()).sum() + (rc * r_c.double()).sum()).backward()
     torch.cuda.synchronize()
     ks = {"out": lx.row_k(out.detach(), ro.detach()), "d_xproj": lx.row_k(leaves[0].grad, ref[0].grad),
@@ -197,3 +212,16 @@ def test_per_row_errors_stay_within_k_bf16_ulps_of_the_row_scale(B):
     print("per-row k", B, ks)
     for name, k in ks.items():
         assert k <= LSTM_K[name], (name, k, ks)
+
+    assert len(parts) == 1
+    d_x, part = parts[0][0], parts[0][3]
+    nb = (B + 15) // 16
+    assert part is not None and part.dtype == torch.float32 and part.shape == (G, nb, 4 * H) and torch.equal(d_x, leaves[0].grad)
+    rows = torch.zeros(G, T, nb * 16, 4 * H, dtype=torch.float64, device="cuda")
+    rows[:, :, :B] = d_x.double()
+    rows = rows.view(G, T, nb, 16, 4 * H)
+    want, bound = rows.sum((1, 3)), 16 * T * 2.0 ** -24 * rows.abs().sum((1, 3))
+    err = (part.double() - want).abs()
+    print("bias-sum identity", B, "max err", float(err.max()), "max err / bound", float((err / bound.clamp_min(1e-300)).max()))
+    assert bool((err <= bound).all()), float((err - bound).max())
+    assert float(b_leaf.grad.double().abs().max()) > 0
