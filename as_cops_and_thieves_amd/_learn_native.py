@@ -41,7 +41,8 @@ MODULES = {
                       "cat_dense_dgrad": _ENTRY, "cat_dense_sum_chunks2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])}),
     "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY, "cat_rollout_scripted": _ENTRY}),
     "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]), "cat_render_positions_update": _ENTRY,
-                        "cat_render_positions_ends_update": _ENTRY, "cat_render_nav_build": _ENTRY, "cat_render_nav_step": _ENTRY}),
+                        "cat_render_positions_ends_update": _ENTRY, "cat_render_nav_build": _ENTRY, "cat_render_nav_step": _ENTRY,
+                        "cat_render_nav_shape": _ENTRY}),
     "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
                          "cat_episodes_segment_summary": _ENTRY}),
     "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_collect_step": _ENTRY, "cat_act_league_step": _ENTRY}),
@@ -1080,6 +1081,60 @@ def nav_step(team_positions, uniform, field, agent_indices, opp_masks, table, ac
                     field.grid.data_ptr(), field.free.data_ptr(), field.snap.data_ptr(), field.hops.data_ptr(), field.slot_map.data_ptr(),
                     team_positions.data_ptr(), uniform.data_ptr(), actions.data_ptr(), _ptr(nav_hops))
     _check(lib().cat_render_nav_step(C.byref(a), _stream()), "cat_render_nav_step")
+
+
+class NavShapeArgs(C.Structure):
+    """include/cat_render.h cat_render_nav_shape_args."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("G", C.c_int32), ("n_maps", C.c_int32), ("cell", C.c_int32), ("cap", C.c_int32),
+                ("prime", C.c_int32), ("pad", C.c_int32),
+                ("agent", C.c_int32 * NAV_MAX_NAVIGATORS), ("opp_mask", C.c_uint32 * NAV_MAX_NAVIGATORS), ("coef", C.c_float * NAV_MAX_NAVIGATORS),
+                ("gamma", C.c_float), ("pad2", C.c_int32),
+                ("grid", C.c_void_p), ("snap", C.c_void_p), ("hops", C.c_void_p), ("slot_map", C.c_void_p),
+                ("team_positions", C.c_void_p), ("final_positions", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p),
+                ("reward_out", C.c_void_p), ("sr_g", C.c_int64), ("shaping_out", C.c_void_p), ("ss_g", C.c_int64), ("hops_prev", C.c_void_p)]
+
+
+def _rows_gn(t, G: int, N: int, name: str):
+    """(pointer, row stride in elements) of an fp32 [G, N] tensor whose rows are contiguous (any row stride: a [G, T, N] buffer's [:, t])."""
+    import torch
+    assert t.dtype == torch.float32 and tuple(t.shape) == (G, N) and (N == 1 or t.stride(1) == 1), f"{name}: fp32 [G, N] with contiguous rows"
+    return t.data_ptr(), int(t.stride(0))
+
+
+def nav_shape(team_positions, field, agent_indices, opp_masks, coef, gamma: float, cap: int, hops_prev, *, final_positions=None,
+              terminated=None, truncated=None, reward_out=None, shaping_out=None, prime: bool = False) -> None:
+    """One tick of geodesic reward shaping in one launch (``cat_render_nav_shape``; ``navigation.shaping_step`` is its definition):
+    team_positions / final_positions f16 [N, A, 2], terminated / truncated u8 [N], ``field`` as in ``nav_step``, per shaped agent its column,
+    opponent bitmask and fp32 coefficient; hops_prev int32 [G, N] (read and rewritten), reward_out fp32 [G, N] with contiguous rows at any
+    row stride (takes ``+ F``), shaping_out the same or None (takes ``F``).  ``prime``: only hops_prev is written and the other buffers may
+    be None."""
+    import torch
+    N, A, _ = team_positions.shape
+    G = len(agent_indices)
+    assert 1 <= G <= NAV_MAX_NAVIGATORS and len(opp_masks) == G == len(coef)
+    assert team_positions.dtype == torch.float16 and team_positions.shape == (N, A, 2) and team_positions.is_contiguous()
+    assert hops_prev.dtype == torch.int32 and hops_prev.shape == (G, N) and hops_prev.is_contiguous()
+    assert field.slot_map.dtype == torch.int32 and field.slot_map.shape == (N,) and field.slot_map.is_contiguous()
+    tensors = [team_positions, hops_prev, field.grid, field.snap, field.hops, field.slot_map]
+    rp = sp = sr = ss = 0
+    if not prime:
+        assert final_positions is not None and final_positions.dtype == torch.float16 and final_positions.shape == (N, A, 2) and final_positions.is_contiguous()
+        for f in (terminated, truncated):
+            assert f is not None and f.dtype == torch.uint8 and f.shape == (N,) and f.is_contiguous()
+        rp, sr = _rows_gn(reward_out, G, N, "reward_out")
+        tensors += [final_positions, terminated, truncated, reward_out]
+        if shaping_out is not None:
+            sp, ss = _rows_gn(shaping_out, G, N, "shaping_out")
+            tensors.append(shaping_out)
+    assert all(t.device == team_positions.device for t in tensors)
+    pad = [0] * (NAV_MAX_NAVIGATORS - G)
+    a = NavShapeArgs(N, A, G, field.grid.shape[0], int(field.cell), int(cap), int(bool(prime)), 0,
+                     (C.c_int32 * NAV_MAX_NAVIGATORS)(*agent_indices, *pad), (C.c_uint32 * NAV_MAX_NAVIGATORS)(*opp_masks, *pad),
+                     (C.c_float * NAV_MAX_NAVIGATORS)(*[float(c) for c in coef], *pad), float(gamma), 0,
+                     field.grid.data_ptr(), field.snap.data_ptr(), field.hops.data_ptr(), field.slot_map.data_ptr(),
+                     team_positions.data_ptr(), _ptr(None if prime else final_positions), _ptr(None if prime else terminated),
+                     _ptr(None if prime else truncated), rp or None, sr, sp or None, ss, hops_prev.data_ptr())
+    _check(lib().cat_render_nav_shape(C.byref(a), _stream()), "cat_render_nav_shape")
 
 
 # ---------------------------------------------------------------------------------------------- scripted opponents

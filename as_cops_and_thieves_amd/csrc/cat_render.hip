@@ -539,6 +539,34 @@ extern "C" int cat_render_nav_step(const cat_render_nav_step_args *a, void *stre
     return launched("cat_render_nav_step");
 }
 
+extern "C" int cat_render_nav_shape(const cat_render_nav_shape_args *a, void *stream)
+{
+    if (!a) return nhfail("NULL arguments");
+    if (a->N <= 0 || a->A <= 0 || a->A > CAT_RENDER_MAX_AGENTS) return nhfail("bad dimensions");
+    if (a->G < 1 || a->G > CAT_NAV_MAX_NAVIGATORS) return nhfail("G must lie in 1 .. 8");
+    if (a->n_maps < 1 || a->n_maps > CAT_NAV_MAX_MAPS) return nhfail("n_maps must lie in 1 .. 16");
+    if (a->cell < 1) return nhfail("cell must be >= 1");
+    if (a->cap < 1 || a->cap > 65534) return nhfail("cap must lie in 1 .. 65534");
+    if (a->prime != 0 && a->prime != 1) return nhfail("prime must be 0 or 1");
+    if (!agents_ok(a->agent, a->G, a->A)) return nhfail("an agent index outside [0, A)");
+    for (int g = 0; g < a->G; ++g) {
+        if ((a->A < 32 && (a->opp_mask[g] >> a->A)) || ((a->opp_mask[g] >> a->agent[g]) & 1u))
+            return nhfail("opp_mask names an agent outside [0, A) or the shaped agent itself");
+        if (!isfinite(a->coef[g])) return nhfail("a coefficient is not finite");
+    }
+    if (!isfinite(a->gamma) || a->gamma < 0.0f) return nhfail("gamma must be finite and >= 0");
+    if (!a->grid || !a->snap || !a->hops) return nhfail("a table of the field is NULL");
+    if (!a->team_positions || !a->hops_prev) return nhfail("a required buffer is NULL");
+    if ((uintptr_t)a->team_positions & 3) return nhfail("team_positions must be 4-byte aligned");
+    if (!a->prime) {
+        if (!a->final_positions || !a->terminated || !a->truncated || !a->reward_out) return nhfail("a required buffer is NULL (only prime mode does without)");
+        if ((uintptr_t)a->final_positions & 3) return nhfail("final_positions must be 4-byte aligned");
+        if (a->G > 1 && (a->sr_g < a->N || (a->shaping_out && a->ss_g < a->N))) return nhfail("a row stride below N: the rows would overlap");
+    }
+    hipLaunchKernelGGL(nav_shape_kernel, dim3((unsigned)((a->N + NAV_BLOCK - 1) / NAV_BLOCK)), dim3(NAV_BLOCK), 0, (hipStream_t)stream, *a);
+    return launched("cat_render_nav_shape");
+}
+
 extern "C" int cat_render_abi_version(void) { return CAT_RENDER_ABI_VERSION; }
 extern "C" const char *cat_render_last_error(void) { return g_err; }
 

@@ -1,7 +1,8 @@
 // cat_render_nav.h -- the navigation kernels of cat_render.hip (included there and nowhere else): the all-pairs hop table of a batch of
-// map grids (cat_render_nav_build) and one tick of the privileged "pursue" / "flee" opponents (cat_render_nav_step).  include/cat_render.h
-// states the rules; as_cops_and_thieves_amd/navigation.py (hops_reference, navigate_step) is their NumPy / torch statement, which both
-// kernels equal exactly: every value is an integer.
+// map grids (cat_render_nav_build), one tick of the privileged "pursue" / "flee" opponents (cat_render_nav_step) and one tick of geodesic reward
+// shaping (cat_render_nav_shape).  include/cat_render.h states the rules; as_cops_and_thieves_amd/navigation.py (hops_reference,
+// navigate_step, shaping_step) is their NumPy / torch statement, which the kernels equal exactly: every value is an integer, or an fp32
+// result of the same rounded operations.
 #pragma once
 
 #include "cat_learn_common.h"
@@ -176,7 +177,90 @@ __global__ __launch_bounds__(NAV_BLOCK) void nav_step_kernel(const cat_render_na
     if (a.nav_hops) a.nav_hops[(size_t)g * a.N + n] = d_out;
 }
 
+// ---- reward shaping.  A thread owns one slot: it finds the cells of the slot's A agents once (they are the same for every shaped agent g),
+// then walks the G rows; g is uniform, so agent / opp_mask / coef are scalar loads.  The cell arrays are indexed by unrolled constants only
+// (agent[g] is picked by comparison), so they stay in registers.  The enclosing file is compiled with contraction off: gamma * phi1 - phi0 is a
+// rounded multiply and a rounded subtraction, as navigation.shaping_step has them.
+__device__ __forceinline__ void nav_cells(const uint32_t *pos, int A, int cell, const NavGrid &gr, int (&c)[CAT_RENDER_MAX_AGENTS])
+{
+#pragma unroll
+    for (int j = 0; j < CAT_RENDER_MAX_AGENTS; ++j) {
+        float x, y;
+        c[j] = (j < A && gr.C) ? nav_cell(pos[j], cell, gr, x, y) : -1;
+    }
+}
+
+// separation(P, g) of include/cat_render.h over the cells c of P's row
+__device__ __forceinline__ int nav_separation(const int (&c)[CAT_RENDER_MAX_AGENTS], int me, uint32_t mask, const NavGrid &gr)
+{
+    int ca = -1;
+#pragma unroll
+    for (int j = 0; j < CAT_RENDER_MAX_AGENTS; ++j)
+        if (j == me) ca = c[j];
+    if (ca < 0) return -1;
+    uint32_t best = NAV_NONE;
+#pragma unroll
+    for (int j = 0; j < CAT_RENDER_MAX_AGENTS; ++j)
+        if (((mask >> j) & 1u) && c[j] >= 0) best = min(best, (uint32_t)gr.hops[(size_t)c[j] * gr.C + ca]);
+    return best == NAV_NONE ? -1 : (int)best;
+}
+
+__global__ __launch_bounds__(NAV_BLOCK) void nav_shape_kernel(const cat_render_nav_shape_args a)
+{
+    const int n = blockIdx.x * NAV_BLOCK + threadIdx.x;
+    if (n >= a.N) return;
+    const int A = a.A;
+    const int m = a.slot_map ? a.slot_map[n] : 0;
+    NavGrid gr{0, 0, 0, nullptr, nullptr, nullptr};
+    if (m >= 0 && m < a.n_maps) {
+        const int32_t *row = a.grid + 4 * m;
+        const int w = row[0], h = row[1];
+        if (w >= 1 && h >= 1 && (long)w * h <= CAT_NAV_MAX_CELLS) {
+            gr.Wc = w; gr.Hc = h; gr.C = w * h;
+            gr.snap = a.snap + row[2]; gr.hops = a.hops + row[3];
+        }
+    }
+    int now[CAT_RENDER_MAX_AGENTS], fin[CAT_RENDER_MAX_AGENTS];
+    nav_cells((const uint32_t *)a.team_positions + (size_t)n * A, A, a.cell, gr, now);
+    const bool prime = a.prime != 0;
+    const bool term = !prime && a.terminated[n] != 0;
+    const bool timeout = term && a.truncated[n] != 0;
+    if (timeout) {                                          // the only rows of final_positions that are ever read
+        nav_cells((const uint32_t *)a.final_positions + (size_t)n * A, A, a.cell, gr, fin);
+    } else {
+#pragma unroll
+        for (int j = 0; j < CAT_RENDER_MAX_AGENTS; ++j) fin[j] = -1;
+    }
+    for (int g = 0; g < a.G; ++g) {
+        const int me = a.agent[g];
+        const uint32_t mask = a.opp_mask[g];
+        const int d_now = nav_separation(now, me, mask, gr);
+        int32_t *state = a.hops_prev + (size_t)g * a.N + n;
+        if (!prime) {
+            const float coef = a.coef[g];
+            const int d0 = *state;
+            bool defined = d0 >= 0;
+            float phi1 = 0.0f;                              // a capture: the potential of a terminal state
+            if (!term || timeout) {
+                const int d1 = timeout ? nav_separation(fin, me, mask, gr) : d_now;
+                defined = defined && d1 >= 0;
+                phi1 = coef * (float)min(max(d1, 0), a.cap);
+            }
+            float F = 0.0f;
+            if (defined) {
+                const float phi0 = coef * (float)min(d0, a.cap);
+                F = a.gamma * phi1 - phi0;
+            }
+            float *r = a.reward_out + (size_t)g * a.sr_g + n;
+            *r = *r + F;
+            if (a.shaping_out) a.shaping_out[(size_t)g * a.ss_g + n] = F;
+        }
+        *state = d_now;
+    }
+}
+
 int nbfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_nav_build", msg); }
 int nsfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_nav_step", msg); }
+int nhfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_nav_shape", msg); }
 
 }   // namespace

@@ -31,6 +31,26 @@ The tick, per row = (navigator g, env n) -- actions 0 = -x, 1 = +y, 2 = +x, 3 = 
 * flee: per usable neighbour m_i = min and t_i = sum over ALL opponents with a cell of ``hops[b_j][nb_i]`` (``NONE`` counts as 65535: an
   unreachable threat is none): the largest m_i, then the largest t_i, then the lowest action.
 * ``nav_hops`` = d: the geodesic separation of the row from its nearest opponent.
+
+Potential-based reward shaping (Ng, Harada and Russell 1999) on the same table -- ``separation`` and ``shaping_step`` (torch, any device)
+ARE its definition, and ``cat_render_nav_shape`` equals them bit for bit.  The learner's reward takes ``F = gamma Phi(s') - Phi(s)``, which
+leaves the optimal policies as they are: over an episode the sum telescopes.
+
+* ``separation(P, g)`` of agent g in a position array P (f16 [N, A, 2]), by the cell rule above: a = g's cell; d = the smallest
+  ``hops[b_j][a]`` over the opponents j of ``opp_mask[g]`` that have a cell and whose entry is not ``NONE``; -1 if g has no cell or there
+  is no such opponent.  (No neighbour needs to be usable: that is the navigators' concern.)
+* ``phi(g, d) = coef[g] (*) float(min(d, cap))`` for d >= 0: one rounded fp32 multiply of an exactly converted integer.  ``coef[g]`` is
+  negative for a cop (closer is better) and positive for a thief; ``cap`` is an integer in 1 .. 65534.
+* One tick of row (g, n); its state ``hops_prev[g][n]`` (int32) is the separation at the start of the tick, d0:
+  ``terminated[n]`` and not ``truncated[n]`` (a capture: a true terminal state): phi1 = +0.0, defined.
+  ``terminated[n]`` and ``truncated[n]`` (the time limit, no property of the state): d1 = separation(final_positions, g).
+  Otherwise d1 = separation(team_positions, g).
+  F = +0.0 if d0 < 0 or a needed d1 < 0, else ``(gamma (*) phi1) (-) phi(g, d0)``: two rounded fp32 operations in that order, never fused.
+  ``reward_out[g][n] = reward_out[g][n] (+) F`` (always performed), ``shaping_out[g][n] = F`` where given, and
+  ``hops_prev[g][n] = separation(team_positions, g)`` -- always; on a terminal row that is the NEW episode's first state, because the env
+  resets inside the tick.
+* Prime mode: only the last assignment.
+* ``final_positions`` is read on rows with ``terminated`` and ``truncated`` both set and nowhere else: every other row of it is stale or NaN.
 """
 from __future__ import annotations
 
@@ -159,6 +179,28 @@ def component_sizes(free: np.ndarray, Wc: int, Hc: int) -> List[int]:
     return sorted((int(c) for c in np.bincount(label[f]) if c), reverse=True)
 
 
+def arena_cells(cmap, cell: int, clearance: float) -> Tuple[np.ndarray, int, int]:
+    """``free_cells`` restricted to the 4-connected components in which the map lets an agent start: those that hold the cell of a start
+    position or of a spawn region's centre (``CompiledMap.start_pos``, ``.regions`` = x, y, w, h).  Everything else counts as blocked,
+    so a blocked cell snaps INTO the arena.  Why: ``snap`` picks the nearest free cell without asking whether the agents can get there, and
+    a wall thinner than a cell has free cells on both sides at the same distance -- on squarinth an agent that touches the top or the left
+    wall from inside would snap to the ground outside the enclosure and lose every separation.  (All of a map's free cells are kept where
+    none of these points lies in a free cell.)"""
+    free, Wc, Hc = free_cells(cmap, cell, clearance)
+    pts = [np.asarray(cmap.start_pos, np.float64).reshape(-1, 2)]
+    reg = np.asarray(cmap.regions, np.float64).reshape(-1, 4)
+    pts.append(reg[:, :2] + 0.5 * reg[:, 2:])
+    pts = np.concatenate(pts)
+    ix, iy = np.floor(pts[:, 0]).astype(np.int64) // cell, np.floor(pts[:, 1]).astype(np.int64) // cell
+    on = (pts >= 0).all(axis=1) & (ix < Wc) & (iy < Hc)
+    seeds = np.unique((ix * Hc + iy)[on])
+    seeds = seeds[free[seeds] != 0]
+    if not len(seeds):
+        return free, Wc, Hc
+    reached = (hops_reference(free, Wc, Hc, goals=seeds) != NONE).any(axis=0)
+    return (free * reached).astype(np.uint8), Wc, Hc
+
+
 class NavField:
     """The tables of a batch of maps, on ``device``.
 
@@ -201,21 +243,21 @@ class NavField:
             self.hops = torch.from_numpy(np.concatenate([hops_reference(f, Wc, Hc).reshape(-1) for f, Wc, Hc in masks]).view(np.int16).copy())
 
     @classmethod
-    def from_maps(cls, compiled, slot_map, cell: int = 16, clearance: float = 6.0, device="cpu") -> "NavField":
-        """The field of ``CompiledMap``s (``free_cells`` of each)."""
-        return cls(cell, [free_cells(cm, cell, clearance) for cm in compiled], slot_map, device)
+    def from_maps(cls, compiled, slot_map, cell: int = 16, clearance: float = 6.0, device="cpu", arena: bool = False) -> "NavField":
+        """The field of ``CompiledMap``s: ``free_cells`` of each, or with ``arena`` its ``arena_cells``."""
+        return cls(cell, [(arena_cells if arena else free_cells)(cm, cell, clearance) for cm in compiled], slot_map, device)
 
     @classmethod
-    def from_env(cls, env, cell: int = 16, clearance: Optional[float] = None) -> "NavField":
+    def from_env(cls, env, cell: int = 16, clearance: Optional[float] = None, arena: bool = False) -> "NavField":
         """The field of ``env``'s compiled maps and slots; ``clearance`` defaults to the env's agent_radius + wall_radius (6.0 with the
-        default physics)."""
+        default physics); ``arena``: ``arena_cells`` instead of ``free_cells``."""
         cfg = env._cfg
         if clearance is None:
             clearance = float(cfg.agent_radius) + float(cfg.wall_radius)
         slot_map = getattr(env, "slot_map_ids", None)
         if slot_map is None:
             slot_map = np.zeros(env.num_envs, dtype=np.int32)
-        return cls.from_maps(env._compiled, slot_map, cell, float(clearance), env.device)
+        return cls.from_maps(env._compiled, slot_map, cell, float(clearance), env.device, **({"arena": True} if arena else {}))
 
     @property
     def n_maps(self) -> int:
@@ -242,20 +284,17 @@ class NavField:
         return [component_sizes(self.free_of(m), int(self.grid_host[m, 0]), int(self.grid_host[m, 1])) for m in range(self.n_maps)]
 
 
-@torch.no_grad()
-def navigate_step(team_positions: torch.Tensor, uniform: torch.Tensor, field: NavField, agent_index: Sequence[int], script,
-                  opponent_mask: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The rule of the module docstring: team_positions f16 [N, A, 2], uniform fp32 [G, N], per navigator g its env agent index, its
-    script (an int or an integer tensor [N] per navigator, or one tensor [G, N]: PURSUE, FLEE or -1) and the bitmask of its opponents'
-    agent indices.  Returns (action int32 [G, N], nav_hops int32 [G, N]); both are -1 where the script is -1, and nav_hops is -1 after
-    the fallback.  Nothing is modified."""
-    N, A, _ = team_positions.shape
-    G = len(agent_index)
-    assert team_positions.dtype == torch.float16 and uniform.dtype == torch.float32 and tuple(uniform.shape) == (G, N)
-    dev, i64 = team_positions.device, torch.int64
+def _cells_and_hops(positions: torch.Tensor, field: NavField):
+    """The cell and hop lookup that ``navigate_step`` and ``separation`` share, for positions f16 [N, A, 2]: (pos fp32 [N, A, 2], cells
+    int64 [N, A] -- every agent's snapped cell by the rule of the module docstring, -1 = none --, H, (Wc, Hc, coff, free)) with
+    ``H(b, k)`` = ``hops[b][k]`` of the row's map where both are cells and ``NONE`` elsewhere (b, k int64 [N, ...]), Wc / Hc / coff [N, 1]
+    the row's grid and its first element in the per-cell arrays, ``free`` the field's mask on the positions' device."""
+    N = positions.shape[0]
+    assert positions.dtype == torch.float16 and positions.dim() == 3 and positions.shape[2] == 2
+    dev, i64 = positions.device, torch.int64
     cell, M = field.cell, field.n_maps
-    pos = team_positions.float()                                               # f16 -> fp32 is exact
-    bits = team_positions.view(torch.int16).to(i64) & 0xFFFF
+    pos = positions.float()                                                    # f16 -> fp32 is exact
+    bits = positions.view(torch.int16).to(i64) & 0xFFFF
     finite = ((bits & 0x7C00) != 0x7C00).all(-1)
     m = field.slot_map.to(dev).to(i64)
     map_ok = (m >= 0) & (m < M)
@@ -276,6 +315,22 @@ def navigate_step(team_positions: torch.Tensor, uniform: torch.Tensor, field: Na
         per_row = (N,) + (1,) * (ok.dim() - 1)
         v = hops[hoff.view(per_row) + torch.where(ok, b * C.view(per_row) + k, torch.zeros_like(b + k))].to(i64) & 0xFFFF
         return torch.where(ok, v, torch.full_like(v, NONE))
+
+    return pos, cells, H, (Wc, Hc, coff, free)
+
+
+@torch.no_grad()
+def navigate_step(team_positions: torch.Tensor, uniform: torch.Tensor, field: NavField, agent_index: Sequence[int], script,
+                  opponent_mask: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The rule of the module docstring: team_positions f16 [N, A, 2], uniform fp32 [G, N], per navigator g its env agent index, its
+    script (an int or an integer tensor [N] per navigator, or one tensor [G, N]: PURSUE, FLEE or -1) and the bitmask of its opponents'
+    agent indices.  Returns (action int32 [G, N], nav_hops int32 [G, N]); both are -1 where the script is -1, and nav_hops is -1 after
+    the fallback.  Nothing is modified."""
+    N, A, _ = team_positions.shape
+    G = len(agent_index)
+    assert team_positions.dtype == torch.float16 and uniform.dtype == torch.float32 and tuple(uniform.shape) == (G, N)
+    dev, i64 = team_positions.device, torch.int64
+    pos, cells, H, (Wc, Hc, coff, free) = _cells_and_hops(team_positions, field)
 
     script_t = torch.stack([torch.as_tensor(sc, device=dev).to(i64).expand(N) for sc in script]) if not torch.is_tensor(script) else \
         script.to(dev).to(i64).expand(G, N)
@@ -327,3 +382,55 @@ def navigate_step(team_positions: torch.Tensor, uniform: torch.Tensor, field: Na
         actions.append(torch.where(sc >= 0, act, torch.full_like(act, -1)))
         nav.append(torch.where((sc >= 0) & ok, d, torch.full_like(d, -1)))
     return torch.stack(actions).to(torch.int32), torch.stack(nav).to(torch.int32)
+
+
+@torch.no_grad()
+def separation(positions: torch.Tensor, field: NavField, agent_index: Sequence[int], opponent_mask: Sequence[int]) -> torch.Tensor:
+    """The geodesic separation int32 [G, N] of the module docstring for positions f16 [N, A, 2]: per row (g, n) the smallest
+    ``hops[b_j][a]`` over g's opponents with a cell and an entry that is not ``NONE``; -1 where g has no cell or there is no such opponent."""
+    N, A, _ = positions.shape
+    _, cells, H, _ = _cells_and_hops(positions, field)
+    out = []
+    for g in range(len(agent_index)):
+        me, opp = int(agent_index[g]), [j for j in range(A) if (int(opponent_mask[g]) >> j) & 1]
+        if not opp:
+            out.append(torch.full((N,), -1, dtype=torch.int64, device=positions.device))
+            continue
+        d = H(cells[:, opp], cells[:, me:me + 1]).min(dim=1).values            # NONE where either has no cell: the largest value
+        out.append(torch.where(d != NONE, d, torch.full_like(d, -1)))
+    return torch.stack(out).to(torch.int32)
+
+
+@torch.no_grad()
+def shaping_step(team_positions: torch.Tensor, final_positions: Optional[torch.Tensor], terminated: Optional[torch.Tensor],
+                 truncated: Optional[torch.Tensor], field: NavField, agent_index: Sequence[int], opponent_mask: Sequence[int],
+                 coef: Sequence[float], gamma: float, cap: int, hops_prev: torch.Tensor, reward_out: Optional[torch.Tensor] = None,
+                 shaping_out: Optional[torch.Tensor] = None, prime: bool = False) -> None:
+    """One tick of the shaping rule of the module docstring, in place: team_positions / final_positions f16 [N, A, 2], terminated /
+    truncated [N] (bool or u8), per shaped agent g its env agent index, the bitmask of its opponents and its fp32 coefficient; ``gamma``
+    is rounded to fp32 once.  ``hops_prev`` int32 [G, N] is read and rewritten, ``reward_out`` fp32 [G, N] (any row stride) takes
+    ``(+) F`` and ``shaping_out`` (where given) ``F``.  ``prime``: only ``hops_prev`` is written, and only team_positions is read."""
+    N, A, _ = team_positions.shape
+    G = len(agent_index)
+    if not (isinstance(cap, (int, np.integer)) and not isinstance(cap, bool) and 1 <= cap <= 65534):
+        raise ValueError(f"cap is a hop count in 1 .. 65534, got {cap!r}")
+    assert hops_prev.dtype == torch.int32 and tuple(hops_prev.shape) == (G, N) and len(opponent_mask) == G == len(coef)
+    d_now = separation(team_positions, field, agent_index, opponent_mask)
+    if not prime:
+        dev, f32 = team_positions.device, torch.float32
+        assert reward_out is not None and reward_out.dtype == f32 and tuple(reward_out.shape) == (G, N)
+        assert shaping_out is None or (shaping_out.dtype == f32 and tuple(shaping_out.shape) == (G, N))
+        term, trunc = (terminated.to(dev) != 0).view(1, N), (truncated.to(dev) != 0).view(1, N)
+        capture, timeout = term & ~trunc, term & trunc
+        d_fin = separation(final_positions, field, agent_index, opponent_mask)   # (rows that are no timeout drop out in the next line)
+        d0, d1 = hops_prev.to(dev), torch.where(timeout, d_fin, d_now)
+        c = torch.tensor([float(v) for v in coef], dtype=f32, device=dev).view(G, 1)
+        g32 = torch.tensor(float(gamma), dtype=f32, device=dev)
+        phi = lambda d: c * d.clamp(0, int(cap)).to(f32)                       # one rounded multiply; the conversion is exact
+        zero = torch.zeros(G, N, dtype=f32, device=dev)
+        phi1 = torch.where(capture, zero, phi(d1))
+        F = torch.where((d0 >= 0) & (capture | (d1 >= 0)), g32 * phi1 - phi(d0), zero)    # two rounded operations, in this order
+        reward_out.copy_(reward_out + F)
+        if shaping_out is not None:
+            shaping_out.copy_(F)
+    hops_prev.copy_(d_now)

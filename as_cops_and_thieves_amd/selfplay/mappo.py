@@ -26,6 +26,7 @@ as device-side gates -- no host synchronisation inside an update, so the minibat
 from __future__ import annotations
 
 import dataclasses
+import math
 import warnings
 from typing import Sequence, Dict, List, Optional, Tuple
 
@@ -168,11 +169,37 @@ class TrainerConfig:
                                            # are normalised values: the GAE scan denormalises them as it reads them (``cat_ppo_gae_scan_scaled``),
                                            # the moments take in every update's raw returns (``cat_ppo_moments``: fixed order, bit-reproducible,
                                            # include/cat_ppo.h), then the targets are normalised with the new scale.  False: nothing is added
+    geodesic_shaping: float = 0.0          # W > 0: geodesic potential-based reward shaping (Ng, Harada and Russell 1999; ``selfplay/shaping.py``).
+                                           # Every learner's reward rows take ``F = gamma Phi(s') - Phi(s)`` with its own ``discount_factor`` and
+                                           # ``Phi = -W min(hops, cap)`` for a cop, ``+shaping_scale_thief min(hops, cap)`` for a thief, hops the
+                                           # shortest-path separation from the nearest opponent on the map's grid (``navigation.NavField``): one
+                                           # launch of ``cat_render_nav_shape`` per learner and tick inside the captured rollout, and one at its top
+                                           # that primes the separations from the env's current state.  ``F`` is kept in ``buf["shape"]``;
+                                           # ``read_stats`` adds ``shaping/<agent>`` and ``geodesic_hops/<agent>``.  The env's own rewards, episode
+                                           # statistics and observations are untouched.  Needs an env built with ``final_positions=True`` that offers
+                                           # ``raw_outputs``.  0 (the reference trains unshaped): no shaper, no field, no buffer, no launch
+    shaping_scale_thief: Optional[float] = None     # the thieves' scale; None: ``geodesic_shaping``.  0 leaves the thieves unshaped
+    shaping_cap: int = 64                  # hop counts above it count as it (1 .. 65534): the potential is bounded by scale * cap
 
     def __post_init__(self):
         k = self.frame_skip
         if isinstance(k, bool) or not isinstance(k, int) or k < 1:
             raise ValueError(f"TrainerConfig.frame_skip must be an integer >= 1, got {k!r}")
+        for name in ("geodesic_shaping", "shaping_scale_thief"):
+            v = getattr(self, name)
+            if v is None and name == "shaping_scale_thief":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"TrainerConfig.{name} must be a finite number >= 0, got {v!r}")
+        c = self.shaping_cap
+        if isinstance(c, bool) or not isinstance(c, int) or not 1 <= c <= 65534:
+            raise ValueError(f"TrainerConfig.shaping_cap must be an integer in 1 .. 65534, got {c!r}")
+
+    @property
+    def shaping_scales(self) -> Tuple[float, float]:
+        """(cop scale, thief scale) of ``geodesic_shaping``; (0, 0) = off."""
+        w = float(self.geodesic_shaping)
+        return w, (w if self.shaping_scale_thief is None else float(self.shaping_scale_thief))
 
 
 def compute_gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: torch.Tensor,
@@ -809,8 +836,25 @@ class MAPPOTrainer:
         self.stats: Dict[str, float] = {}
         self.use_graphs = on_gpu
         self._collect_params: Dict[str, object] = {}    # fused_collect: learner key -> the kernel's parameter block (pointers into fp.lp)
+        self._shapers: Dict[str, object] = {}      # geodesic_shaping: learner key -> its GeodesicShaper (all share one NavField)
+        if any(self.tcfg.shaping_scales):
+            self._build_shapers()
         if self.tcfg.fused_collect:
             self._check_fused_collect(on_gpu)
+
+    def _build_shapers(self) -> None:
+        """``TrainerConfig.geodesic_shaping``: per learner with a shaped agent a ``GeodesicShaper`` with the learner's own discount factor and
+        a ``buf["shape"]`` [G, T, N] for the shaping terms (rows of agents left out stay 0).  ValueError where the env cannot serve it."""
+        from .shaping import GeodesicShaper
+        w_cop, w_thief = self.tcfg.shaping_scales
+        field = None
+        for key, rl in self.roles.items():
+            shaper = GeodesicShaper(self.env, rl.agents, scale_cop=w_cop, scale_thief=w_thief, cap=self.tcfg.shaping_cap,
+                                    gamma=rl.cfg.discount_factor, field=field)
+            field = shaper.field
+            if shaper.G:
+                self._shapers[key] = shaper
+                rl.buf["shape"] = torch.zeros(rl.G, self.tcfg.horizon, self.N, dtype=torch.float32, device=self.device)
 
     def _check_fused_collect(self, on_gpu: bool) -> None:
         """``TrainerConfig.fused_collect`` where the one-launch tick can never apply is an error, not a silent per-layer rollout."""
@@ -889,6 +933,9 @@ class MAPPOTrainer:
         all_fused = self._native_post and not any_random and all(rl.native and rl.random_rows is None for rl in learners.values())
         defer = all_fused and self._native_io and self.tcfg.deferred_values
         collect = self.tcfg.fused_collect and defer        # (defer implies all_fused: every learner is native and none acts at random)
+        shapers = {key: self._shapers[key] for key in learners if key in self._shapers}
+        for shaper in shapers.values():     # the separations of the state the rollout starts from, whatever happened to the env since the last
+            shaper.prime(self.env.raw_outputs())       # one (reset, reset_episodes, load_state_dict, the random-phase fast-forward)
         for t in range(T):
             state = self.env.state()
             keep = self._keep32 if all_fused else (~self._starts).view(1, N)
@@ -940,17 +987,21 @@ class MAPPOTrainer:
                 raw = self.env.step_raw(self._actions, **skip)
                 if skip:
                     self._env_ticks.add_(raw["ticks"].sum())
-                for i, rl in enumerate(learners.values()):
+                for i, (key, rl) in enumerate(learners.items()):
                     flags = (self._done_buf[t], self._starts, self._keep32) if i == 0 else (None, None, None)
                     _learn_native.rollout_post(raw, rl.indices, rl.buf["rew"][:, t], *flags)
+                    if key in shapers:             # rew += F, shape = F: one launch, after the rewards of the tick are in place
+                        shapers[key].step(raw, rl.buf["rew"][:, t], rl.buf["shape"][:, t])
                 self._obs = self.env.observations()
                 continue
             self._obs, rewards, terms, truncs, infos = self.env.step(self._actions, **skip)
             if skip:
                 self._env_ticks.add_(infos["ticks"].sum())
             done = terms[self.agents[0]]
-            for rl in learners.values():
+            for key, rl in learners.items():
                 rl.buf["rew"][:, t].copy_(torch.stack([rewards[a].float() for a in rl.agents]))
+                if key in shapers:
+                    shapers[key].step(self.env.raw_outputs(), rl.buf["rew"][:, t], rl.buf["shape"][:, t])
             self._done_buf[t].copy_(done)
             self._starts.copy_(done)               # the env auto-resets: the next tick starts a new episode
             self._keep32.copy_((~done).view(1, N))
@@ -1094,6 +1145,16 @@ class MAPPOTrainer:
                 for g, a in enumerate(rl.agents):
                     out[f"lr/{a}"], out[f"entropy_scale/{a}"], out[f"ratio_clip/{a}"] = (float(h[g, HYPER_LR]), float(h[g, HYPER_ENTROPY]),
                                                                                        float(h[g, HYPER_RATIO_CLIP]))
+        for key, shaper in self._shapers.items():
+            if key in self._opponents:
+                continue
+            rl = self.roles[key]
+            mean_f = rl.buf["shape"].mean(dim=(1, 2)).cpu()                # the last rollout's shaping terms
+            hops = shaper.hops_prev.cpu()
+            for g, a in zip(shaper.rows, shaper.agents):
+                out[f"shaping/{a}"] = float(mean_f[g])
+            for row, a in zip(hops, shaper.agents):                        # the separations the next rollout starts from, where defined
+                out[f"geodesic_hops/{a}"] = float(row[row >= 0].float().mean()) if bool((row >= 0).any()) else float("nan")
         ep = self._episode_stats()
         if ep is not None:
             e = ep()

@@ -751,7 +751,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   lr_schedule: str = "constant", lr_final: Optional[float] = None, lr_kl_target: Optional[float] = None,
                   entropy_final: Optional[float] = None, ratio_clip_final: Optional[float] = None,
                   baseline_eval: bool = False, baseline_episodes: int = 64, navigator_eval: bool = False,
-                  navigator_episodes: int = 64) -> Dict[str, object]:
+                  navigator_episodes: int = 64, geodesic_shaping: float = 0.0, shaping_scale_thief: Optional[float] = None,
+                  shaping_cap: Optional[int] = None) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -783,6 +784,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
 
     ``value_norm``: the critics train on returns normalised by running per-agent moments (``TrainerConfig.value_norm``); the joint
     checkpoints then carry each agent's moments (``vn_state``) beside its value network.
+
+    ``geodesic_shaping=W`` (with ``shaping_scale_thief``, ``shaping_cap``): the learners' rewards take the geodesic potential-based shaping
+    term of ``TrainerConfig.geodesic_shaping``; the training env is then built with ``final_positions=True`` (an ``env_factory``'s env must
+    bring it along: ValueError from the trainer otherwise).  Evaluation, the archives and the booked outcomes see the env's own rewards only.
 
     ``lr_schedule`` ("constant", "linear" with ``lr_final``, "kl_adaptive" with ``lr_kl_target``), ``entropy_final``, ``ratio_clip_final``: the
     schedules of ``RoleConfig``, put into both roles' configurations.  A role configuration that leaves ``schedule_updates`` at 0 gets the
@@ -842,6 +847,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         trainer_cfg = dataclasses.replace(trainer_cfg, fused_collect=True)
     if value_norm:
         trainer_cfg = dataclasses.replace(trainer_cfg, value_norm=True)
+    if geodesic_shaping or shaping_scale_thief:
+        trainer_cfg = dataclasses.replace(trainer_cfg, geodesic_shaping=geodesic_shaping, shaping_scale_thief=shaping_scale_thief,
+                                          **({} if shaping_cap is None else {"shaping_cap": shaping_cap}))
+    shaped = any(trainer_cfg.shaping_scales)
     out_dir = Path(out_dir)
     arch = {tc.cop_role_prefix: out_dir / "cops", tc.thief_role_prefix: out_dir / "thieves"}
     if chief:
@@ -860,9 +869,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     train_factory = eval_factory = env_factory
     if env_factory is None:
         preset = load_preset(map_name, n_cops, n_thieves)
-        make = lambda track: (lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
-                                                             env_id_offset=off, query_order=query_order, track_episodes=track))
-        env_factory = train_factory = make(episode_stats)
+        make = lambda track, **more: (lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
+                                                                     env_id_offset=off, query_order=query_order, track_episodes=track, **more))
+        env_factory = train_factory = make(episode_stats, **({"final_positions": True} if shaped else {}))    # the shaper reads where episodes ended
         eval_factory = make(tracked_eval)
         if position_stats is not None:
             eval_factory = lambda n, s, off=0: VecCopsEnv(preset, n, num_rays=num_rays, max_step_count=max_step_count, seed=s, device=device,
@@ -913,7 +922,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         evaluator = PolicyActor.from_checkpoint(None, eval_env, fused="kernel", compute_bf16=trainer_cfg.compute_bf16, normalize_inputs=trainer_cfg.normalize_inputs,
                                                 recurrent=trainer_cfg.recurrent, seed=seed + 1, device=trainer.device)
     else:
-        evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False, fused_collect=False),
+        evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False, fused_collect=False,
+                                                                         geodesic_shaping=0.0, shaping_scale_thief=None),
                                  seed=seed + 1)
     baseline_env = baseline_actor = None
     baseline_log = []
@@ -1138,6 +1148,10 @@ def main() -> None:
     ap.add_argument("--clip-final", type=float, default=None, help="anneal the ratio clip linearly to this value over the run's updates")
     ap.add_argument("--value-norm", action="store_true", help="train the critics on returns normalised by running per-agent moments "
                     "(TrainerConfig.value_norm; off in the reference)")
+    ap.add_argument("--geodesic-shaping", type=float, default=0.0, metavar="W", help="geodesic potential-based reward shaping of the learners with "
+                    "scale W per hop (TrainerConfig.geodesic_shaping; 0 = off, as the reference trains)")
+    ap.add_argument("--shaping-scale-thief", type=float, default=None, metavar="W", help="the thieves' shaping scale (default: that of the cops)")
+    ap.add_argument("--shaping-cap", type=int, default=None, metavar="H", help="hop counts above H count as H (default 64)")
     args = ap.parse_args()
     if args.role_training and args.gpus > 1:
         sys.exit("--role-training is a single-process mode: it cannot be combined with --gpus > 1")
@@ -1167,6 +1181,8 @@ def main() -> None:
                         query_order=args.query_order, tracked_eval=args.tracked_eval, episode_stats=args.episode_stats, fused_eval=args.fused_eval,
                         league_eval=args.league_eval, **({"role_training": True} if args.role_training else {}),
                         **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}),
+                        **({"geodesic_shaping": args.geodesic_shaping, "shaping_scale_thief": args.shaping_scale_thief, "shaping_cap": args.shaping_cap}
+                           if (args.geodesic_shaping or args.shaping_scale_thief) else {}),
                         **({"position_stats": args.position_stats} if args.position_stats is not None else {}),
                         **({"baseline_eval": True, "baseline_episodes": args.baseline_episodes} if args.baseline_eval else {}),
                         **({"navigator_eval": True, "navigator_episodes": args.navigator_episodes} if args.navigator_eval else {}),

@@ -231,6 +231,53 @@ typedef struct cat_render_nav_step_args {
 /* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
 int cat_render_nav_step(const cat_render_nav_step_args *a, void *stream);
 
+/*
+ * Geodesic potential-based reward shaping (Ng, Harada and Russell 1999): one tick of G <= CAT_NAV_MAX_NAVIGATORS shaped agents over N slots in
+ * ONE launch -- a thread per slot, which finds the cells of the slot's A agents once and then walks the G rows; workgroups of 256, no LDS, no
+ * atomics, no allocation, no synchronisation (capturable).  A row's state and outputs are touched by the thread of its slot alone.
+ * navigation.py (separation, shaping_step) defines every number; the fp32 results are bit-equal to it (this file is compiled without a*b+c
+ * contraction).
+ *
+ *   Map m = slot_map[n] (0 where slot_map is NULL); the cell of a position as in cat_render_nav_step.
+ *   separation(P, g), P an [N][A][2] f16 position array: a = the cell of P[n][agent[g]]; the smallest hops[b_j][a] over the opponents j (the
+ *   bits of opp_mask[g]) that have a cell and whose entry is not CAT_NAV_NONE; -1 if there is no a or no such opponent.
+ *   phi(g, d) = coef[g] * (float)min(d, cap) for d >= 0: one rounded multiply, the conversion is exact.
+ *   Row (g, n), d0 = hops_prev[g][n] (the separation at the start of the tick):
+ *     terminated[n] and not truncated[n] (a capture, a true terminal state): phi1 = +0.0f, defined;
+ *     terminated[n] and truncated[n] (the time limit, no property of the state): d1 = separation(final_positions, g);
+ *     otherwise d1 = separation(team_positions, g);  phi1 = phi(g, d1) where d1 >= 0.
+ *     F = +0.0f if d0 < 0 or a needed d1 < 0, else (gamma * phi1) - phi(g, d0): two rounded operations in that order.
+ *     reward_out[g * sr_g + n] += F (the add is always performed: -0.0f + +0.0f = +0.0f); shaping_out[g * ss_g + n] = F where given;
+ *     hops_prev[g][n] = separation(team_positions, g), always -- on a terminal row the NEW episode's first state (the env resets in the tick).
+ *   prime != 0: only the last assignment; final_positions, terminated, truncated, reward_out and shaping_out are not touched and may be NULL.
+ *   final_positions is read on rows with terminated and truncated both set and on no other row (those hold stale positions or NaN).
+ */
+typedef struct cat_render_nav_shape_args {
+    int32_t N, A, G, n_maps;        /* slots, agents (<= CAT_RENDER_MAX_AGENTS), shaped agents, maps of the field (1 .. CAT_NAV_MAX_MAPS) */
+    int32_t cell, cap, prime, pad;  /* cell size in pixels (>= 1), hop cap (1 .. 65534), prime mode (0 / 1) */
+    int32_t agent[CAT_NAV_MAX_NAVIGATORS];       /* shaped agent g's column of the position arrays */
+    uint32_t opp_mask[CAT_NAV_MAX_NAVIGATORS];   /* bit j: agent j is an opponent of g (not agent[g] itself, j < A) */
+    float coef[CAT_NAV_MAX_NAVIGATORS];          /* finite; negative for a cop, positive for a thief */
+    float gamma;                    /* the learner's discount factor: finite, >= 0 */
+    int32_t pad2;
+    const int32_t *grid;            /* [n_maps][4] */
+    const uint16_t *snap;           /* [sum C] */
+    const uint16_t *hops;           /* [sum C^2] */
+    const int32_t *slot_map;        /* [N] map of slot n, or NULL = map 0 */
+    const uint16_t *team_positions; /* [N][A][2] float16 bits (cat_outputs.team_positions), 4-byte aligned */
+    const uint16_t *final_positions;/* [N][A][2] float16 bits (cat_bind_final_positions), 4-byte aligned; may be NULL only if prime */
+    const uint8_t *terminated;      /* [N] */
+    const uint8_t *truncated;       /* [N] */
+    float *reward_out;              /* row g begins at element g * sr_g, N elements */
+    int64_t sr_g;                   /* >= N where G > 1 */
+    float *shaping_out;             /* row g begins at element g * ss_g, or NULL */
+    int64_t ss_g;                   /* >= N where G > 1 and shaping_out is given */
+    int32_t *hops_prev;             /* [G][N] */
+} cat_render_nav_shape_args;
+
+/* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
+int cat_render_nav_shape(const cat_render_nav_shape_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
