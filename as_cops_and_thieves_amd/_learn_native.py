@@ -42,7 +42,7 @@ MODULES = {
     "cat_rollout": (1, {"cat_rollout_pack": _ENTRY, "cat_rollout_sample": _ENTRY, "cat_rollout_post": _ENTRY, "cat_rollout_scripted": _ENTRY}),
     "cat_render": (1, {"cat_render_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]), "cat_render_positions_update": _ENTRY,
                         "cat_render_positions_ends_update": _ENTRY, "cat_render_nav_build": _ENTRY, "cat_render_nav_step": _ENTRY,
-                        "cat_render_nav_shape": _ENTRY}),
+                        "cat_render_nav_shape": _ENTRY, "cat_render_nav_spawn": _ENTRY}),
     "cat_episodes": (1, {"cat_episodes_update": _ENTRY, "cat_episodes_summary": _ENTRY, "cat_episode_windows_update": _ENTRY,
                          "cat_episodes_segment_summary": _ENTRY}),
     "cat_act": (1, {"cat_act_supported": _QUERY, "cat_act_step": _ENTRY, "cat_act_collect_step": _ENTRY, "cat_act_league_step": _ENTRY}),
@@ -1135,6 +1135,32 @@ def nav_shape(team_positions, field, agent_indices, opp_masks, coef, gamma: floa
                      team_positions.data_ptr(), _ptr(None if prime else final_positions), _ptr(None if prime else terminated),
                      _ptr(None if prime else truncated), rp or None, sr, sp or None, ss, hops_prev.data_ptr())
     _check(lib().cat_render_nav_shape(C.byref(a), _stream()), "cat_render_nav_shape")
+
+
+class NavSpawnArgs(C.Structure):
+    """include/cat_render.h cat_render_nav_spawn_args."""
+    _fields_ = [("N", C.c_int32), ("A", C.c_int32), ("n_cops", C.c_int32), ("n_maps", C.c_int32), ("cell", C.c_int32), ("pad", C.c_int32),
+                ("grid", C.c_void_p), ("free", C.c_void_p), ("hops", C.c_void_p), ("slot_map", C.c_void_p),
+                ("mask", C.c_void_p), ("band", C.c_void_p), ("uniform", C.c_void_p), ("positions", C.c_void_p), ("placed", C.c_void_p)]
+
+
+def nav_spawn(mask, uniform, band, field, n_cops: int, positions, placed) -> None:
+    """Start states of the geodesic curriculum in one launch (``cat_render_nav_spawn``; ``navigation.spawn_step`` is its definition): mask u8
+    [N], uniform fp32 [A, N], band int32 [N, 2], ``field`` as in ``nav_step``; positions f64 [N, A, 2] (rows with ``placed[n] == 1`` are
+    written, no other) and placed u8 [N] (every row)."""
+    import torch
+    A, N = uniform.shape
+    assert mask.dtype == torch.uint8 and mask.shape == (N,) and mask.is_contiguous()
+    assert uniform.dtype == torch.float32 and uniform.is_contiguous()
+    assert band.dtype == torch.int32 and band.shape == (N, 2) and band.is_contiguous()
+    assert positions.dtype == torch.float64 and positions.shape == (N, A, 2) and positions.is_contiguous()
+    assert placed.dtype == torch.uint8 and placed.shape == (N,) and placed.is_contiguous()
+    assert field.slot_map.dtype == torch.int32 and field.slot_map.shape == (N,) and field.slot_map.is_contiguous()
+    assert all(t.device == positions.device for t in (mask, uniform, band, placed, field.grid, field.free, field.hops, field.slot_map))
+    a = NavSpawnArgs(N, A, int(n_cops), field.grid.shape[0], int(field.cell), 0, field.grid.data_ptr(), field.free.data_ptr(),
+                     field.hops.data_ptr(), field.slot_map.data_ptr(), mask.data_ptr(), band.data_ptr(), uniform.data_ptr(),
+                     positions.data_ptr(), placed.data_ptr())
+    _check(lib().cat_render_nav_spawn(C.byref(a), _stream()), "cat_render_nav_spawn")
 
 
 # ---------------------------------------------------------------------------------------------- scripted opponents

@@ -567,6 +567,22 @@ extern "C" int cat_render_nav_shape(const cat_render_nav_shape_args *a, void *st
     return launched("cat_render_nav_shape");
 }
 
+extern "C" int cat_render_nav_spawn(const cat_render_nav_spawn_args *a, void *stream)
+{
+    if (!a) return npfail("NULL arguments");
+    if (a->N <= 0 || a->A <= 0) return npfail("bad dimensions");
+    if (a->A > CAT_RENDER_MAX_AGENTS) return npfail("more agents than CAT_RENDER_MAX_AGENTS");
+    if (a->n_cops < 1 || a->n_cops > a->A - 1) return npfail("n_cops must lie in 1 .. A - 1");
+    if (a->n_maps < 1 || a->n_maps > CAT_NAV_MAX_MAPS) return npfail("n_maps must lie in 1 .. 16");
+    if (a->cell < 1) return npfail("cell must be >= 1");
+    if (!a->grid || !a->free || !a->hops) return npfail("a table of the field is NULL");
+    if (!a->mask || !a->band || !a->uniform || !a->positions || !a->placed) return npfail("a required buffer is NULL");
+    if ((uintptr_t)a->positions & 7) return npfail("positions must be 8-byte aligned");
+    const unsigned per = NAV_BLOCK / SPAWN_WAVE;
+    hipLaunchKernelGGL(nav_spawn_kernel, dim3(((unsigned)a->N + per - 1) / per), dim3(NAV_BLOCK), 0, (hipStream_t)stream, *a);
+    return launched("cat_render_nav_spawn");
+}
+
 extern "C" int cat_render_abi_version(void) { return CAT_RENDER_ABI_VERSION; }
 extern "C" const char *cat_render_last_error(void) { return g_err; }
 

@@ -1,7 +1,7 @@
 // cat_render_nav.h -- the navigation kernels of cat_render.hip (included there and nowhere else): the all-pairs hop table of a batch of
 // map grids (cat_render_nav_build), one tick of the privileged "pursue" / "flee" opponents (cat_render_nav_step) and one tick of geodesic reward
-// shaping (cat_render_nav_shape).  include/cat_render.h states the rules; as_cops_and_thieves_amd/navigation.py (hops_reference,
-// navigate_step, shaping_step) is their NumPy / torch statement, which the kernels equal exactly: every value is an integer, or an fp32
+// shaping (cat_render_nav_shape) and the start states of the geodesic curriculum (cat_render_nav_spawn).  include/cat_render.h states the
+// rules; as_cops_and_thieves_amd/navigation.py (hops_reference, navigate_step, shaping_step, spawn_step) is their NumPy / torch statement, which the kernels equal exactly: every value is an integer, or an fp32
 // result of the same rounded operations.
 #pragma once
 
@@ -259,8 +259,89 @@ __global__ __launch_bounds__(NAV_BLOCK) void nav_shape_kernel(const cat_render_n
     }
 }
 
+// ---- the start-state curriculum.  A wavefront owns one slot (four slots to a workgroup); n is made provably wave-uniform, so the slot's mask,
+// band, map row and draws are scalar loads.  `mine` holds the cells chosen so far, one per lane: lane i the cell of the i-th placed agent
+// (thieves first); a uniform lane read brings one back, so no array is indexed by a variable and nothing spills.  Every load of the sweeps is
+// unconditional and clamped to the grid (k < C is part of the predicate), so the ballots run with all 64 lanes.
+constexpr int SPAWN_WAVE = 64;
+
+// is cell k a candidate of the i-th placed agent?  (i, nt, lo, hi and the lane reads of `mine` are wave-uniform)
+__device__ __forceinline__ bool spawn_candidate(int k, int i, int nt, int lo, int hi, const NavGrid &g, int mine)
+{
+    const int kk = min(k, g.C - 1);
+    bool c = k < g.C && g.free[kk] != 0;
+    for (int p = 0; p < i; ++p) c = c && kk != __builtin_amdgcn_readlane(mine, p);
+    if (i > 0 && i < nt) {
+        c = c && g.hops[(size_t)__builtin_amdgcn_readlane(mine, 0) * g.C + kk] != NAV_NONE;
+    } else if (i >= nt) {
+        uint32_t d = NAV_NONE;
+        for (int t = 0; t < nt; ++t) d = min(d, (uint32_t)g.hops[(size_t)__builtin_amdgcn_readlane(mine, t) * g.C + kk]);
+        c = c && d != NAV_NONE && d >= (uint32_t)lo && d <= (uint32_t)hi;
+    }
+    return c;
+}
+
+__global__ __launch_bounds__(NAV_BLOCK) void nav_spawn_kernel(const cat_render_nav_spawn_args a)
+{
+    const int lane = threadIdx.x & (SPAWN_WAVE - 1);
+    const int n = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (NAV_BLOCK / SPAWN_WAVE) + threadIdx.x / SPAWN_WAVE));
+    if (n >= a.N) return;
+    const int lo = a.band[2 * n], hi = a.band[2 * n + 1];
+    bool ok = a.mask[n] != 0 && lo >= 1 && lo <= hi && hi <= 65534;
+    NavGrid gr{0, 0, 0, nullptr, nullptr, nullptr};
+    if (ok) {
+        const int m = a.slot_map ? a.slot_map[n] : 0;
+        ok = m >= 0 && m < a.n_maps;
+        if (ok) {
+            const int32_t *row = a.grid + 4 * m;
+            const int w = row[0], h = row[1];
+            ok = w >= 1 && h >= 1 && (long)w * h <= CAT_NAV_MAX_CELLS;
+            if (ok) { gr.Wc = w; gr.Hc = h; gr.C = w * h; gr.free = a.free + row[2]; gr.hops = a.hops + row[3]; }
+        }
+    }
+    if (!ok) {                                              // off, unmasked, or a bad device copy of the tables: the env's own spawn
+        if (lane == 0) a.placed[n] = 0;
+        return;
+    }
+    const int A = a.A, nt = A - a.n_cops;
+    int mine = 0;
+    for (int i = 0; i < A; ++i) {
+        int cnt = 0;
+        for (int base = 0; base < gr.C; base += SPAWN_WAVE)
+            cnt += __popcll(__ballot(spawn_candidate(base + lane, i, nt, lo, hi, gr, mine)));
+        if (cnt == 0) {                                     // (uniform) nothing of this slot has been written
+            if (lane == 0) a.placed[n] = 0;
+            return;
+        }
+        const float u = a.uniform[(size_t)i * a.N + n];
+        const int j = min(cnt - 1, max(0, (int)(u * (float)cnt)));
+        int before = 0, pick = 0;
+        for (int base = 0; base < gr.C; base += SPAWN_WAVE) {
+            const bool c = spawn_candidate(base + lane, i, nt, lo, hi, gr, mine);
+            const unsigned long long bits = __ballot(c);
+            const int here = __popcll(bits);
+            if (before + here > j) {                        // the (j - before)-th set bit: the lane with that many candidates below it
+                const int rank = __popcll(bits & ((1ull << lane) - 1ull));
+                pick = base + __ffsll((long long)__ballot(c && rank == j - before)) - 1;
+                break;
+            }
+            before += here;
+        }
+        if (lane == i) mine = pick;
+    }
+    if (lane < A) {
+        const int agent = lane < nt ? a.n_cops + lane : lane - nt;
+        const int ix = mine / gr.Hc, iy = mine - ix * gr.Hc;
+        double *p = a.positions + ((size_t)n * A + agent) * 2;
+        p[0] = ((double)ix + 0.5) * (double)a.cell;
+        p[1] = ((double)iy + 0.5) * (double)a.cell;
+    }
+    if (lane == 0) a.placed[n] = 1;
+}
+
 int nbfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_nav_build", msg); }
 int nsfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_nav_step", msg); }
 int nhfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_nav_shape", msg); }
+int npfail(const char *msg) { return fail(CAT_RENDER_ERR_BAD_ARG, "cat_render_nav_spawn", msg); }
 
 }   // namespace

@@ -378,6 +378,7 @@ class VecCopsEnv:
         self.state_space = self._shared_observation_spaces
         self.max_step_count, self.time_step = max_step_count, time_step
         self._actions = torch.zeros((num_envs, len(everyone)), dtype=torch.int32, device=self.device)
+        self._spawner = None            # set_spawner: a geodesic start-state curriculum (selfplay/curriculum.py)
         self._tracker = None
         if track_episodes:
             from .episodes import EpisodeTracker
@@ -442,12 +443,38 @@ class VecCopsEnv:
         """The ``repeat`` argument of ``step`` / ``step_raw``, checked: None is the constructor's ``frame_skip``."""
         return self.frame_skip if repeat is None else check_repeat(repeat)
 
+    def set_spawner(self, spawner=None) -> None:
+        """Attach a ``selfplay.curriculum.GeodesicSpawner`` built over this env (None, the default, detaches it): ``step`` / ``step_raw``
+        (``repeat=k`` included) then respawn every slot whose episode just ended by the spawner's rule, right after the tick's launch and
+        before anything reads the new episode's first state -- the position tracker's SPAWN plane, ``observations()``, a
+        ``GeodesicShaper`` and the actors all see the start state the episode really has -- and ``reset`` without explicit positions
+        places its slots the same way.  ``out["ticks"]``, the rewards, the flags, ``winner`` and ``final_positions`` stay the terminal
+        tick's.  Slots the rule cannot serve, or whose band is off, keep the map's own spawn.  A respawned slot's ``reset_count``
+        advances twice per episode, which shifts the slot's Philox spawn stream and nothing else.  ``rollout_random`` raises ValueError
+        while a spawner is attached: the resident launch cannot respawn between its ticks.  Off: one ``is None`` test per step on the
+        host, the launches are unchanged."""
+        if spawner is not None:
+            if not self.auto_reset:
+                raise ValueError("a spawner needs auto_reset=True: it re-places the slots the tick has just reset")
+            if getattr(spawner, "N", None) != self.num_envs or getattr(spawner, "A", None) != len(self.possible_agents) or \
+                    torch.device(spawner.device) != torch.device(self.device):
+                raise ValueError(f"the spawner must be built over this env ({self.num_envs} envs, {len(self.possible_agents)} agents, {self.device})")
+        self._spawner = spawner
+
+    def _spawn_reset(self, mask, positions) -> None:
+        """What a spawner calls: one masked ``cat_reset`` launch with injected positions (no allocation, no synchronisation)."""
+        self._sim.reset(mask=mask, positions=positions)
+
     def _step_sim(self, acts, repeat: int):
         if repeat == 1:
             out = self._sim.step_fused(acts, auto_reset=self.auto_reset)
+            if self._spawner is not None:
+                self._spawner.respawn(out)
             self._track(out)
             return out
         out = self._sim.step_repeat(acts, repeat, auto_reset=self.auto_reset)
+        if self._spawner is not None:
+            self._spawner.respawn(out)
         self._track(out, out["ticks"])      # a row of a repeat call stands for ticks[n] env ticks of slot n
         return out
 
@@ -478,6 +505,8 @@ class VecCopsEnv:
         positions = None if not options else options.get("positions")
         mask = None if not options else options.get("mask")
         self._sim.reset(mask=mask, positions=positions)
+        if self._spawner is not None and positions is None:      # the reset slots start by the spawner's rule; fallbacks keep the spawn above
+            self._spawner.place_reset(mask)
         if self._tracker is not None:
             self._tracker.abandon(mask)
         return self._obs(), {a: {} for a in self.possible_agents}
@@ -551,6 +580,8 @@ class VecCopsEnv:
         ticks = int(ticks)
         if ticks < 1:
             raise ValueError("ticks must be >= 1")
+        if self._spawner is not None:
+            raise ValueError("rollout_random with a spawner attached: the resident launch cannot respawn between its ticks (step tick by tick, or set_spawner(None))")
         done, cap = 0, 65536
         keys = self._tracked_keys()
         if keys:

@@ -51,6 +51,28 @@ leaves the optimal policies as they are: over an episode the sum telescopes.
   resets inside the tick.
 * Prime mode: only the last assignment.
 * ``final_positions`` is read on rows with ``terminated`` and ``truncated`` both set and nowhere else: every other row of it is stale or NaN.
+
+A geodesic start-state curriculum on the same table -- ``spawn_step`` (torch, any device) IS its definition, and ``cat_render_nav_spawn``
+equals it exactly: every output is an integer or an exactly representable f64.  It chooses start positions such that every cop stands a
+chosen number of hops from a thief (``selfplay/curriculum.py`` hands them to the env core's masked reset).
+
+* Slot n takes part iff ``mask[n] != 0`` and its band ``(lo, hi) = band[n]`` satisfies ``1 <= lo <= hi <= 65534``; any other band means
+  "this slot keeps the map's own spawn".  Everything below is per participating slot, on its map ``slot_map[n]``.
+* The draw among ``cnt`` candidates, visited in cell-index order: rank ``j = min(cnt - 1, int(u (*) float(cnt)))`` -- one rounded fp32
+  multiply of an exactly converted integer, then truncation (``navigate_step``'s fallback has the same shape); u in [0, 1).
+* Placement order: the thieves in env order, then the cops in env order; the i-th placed agent reads ``uniform[i][n]``.
+  Thief 0 (the anchor): all free cells.  Every further thief: the free cells k with ``hops[anchor][k] != NONE`` that no earlier agent has
+  taken.  Every cop: the free cells k not taken with ``lo <= d(k) <= hi``, ``d(k)`` the smallest ``hops[b_j][k]`` over the placed thieves'
+  cells b_j, ``NONE`` entries ignored (all ``NONE``: no candidate).
+* A placed agent stands at its cell's centre ((ix + .5) cell, (iy + .5) cell): exact in f64, exact in the f16 of ``team_positions`` on
+  every map the field admits, farther than ``clearance`` from every wall by the definition of ``free``; distinct cells are ``cell`` = 16 px
+  apart against two radii of 10, so agents never overlap.
+* Fallback: an agent with ``cnt == 0`` gives ``placed[n] = 0`` and the slot's positions are NOT written (the env's own spawn stands); else
+  ``placed[n] = 1``.  Rows that do not take part give ``placed[n] = 0`` and are not written.
+* Nothing is checked about captures.  ``lo = 1`` puts a cop 16 px from a thief, inside the termination radius of 20, and the first tick
+  captures; ``lo >= 2`` never does that (32 px straight, 22.6 px diagonal).
+* The field must be the arena field (``NavField.from_env(env, arena=True)``), for the reason ``GeodesicShaper`` gives: on the plain field
+  a free cell can lie outside the enclosure the agents play in.
 """
 from __future__ import annotations
 
@@ -434,3 +456,70 @@ def shaping_step(team_positions: torch.Tensor, final_positions: Optional[torch.T
         if shaping_out is not None:
             shaping_out.copy_(F)
     hops_prev.copy_(d_now)
+
+
+BAND_MAX = 65534        # the largest hop count a band may name (NONE - 1)
+
+
+@torch.no_grad()
+def spawn_step(mask: torch.Tensor, uniform: torch.Tensor, band: torch.Tensor, field: NavField, n_cops: int,
+               positions: Optional[torch.Tensor] = None, placed: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The start-state rule of the module docstring: mask u8 / bool [N], uniform fp32 [A, N], band int32 [N, 2], ``n_cops`` in 1 .. A - 1
+    (env order: cops first).  Returns (positions f64 [N, A, 2], placed u8 [N]).  ``positions`` / ``placed``, where given, are written in
+    place: ``placed`` in every row, ``positions`` in the rows with ``placed[n] == 1`` and in no other (fresh ones are zero there)."""
+    A, N = uniform.shape
+    if not (isinstance(n_cops, (int, np.integer)) and not isinstance(n_cops, bool) and 1 <= n_cops <= A - 1):
+        raise ValueError(f"n_cops must lie in 1 .. A - 1 = {A - 1}, got {n_cops!r}")
+    assert uniform.dtype == torch.float32 and tuple(mask.shape) == (N,) and tuple(band.shape) == (N, 2) and band.dtype == torch.int32
+    dev, i64 = uniform.device, torch.int64
+    nt = A - int(n_cops)
+    row = field.grid.to(dev).to(i64)[field.slot_map.to(dev).to(i64)]                     # [N, 4]
+    Wc, Hc, coff, hoff = (row[:, c].unsqueeze(1) for c in range(4))            # [N, 1]
+    C = Wc * Hc
+    k = torch.arange(int(C.max()) if N else 1, device=dev).view(1, -1)         # every map's cells, padded to the largest grid
+    on = k < C
+    k0 = torch.where(on, k, torch.zeros_like(k))
+    free = on & (field.free.to(dev)[coff + k0] != 0)                           # [N, K]
+    hops = field.hops.to(dev)
+    rows = torch.arange(N, device=dev)
+
+    def hop_row(b):                                                            # hops[b][k] of the row's map, NONE off its grid
+        v = hops[hoff + b.view(N, 1) * C + k0].to(i64) & 0xFFFF
+        return torch.where(on, v, torch.full_like(v, NONE))
+
+    lo, hi = band[:, 0:1].to(dev).to(i64), band[:, 1:2].to(dev).to(i64)
+    ok = (mask.to(dev) != 0) & ((lo >= 1) & (lo <= hi) & (hi <= BAND_MAX)).squeeze(1)
+    taken = torch.zeros_like(free)
+    d = torch.full(free.shape, NONE, dtype=i64, device=dev)                    # the smallest hop count to a placed thief
+    reach, picks = None, []
+    for i in range(A):
+        if i == 0:
+            cand = free
+        elif i < nt:
+            cand = free & ~taken & (reach != NONE)
+        else:
+            cand = free & ~taken & (d != NONE) & (d >= lo) & (d <= hi)
+        cnt = cand.sum(dim=1)
+        j = torch.minimum((uniform[i] * cnt.to(torch.float32)).to(i64).clamp(min=0), cnt - 1)       # one rounded multiply, truncated
+        ok = ok & (cnt > 0)
+        pick = (cand & (cand.cumsum(dim=1) == (j + 1).view(N, 1))).to(torch.uint8).argmax(dim=1)     # the j-th candidate in cell order
+        picks.append(pick)
+        taken = taken.clone()
+        taken[rows, pick] = True
+        if i < nt:
+            r = hop_row(pick)
+            reach = r if i == 0 else reach
+            d = torch.minimum(d, r)
+    if positions is None:
+        positions = torch.zeros(N, A, 2, dtype=torch.float64, device=dev)
+    if placed is None:
+        placed = torch.zeros(N, dtype=torch.uint8, device=dev)
+    assert positions.dtype == torch.float64 and tuple(positions.shape) == (N, A, 2) and placed.dtype == torch.uint8 and tuple(placed.shape) == (N,)
+    order = list(range(int(n_cops), A)) + list(range(int(n_cops)))             # the env column of the i-th placed agent
+    cells = torch.stack(picks, dim=1)                                          # [N, A] in placement order
+    centre = torch.stack([cells // Hc, cells % Hc], dim=2).to(torch.float64).add(0.5).mul(float(field.cell))
+    new = positions.clone()
+    new[:, order] = centre.to(positions.device)
+    positions.copy_(torch.where(ok.view(N, 1, 1).to(positions.device), new, positions))
+    placed.copy_(ok.to(torch.uint8))
+    return positions, placed

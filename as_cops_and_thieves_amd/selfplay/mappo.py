@@ -180,8 +180,20 @@ class TrainerConfig:
                                            # ``raw_outputs``.  0 (the reference trains unshaped): no shaper, no field, no buffer, no launch
     shaping_scale_thief: Optional[float] = None     # the thieves' scale; None: ``geodesic_shaping``.  0 leaves the thieves unshaped
     shaping_cap: int = 64                  # hop counts above it count as it (1 .. 65534): the potential is bounded by scale * cap
+    spawn_curriculum: Optional[Tuple[int, int]] = None     # (lo, hi): a geodesic start-state curriculum (``selfplay/curriculum.py``).  The trainer
+                                           # builds a ``GeodesicSpawner`` on the arena field (the shaper's, where both options are on) and
+                                           # attaches it to its env: a slot whose episode ended respawns with every cop lo .. hi shortest-path hops
+                                           # from a thief -- one launch of ``cat_render_nav_spawn`` and one masked ``cat_reset`` per tick inside
+                                           # the captured rollout.  PRIVILEGED information reaches a policy only through where its episodes
+                                           # start.  The random phase then runs tick by tick.  None: nothing is built, attached or launched
+    curriculum_fraction: float = 1.0       # the first ``round(f N)`` slots take the band, the rest keep the map's own spawn
+    curriculum_adapt: Optional[Tuple[float, float]] = None  # (low, high): ``update`` moves ``hi`` with the cops' win rate since the last update
+                                           # (``GeodesicSpawner.adapt``): above ``high`` it rises by ``curriculum_step``, below ``low`` it falls
+    curriculum_step: int = 1
+    curriculum_max: int = 64               # the largest ``hi`` ``curriculum_adapt`` reaches
 
     def __post_init__(self):
+        self._check_curriculum()
         k = self.frame_skip
         if isinstance(k, bool) or not isinstance(k, int) or k < 1:
             raise ValueError(f"TrainerConfig.frame_skip must be an integer >= 1, got {k!r}")
@@ -194,6 +206,29 @@ class TrainerConfig:
         c = self.shaping_cap
         if isinstance(c, bool) or not isinstance(c, int) or not 1 <= c <= 65534:
             raise ValueError(f"TrainerConfig.shaping_cap must be an integer in 1 .. 65534, got {c!r}")
+
+    def _check_curriculum(self) -> None:
+        is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        is_num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+        band = self.spawn_curriculum
+        if band is not None:
+            if not (isinstance(band, (tuple, list)) and len(band) == 2 and all(is_int(v) for v in band) and 1 <= band[0] <= band[1] <= 65534):
+                raise ValueError(f"TrainerConfig.spawn_curriculum must be (lo, hi) with integers 1 <= lo <= hi <= 65534, got {band!r}")
+            self.spawn_curriculum = (int(band[0]), int(band[1]))
+        f = self.curriculum_fraction
+        if not is_num(f) or not 0.0 <= f <= 1.0:
+            raise ValueError(f"TrainerConfig.curriculum_fraction must be a number in 0 .. 1, got {f!r}")
+        ad = self.curriculum_adapt
+        if ad is not None:
+            if not (isinstance(ad, (tuple, list)) and len(ad) == 2 and all(is_num(v) for v in ad) and 0.0 <= ad[0] <= ad[1] <= 1.0):
+                raise ValueError(f"TrainerConfig.curriculum_adapt must be (low, high) with 0 <= low <= high <= 1, got {ad!r}")
+            if band is None:
+                raise ValueError("TrainerConfig.curriculum_adapt moves the band of spawn_curriculum, which is None")
+            self.curriculum_adapt = (float(ad[0]), float(ad[1]))
+        if not is_int(self.curriculum_step) or self.curriculum_step < 1:
+            raise ValueError(f"TrainerConfig.curriculum_step must be an integer >= 1, got {self.curriculum_step!r}")
+        if not is_int(self.curriculum_max) or not 1 <= self.curriculum_max <= 65534 or (band is not None and self.curriculum_max < band[1]):
+            raise ValueError(f"TrainerConfig.curriculum_max must be an integer in 1 .. 65534 and at least the band's hi, got {self.curriculum_max!r}")
 
     @property
     def shaping_scales(self) -> Tuple[float, float]:
@@ -839,8 +874,26 @@ class MAPPOTrainer:
         self._shapers: Dict[str, object] = {}      # geodesic_shaping: learner key -> its GeodesicShaper (all share one NavField)
         if any(self.tcfg.shaping_scales):
             self._build_shapers()
+        self._spawner = None                       # spawn_curriculum: the GeodesicSpawner attached to the env
+        self._curriculum_slots = slice(0, 0)
+        if self.tcfg.spawn_curriculum is not None:
+            self._build_spawner()
         if self.tcfg.fused_collect:
             self._check_fused_collect(on_gpu)
+
+    def _build_spawner(self) -> None:
+        """``TrainerConfig.spawn_curriculum``: a ``GeodesicSpawner`` on the arena field (the shapers' where there is one) over the first
+        ``round(curriculum_fraction N)`` slots, attached to the env; the slots are then reset once more, so that the first episodes
+        already start by the rule.  ValueError where the env cannot serve it."""
+        from .curriculum import GeodesicSpawner
+        if not hasattr(self.env, "set_spawner"):
+            raise ValueError("spawn_curriculum needs an env with set_spawner() (VecCopsEnv)")
+        lo, hi = self.tcfg.spawn_curriculum
+        field = next((s.field for s in self._shapers.values()), None)
+        self._curriculum_slots = slice(0, int(round(self.tcfg.curriculum_fraction * self.N)))
+        self._spawner = GeodesicSpawner(self.env, lo, hi, field=field, slots=self._curriculum_slots)
+        self.env.set_spawner(self._spawner)
+        self._obs, _ = self.env.reset()
 
     def _build_shapers(self) -> None:
         """``TrainerConfig.geodesic_shaping``: per learner with a shaped agent a ``GeodesicShaper`` with the learner's own discount factor and
@@ -1114,6 +1167,9 @@ class MAPPOTrainer:
             check = getattr(self.env, "check_errors", None)   # (the CPU test doubles of the env have no device)
             if check is not None:
                 check()
+        if self._spawner is not None and self.tcfg.curriculum_adapt is not None:     # (the stream is synchronised just above)
+            low, high = self.tcfg.curriculum_adapt
+            self._spawner.adapt(low, high, self.tcfg.curriculum_step, hi_max=self.tcfg.curriculum_max)
         with torch.no_grad():
             state = self.env.state()
             keep = (~self._starts).view(1, N)
@@ -1155,6 +1211,12 @@ class MAPPOTrainer:
                 out[f"shaping/{a}"] = float(mean_f[g])
             for row, a in zip(hops, shaper.agents):                        # the separations the next rollout starts from, where defined
                 out[f"geodesic_hops/{a}"] = float(row[row >= 0].float().mean()) if bool((row >= 0).any()) else float("nan")
+        if self._spawner is not None:      # with curriculum_adapt: the counters the last update's adapt read; else everything since the start
+            sp = self._spawner
+            c = sp.last if (self.tcfg.curriculum_adapt is not None and sp.last is not None) else sp.counters()
+            out["curriculum/hi"] = sp.hi
+            out["curriculum/cop_win_rate"] = c["cop_wins"] / c["ended"] if c["ended"] else float("nan")
+            out["curriculum/placed"], out["curriculum/fallbacks"] = c["placed_total"], c["requested"] - c["placed_total"]
         ep = self._episode_stats()
         if ep is not None:
             e = ep()
@@ -1225,6 +1287,8 @@ class MAPPOTrainer:
         tc = self.tcfg
         if not (tc.resident_random_phase and hasattr(self.env, "rollout_random")) or tc.random_action_roles or self._opponents:
             return 0                                 # (an opponent actor plays its policies during the learner's random phase too)
+        if self._spawner is not None:
+            return 0                                 # (the resident launch cannot respawn between its ticks: the phase runs tick by tick)
         H = tc.horizon
         end = min(rl.cfg.random_timesteps for rl in self.roles.values())
         first_update = min(rl.cfg.learning_starts for rl in self.roles.values())
@@ -1276,6 +1340,8 @@ class MAPPOTrainer:
             if rl.value_norm:           # the running moments the agent's critic was trained under: (n, mean, M2), f64
                 out[a]["vn_state"] = rl.vn_state[g].detach().cpu().clone()
         out[self.META_KEY] = {"format": "cat-mappo-3", "timestep": self.timestep, "num_rays": self.R, "recurrent": bool(self.tcfg.recurrent)}
+        if self._spawner is not None:   # where the start-state curriculum stands
+            out[self.META_KEY]["curriculum"] = {"lo": self._spawner.lo, "hi": self._spawner.hi}
         return out
 
     def load_state_dict(self, sd: dict, roles: Optional[List[str]] = None, optimizer: bool = True) -> None:
@@ -1318,6 +1384,12 @@ class MAPPOTrainer:
                           "their value networks were trained on normalised returns")
         if optimizer and roles is None:
             self.timestep = int(sd.get(self.META_KEY, {}).get("timestep", 0))
+        cur = sd.get(self.META_KEY, {}).get("curriculum") if roles is None else None    # (a copy of one role's models leaves the band alone)
+        if cur is not None and self._spawner is not None:
+            self._spawner.set_band(int(cur["lo"]), int(cur["hi"]), self._curriculum_slots)
+        elif cur is not None:
+            warnings.warn(f"the checkpoint holds a start-state curriculum (lo {cur['lo']}, hi {cur['hi']}), which a trainer with "
+                          "spawn_curriculum=None ignores: its episodes start where the map's spawn rule puts them")
 
     def param_digest(self) -> str:
         """SHA-256 over every learner's fp32 master parameters and optimiser step counts: data-parallel replicas must agree on it."""

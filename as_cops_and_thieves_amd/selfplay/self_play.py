@@ -43,7 +43,7 @@ import os
 import random
 import sys
 from pathlib import Path
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -376,6 +376,50 @@ def evaluate_league(env, actor, episodes_per_segment=None, frame_skip: int = 1, 
     if tracker is not None:
         out["positions"] = tracker.summary()
     return out
+
+
+@torch.no_grad()
+def evaluate_by_separation(env, actor, bands, episodes: int, source=None, who=None, frame_skip: int = 1, greedy: bool = False, field=None) -> Dict[str, object]:
+    """The cops' win rate as a function of the INITIAL geodesic separation -- what a checkpoint has learned, "catches from 6 hops, not from
+    30", where one win rate says nothing.  The env's slots are cut into ``len(bands)`` contiguous segments of ``episodes`` slots
+    (``env.num_envs == len(bands) * episodes``); segment s takes ``bands[s] = (lo, hi)`` through a ``GeodesicSpawner`` attached for the
+    duration (``set_band(lo, hi, slots=)``), so the first episode of every slot starts with each cop lo .. hi hops from a thief; then ONE
+    ``evaluate_league`` pass.  ``actor``: a ``LeagueActor`` over ``env``.  ``source`` (a ``MAPPOTrainer`` or a checkpoint, as in
+    ``evaluate_against_scripts``) is loaded into sets 0 .. A - 1 and plays every agent; or ``who`` ({agent: set index | "random" |
+    "chase" | "evade"}) names the players of sets loaded beforehand; with neither, the actor's own match-ups must already be these
+    segments.  ``field``: an arena ``NavField`` of the env to share.
+    Returns {"bands", "episodes", "cop_wins", "thief_wins", "timeouts" (of the first episode of every slot, lists in band order),
+    "cop_win_rate", "fallback_share" (per band the share of slots the rule could not place: they started from the map's own spawn),
+    "ticks"}.  The env's spawner is detached again afterwards, whatever happens."""
+    from .curriculum import GeodesicSpawner, check_band
+    bands = [check_band(int(lo), int(hi)) for lo, hi in bands]
+    S = len(bands)
+    if S < 1 or episodes < 1 or env.num_envs != S * episodes:
+        raise ValueError(f"evaluate_by_separation plays {S} bands of {episodes} episodes: the env must have {S * episodes} slots, not {env.num_envs}")
+    agents = list(env.possible_agents)
+    if source is not None:
+        if actor.sets < len(agents) or list(actor.agents) != agents:
+            raise ValueError(f"the actor must cover {agents} with at least {len(agents)} sets")
+        for g, a in enumerate(agents):
+            actor.load_set(g, {a: source.agent_models(a)} if isinstance(source, MAPPOTrainer) else source, a)
+        who = {a: g for g, a in enumerate(agents)}
+    bounds = [(s * episodes, (s + 1) * episodes) for s in range(S)]
+    if who is not None:
+        actor.set_matchups([(lo, hi, dict(who)) for lo, hi in bounds])
+    elif [tuple(b) for b in actor.segments] != bounds:
+        raise ValueError(f"without source or who the actor's match-ups must be the {S} segments {bounds}, not {list(actor.segments)}")
+    spawner = GeodesicSpawner(env, *bands[0], field=field)
+    for (lo, hi), (b0, b1) in zip(bands, bounds):
+        spawner.set_band(lo, hi, slots=slice(b0, b1))
+    env.set_spawner(spawner)
+    try:
+        res = evaluate_league(env, actor, frame_skip=frame_skip, greedy=greedy)
+    finally:
+        env.set_spawner(None)
+    placed = spawner.reset_placed.cpu().view(S, episodes).float()
+    return {"bands": [list(b) for b in bands], "episodes": res["episodes"], "cop_wins": res["cop_wins"], "thief_wins": res["thief_wins"],
+            "timeouts": res["timeouts"], "cop_win_rate": [c / episodes for c in res["cop_wins"]],
+            "fallback_share": [float(1.0 - p.mean()) for p in placed], "ticks": res["ticks"]}
 
 
 BASELINE_SEGMENTS = ("cops_vs_evade", "cops_vs_random", "chase_vs_thieves", "random_vs_thieves")
@@ -752,7 +796,9 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                   entropy_final: Optional[float] = None, ratio_clip_final: Optional[float] = None,
                   baseline_eval: bool = False, baseline_episodes: int = 64, navigator_eval: bool = False,
                   navigator_episodes: int = 64, geodesic_shaping: float = 0.0, shaping_scale_thief: Optional[float] = None,
-                  shaping_cap: Optional[int] = None) -> Dict[str, object]:
+                  shaping_cap: Optional[int] = None, spawn_curriculum: Optional[Tuple[int, int]] = None, curriculum_fraction: float = 1.0,
+                  curriculum_adapt: Optional[Tuple[float, float]] = None, curriculum_step: int = 1, curriculum_max: int = 64,
+                  separation_eval: Optional[List[Tuple[int, int]]] = None, separation_episodes: int = 64) -> Dict[str, object]:
     """The self-play loop.  ``resume``: continue after the highest iteration found in the archives ("latest").
     ``query_order``: the visiting order of the walls in the envs' segment queries (``VecCopsEnv``: "index" or "chipmunk").
     ``max_step_count``: 2000, what the reference's driver passes (``self_play_driver.py:34``).
@@ -789,6 +835,14 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     term of ``TrainerConfig.geodesic_shaping``; the training env is then built with ``final_positions=True`` (an ``env_factory``'s env must
     bring it along: ValueError from the trainer otherwise).  Evaluation, the archives and the booked outcomes see the env's own rewards only.
 
+    ``spawn_curriculum=(lo, hi)`` (with ``curriculum_fraction``, ``curriculum_adapt``, ``curriculum_step``, ``curriculum_max``): the geodesic
+    start-state curriculum of ``TrainerConfig.spawn_curriculum``.  ONLY the training env gets the spawner: the evaluation envs keep the map's
+    own spawn, so ``win_rates.json`` stays comparable.  Single process only (ValueError in a data-parallel job, on every rank before any
+    collective).  The joint checkpoints carry the band; a resumed run starts it from the configuration.
+    ``separation_eval=[(lo, hi), ...]``: after every iteration rank 0 runs ``evaluate_by_separation`` -- the cops' win rate as a function of
+    the initial geodesic separation -- on an env of its own with ``len(bands) * separation_episodes`` slots and appends the result to
+    ``separation.json``.  The simultaneous mode only.  Off, nothing of it is built and no random number is drawn for it.
+
     ``lr_schedule`` ("constant", "linear" with ``lr_final``, "kl_adaptive" with ``lr_kl_target``), ``entropy_final``, ``ratio_clip_final``: the
     schedules of ``RoleConfig``, put into both roles' configurations.  A role configuration that leaves ``schedule_updates`` at 0 gets the
     number of updates this call will make for it (``planned_updates``), so that a linear anneal ends with the run.  The schedule runs on
@@ -823,6 +877,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         raise ValueError("role_training is a single-process mode: multi-rank role training is not supported")
     if role_training and position_stats is not None:
         raise ValueError("position_stats writes the heatmaps of the simultaneous mode's evaluations: it cannot be combined with role_training")
+    if (spawn_curriculum is not None or separation_eval) and multi:
+        raise ValueError("spawn_curriculum / separation_eval are single-process options: a data-parallel job cannot take them")
+    if separation_eval and (role_training or separation_episodes < 1):
+        raise ValueError("separation_eval belongs to the simultaneous loop (not role_training) and needs separation_episodes >= 1")
     if role_training and tracked_eval:
         raise ValueError("role_training books its outcomes through evaluate_league (one poll per tick): it cannot be combined with tracked_eval")
 
@@ -850,6 +908,10 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     if geodesic_shaping or shaping_scale_thief:
         trainer_cfg = dataclasses.replace(trainer_cfg, geodesic_shaping=geodesic_shaping, shaping_scale_thief=shaping_scale_thief,
                                           **({} if shaping_cap is None else {"shaping_cap": shaping_cap}))
+    if spawn_curriculum is not None:
+        trainer_cfg = dataclasses.replace(trainer_cfg, spawn_curriculum=tuple(spawn_curriculum), curriculum_fraction=curriculum_fraction,
+                                          curriculum_adapt=None if curriculum_adapt is None else tuple(curriculum_adapt),
+                                          curriculum_step=curriculum_step, curriculum_max=curriculum_max)
     shaped = any(trainer_cfg.shaping_scales)
     out_dir = Path(out_dir)
     arch = {tc.cop_role_prefix: out_dir / "cops", tc.thief_role_prefix: out_dir / "thieves"}
@@ -923,7 +985,8 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                                                 recurrent=trainer_cfg.recurrent, seed=seed + 1, device=trainer.device)
     else:
         evaluator = MAPPOTrainer(eval_env, role_cfg, dataclasses.replace(trainer_cfg, graph_rollout=False, graph_update=False, fused_collect=False,
-                                                                         geodesic_shaping=0.0, shaping_scale_thief=None),
+                                                                         geodesic_shaping=0.0, shaping_scale_thief=None,
+                                                                         curriculum_adapt=None, spawn_curriculum=None),
                                  seed=seed + 1)
     baseline_env = baseline_actor = None
     baseline_log = []
@@ -941,6 +1004,14 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
         navigator_actor = LeagueActor.from_env(navigator_env, len(navigator_env.possible_agents), fused="kernel", compute_bf16=trainer_cfg.compute_bf16,
                                                normalize_inputs=trainer_cfg.normalize_inputs, recurrent=trainer_cfg.recurrent, seed=seed + 5,
                                                device=trainer.device)
+    separation_env = separation_actor = None
+    separation_log = []
+    if separation_eval and chief:  # the cops' win rate by initial geodesic separation: one segment of separation_episodes slots per band
+        from .actor import LeagueActor
+        separation_env = eval_factory(len(separation_eval) * separation_episodes, seed + 7937)
+        separation_actor = LeagueActor.from_env(separation_env, len(separation_env.possible_agents), fused="kernel", compute_bf16=trainer_cfg.compute_bf16,
+                                                normalize_inputs=trainer_cfg.normalize_inputs, recurrent=trainer_cfg.recurrent, seed=seed + 9,
+                                                device=trainer.device)
     rng = random.Random(seed)
     start = 0
     if resume:
@@ -961,8 +1032,14 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
     if navigator_env is not None and start > 0 and navigators_file.exists():
         navigator_log = json.loads(navigators_file.read_text())
 
+    separation_file = out_dir / "separation.json"
+    if separation_env is not None and start > 0 and separation_file.exists():
+        separation_log = json.loads(separation_file.read_text())
+
     def finish():
         digest = trainer.param_digest()
+        if separation_env is not None:
+            separation_env.close()
         env.close()
         eval_env.close()
         if baseline_env is not None:
@@ -1011,6 +1088,12 @@ def run_self_play(map_name: str, num_envs: int, out_dir: Path, iterations: Optio
                     navigator_log.append(dict({"iteration": it}, **b))
                     navigators_file.write_text(json.dumps(navigator_log, indent=1))
                     log("[self-play] navigators (privileged), cop win rate: " + ", ".join(f"{n} {r:.2f}" for n, r in zip(b["segments"], b["cop_win_rate"])))
+                if separation_env is not None:  # ... and what the checkpoint catches from how far: the learned policies on both sides
+                    b = evaluate_by_separation(separation_env, separation_actor, separation_eval, separation_episodes, source=trainer,
+                                               frame_skip=trainer_cfg.frame_skip)
+                    separation_log.append(dict({"iteration": it}, **b))
+                    separation_file.write_text(json.dumps(separation_log, indent=1))
+                    log("[self-play] cop win rate by initial separation: " + ", ".join(f"{lo}..{hi} {r:.2f}" for (lo, hi), r in zip(b["bands"], b["cop_win_rate"])))
                 # ---- 4. joint checkpoint into both archives (orchestration.py:225-245)
                 ck = out_dir / f"joint_iter_{it}_full_agent.pt"
                 torch.save(trainer.state_dict(), ck)
@@ -1092,7 +1175,40 @@ def init_ranks(gpus: int) -> str:
     return "nccl (RCCL)"
 
 
-def main() -> None:
+def parse_separation_bands(text: str) -> List[Tuple[int, int]]:
+    """``LO:HI,LO:HI,...`` -> [(lo, hi), ...]; ValueError for anything but integers with 1 <= lo <= hi <= 65534."""
+    from .curriculum import check_band
+    bands = []
+    for part in text.split(","):
+        lo, sep, hi = part.strip().partition(":")
+        if not sep or not lo.strip().isdigit() or not hi.strip().isdigit():
+            raise ValueError(f"--separation-eval takes LO:HI,LO:HI,..., got {text!r}")
+        bands.append(check_band(int(lo), int(hi)))
+    return bands
+
+
+def curriculum_options(args) -> dict:
+    """The ``run_self_play`` arguments of the curriculum options of the command line; ValueError where they cannot apply."""
+    out = {}
+    if args.spawn_curriculum is None:
+        if args.curriculum_adapt is not None:
+            raise ValueError("--curriculum-adapt moves the band of --spawn-curriculum, which is not given")
+    else:
+        if args.gpus > 1:
+            raise ValueError("--spawn-curriculum is a single-process option: it cannot be combined with --gpus > 1")
+        out.update(spawn_curriculum=tuple(args.spawn_curriculum), curriculum_fraction=args.curriculum_fraction, curriculum_step=args.curriculum_step,
+                   curriculum_max=args.curriculum_max)
+        if args.curriculum_adapt is not None:
+            out["curriculum_adapt"] = tuple(args.curriculum_adapt)
+    if args.separation_eval is not None:
+        if args.gpus > 1:
+            raise ValueError("--separation-eval is a single-process option: it cannot be combined with --gpus > 1")
+        out["separation_eval"] = parse_separation_bands(args.separation_eval)
+        out["separation_episodes"] = args.separation_episodes
+    return out
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--map", default="squarinth")
     ap.add_argument("--envs", type=int, default=1024)
@@ -1152,11 +1268,27 @@ def main() -> None:
                     "scale W per hop (TrainerConfig.geodesic_shaping; 0 = off, as the reference trains)")
     ap.add_argument("--shaping-scale-thief", type=float, default=None, metavar="W", help="the thieves' shaping scale (default: that of the cops)")
     ap.add_argument("--shaping-cap", type=int, default=None, metavar="H", help="hop counts above H count as H (default 64)")
-    args = ap.parse_args()
+    ap.add_argument("--spawn-curriculum", type=int, nargs=2, default=None, metavar=("LO", "HI"), help="a geodesic start-state curriculum: a training slot "
+                    "whose episode ended respawns with every cop LO .. HI shortest-path hops from a thief (TrainerConfig.spawn_curriculum; the "
+                    "evaluation envs keep the map's own spawn); not with --gpus > 1")
+    ap.add_argument("--curriculum-fraction", type=float, default=1.0, metavar="F", help="the share of the training slots that takes the band (the first ones)")
+    ap.add_argument("--curriculum-adapt", type=float, nargs=2, default=None, metavar=("LOW", "HIGH"), help="move HI with the cops' win rate between "
+                    "updates: above HIGH it rises, below LOW it falls")
+    ap.add_argument("--curriculum-step", type=int, default=1, metavar="S", help="--curriculum-adapt: hops per move")
+    ap.add_argument("--curriculum-max", type=int, default=64, metavar="H", help="--curriculum-adapt: the largest HI")
+    ap.add_argument("--separation-eval", default=None, metavar="LO:HI,LO:HI,...", help="after every iteration the cops' win rate as a function of the "
+                    "initial geodesic separation: one pass over an env cut into one segment per band, appended to separation.json")
+    ap.add_argument("--separation-episodes", type=int, default=64, help="--separation-eval: episodes (slots) per band")
+    return ap
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
+    curriculum = curriculum_options(args)
     if args.role_training and args.gpus > 1:
         sys.exit("--role-training is a single-process mode: it cannot be combined with --gpus > 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))          # plain command: start the ranks ourselves
+        sys.exit(launch_ranks(args.gpus, sys.argv[1:] if argv is None else list(argv)))          # plain command: start the ranks ourselves
     backend = None
     if args.gpus > 1:
         backend = init_ranks(args.gpus)
@@ -1183,7 +1315,7 @@ def main() -> None:
                         **({"fused_collect": True} if args.fused_collect else {}), **({"value_norm": True} if args.value_norm else {}),
                         **({"geodesic_shaping": args.geodesic_shaping, "shaping_scale_thief": args.shaping_scale_thief, "shaping_cap": args.shaping_cap}
                            if (args.geodesic_shaping or args.shaping_scale_thief) else {}),
-                        **({"position_stats": args.position_stats} if args.position_stats is not None else {}),
+                        **({"position_stats": args.position_stats} if args.position_stats is not None else {}), **curriculum,
                         **({"baseline_eval": True, "baseline_episodes": args.baseline_episodes} if args.baseline_eval else {}),
                         **({"navigator_eval": True, "navigator_episodes": args.navigator_episodes} if args.navigator_eval else {}),
                         **{k: v for k, v in (("lr_schedule", args.lr_schedule), ("lr_final", args.lr_final), ("lr_kl_target", args.lr_kl_target),

@@ -120,6 +120,11 @@ class CatSim:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def reset(self, mask: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None):
+        """One ``cat_reset`` launch: the slots of ``mask`` (u8 [N]; None: all) start a new episode, at ``positions`` (f64 [N, A, 2], without
+        the rejection sampling) where given.  With tensors of these types on the device already nothing is allocated and nothing
+        synchronises, so the call may stand inside a captured graph (``selfplay.curriculum.GeodesicSpawner`` puts it there).  It stores
+        no reward, flag or winner and writes nothing to a bound final-positions buffer; every masked slot's ``reset_count`` advances, so a
+        slot reset by the tick's auto-reset and again here advances twice per episode, which shifts its Philox spawn stream and nothing else."""
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             assert mask.shape == (self.N,)

@@ -278,6 +278,42 @@ typedef struct cat_render_nav_shape_args {
 /* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
 int cat_render_nav_shape(const cat_render_nav_shape_args *a, void *stream);
 
+/*
+ * A geodesic start-state curriculum: start positions for the masked slots such that every cop stands a chosen number of shortest-path hops
+ * from a thief, in ONE launch -- a wavefront (64 lanes) per slot, workgroups of 256 = four slots; no LDS, no atomics, no scratch, no
+ * allocation, no synchronisation (capturable).  navigation.spawn_step defines every number: cells are integers, positions exact f64.
+ *
+ *   Slot n takes part iff mask[n] != 0 and (lo, hi) = band[n] satisfies 1 <= lo <= hi <= 65534; any other band keeps the map's own spawn.  A
+ *   slot that does not take part leaves after its mask byte and band (the common case: a few slots end per tick) with placed[n] = 0.
+ *   Map m = slot_map[n] (0 where slot_map is NULL).  Agents 0 .. n_cops - 1 are the cops, the rest the thieves (the env's order).
+ *   Placement order: the thieves in env order, then the cops in env order; the i-th placed agent draws with u = uniform[i][n] in [0, 1):
+ *     among cnt candidates in cell-index order the one at rank j = min(cnt - 1, (int)(u * (float)cnt)) -- one rounded fp32 multiply.
+ *     Thief 0 (the anchor): every free cell.  A further thief: the free cells k with hops[anchor][k] != CAT_NAV_NONE not taken by an earlier
+ *     agent.  A cop: the free cells k not taken with lo <= d(k) <= hi, d(k) the smallest hops[b_j][k] over the placed thieves' cells b_j,
+ *     CAT_NAV_NONE entries ignored (all CAT_NAV_NONE: no candidate).
+ *   Per agent the wave sweeps the map's cells 64 at a time, a lane a cell (free and the thieves' hop rows are read coalesced); the predicate
+ *   goes through a ballot, a chunk's count is its popcount; a second sweep stops in the chunk where the running count passes j and takes its
+ *   (j - before)-th set bit.  The cells chosen so far live one per lane and are read back with a lane read.
+ *   cnt == 0 for any agent: placed[n] = 0 and positions[n] is NOT written.  Otherwise placed[n] = 1 and positions[n][agent] = the cell's
+ *   centre ((ix + .5) cell, (iy + .5) cell).  Nothing is checked about captures (lo = 1 puts a cop inside the termination radius).
+ */
+typedef struct cat_render_nav_spawn_args {
+    int32_t N, A, n_cops, n_maps;   /* slots, agents (<= CAT_RENDER_MAX_AGENTS), cops (1 .. A - 1), maps of the field (1 .. CAT_NAV_MAX_MAPS) */
+    int32_t cell, pad;              /* cell size in pixels (>= 1) */
+    const int32_t *grid;            /* [n_maps][4] */
+    const uint8_t *free;            /* [sum C] */
+    const uint16_t *hops;           /* [sum C^2] */
+    const int32_t *slot_map;        /* [N] map of slot n, or NULL = map 0 */
+    const uint8_t *mask;            /* [N] */
+    const int32_t *band;            /* [N][2] lo, hi */
+    const float *uniform;           /* [A][N] in [0, 1) */
+    double *positions;              /* [N][A][2], 8-byte aligned (cat_reset's positions); rows with placed[n] == 0 are not written */
+    uint8_t *placed;                /* [N], every row written */
+} cat_render_nav_spawn_args;
+
+/* An entry added after ABI version 1 was fixed (the entries and structs above are unchanged). */
+int cat_render_nav_spawn(const cat_render_nav_spawn_args *a, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
